@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- SSFM sample*steps/s on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|c2|c3|c4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload auto|c2|c3|c4] [--dump-outputs DIR]
 
 One bench "step" = one complete pass of the workload over its synthetic input, resident in HBM when the timed region
 starts (each timed step restores the input with a device-to-device copy, ~1e-3 of a step, so that every step propagates
@@ -30,6 +30,10 @@ as a child, passes on the ONE JSON line of the child's rank 0 and exits with the
 stdout carries the JSON line and nothing else: every rank points file descriptor 1 at stderr before any library is loaded (RCCL prints a
 five-line version banner and gloo its connection report on the C-level stdout) and keeps a private duplicate of the real stdout for the
 line; a self-launching parent also filters its child's stdout down to the last JSON line.
+
+--dump-outputs DIR: after the timed steps rank 0 writes the fields the timed path returned in its last step (the result of every step: each one
+starts from the same input) to DIR as float32 .npy files, a seeded sample of the samples when the whole would exceed 64 MB (dump_outputs).  The
+inputs are seeded, so two builds run with the same arguments can be compared output for output.
 
 CPU placement: before anything touches a GPU every rank pins itself (os.sched_setaffinity) to the cores of its GPU's NUMA node
 (/sys/class/drm/card*/device/numa_node -> /sys/devices/system/node/nodeK/cpulist), split between the ranks that share the node; the set is
@@ -72,7 +76,48 @@ def parse_args(argv=None):
     ap.add_argument("--launch-timeout", type=float, default=600.0,
                     help="wall-clock budget [s] of a self-launched multi-rank run: beyond it the ranks' process group is killed, what every rank last "
                          "logged is printed, and the exit code is 124 (0 = no limit)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the fields the timed path returned in its last step to DIR as float32 .npy files (see dump_outputs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup < 0:
+        ap.error("--warmup must not be negative")
+    if args.dump_outputs is not None:
+        args.dump_outputs = os.path.abspath(args.dump_outputs)       # (a self-launched child sees the same directory)
+    return args
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6                 # all files of one --dump-outputs together
+DUMP_SAMPLE_SEED = 20240
+
+
+def dump_outputs(out_dir, fields):
+    """Write what the timed path computed in its last step: `fields` (n_fields, N_POL, n) complex64, the propagated fields in unit order.
+    field.npy: float32 (n_fields, N_POL, m, 2), real and imaginary parts.  When all n samples do not fit in DUMP_MAX_BYTES, m < n samples at
+    the same seeded positions of every row, listed (ascending) in sample_index.npy as float64; otherwise m = n and there is no index file.
+    Returns the names written."""
+    import numpy as np
+    fields = np.asarray(fields)
+    n_fields, n_pol, n = fields.shape
+    m = n
+    if n_fields * n_pol * n * 8 > DUMP_MAX_BYTES:
+        m = 1
+        while n_fields * n_pol * (2 * m) * 8 + 2 * m * 8 <= DUMP_MAX_BYTES and 2 * m <= n:
+            m *= 2
+    os.makedirs(out_dir, exist_ok=True)
+    names = []
+    if m < n:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, m, replace=False))
+        fields = fields[..., idx]
+        np.save(os.path.join(out_dir, "sample_index.npy"), idx.astype(np.float64))
+        names.append("sample_index")
+    y = np.empty((n_fields, n_pol, m, 2), np.float32)
+    y[..., 0] = fields.real
+    y[..., 1] = fields.imag
+    np.save(os.path.join(out_dir, "field.npy"), y)
+    names.append("field")
+    return names
 
 
 _REAL_STDOUT = None
@@ -705,6 +750,7 @@ def main():
     # the only "exchange" of this path: the gather of the results at the end, in GPU memory (RCCL over xGMI)
     gather_ms = None
     collectives = None
+    gathered = g = None
     checks = powers
     if distributed and backend == "nccl":
         def gather():
@@ -720,7 +766,7 @@ def main():
         progress(f"gather done: {gather_ms:.2f} ms")
         collectives = dict(od.COLLECTIVES)
         if rank == 0:
-            g = got.to_host()
+            g = gathered = got.to_host()
             checks = [float(np.mean(np.abs(g[u].astype(np.complex128)) ** 2)) for u in range(total_fields)]
             mine = od.shard(total_fields, 0, world)
             for k, u in enumerate(mine):                                                      # the gathered block holds this rank's own results in place
@@ -828,6 +874,12 @@ def main():
         if world == 1 and args.cpu_manycore > 0:
             cpu_many = cpu_baseline_manycore(dt, fibre, args.cpu_manycore, max(8, args.cpu_steps // 4))
 
+    dumped = None
+    if rank == 0 and args.dump_outputs is not None:
+        # every field of the job once gathered to rank 0; without the RCCL gather (diagnostic backends) rank 0's own fields
+        dumped = {"dir": args.dump_outputs, "files": dump_outputs(args.dump_outputs, g if gathered is not None else out),
+                  "fields": "all" if gathered is not None or world == 1 else "rank 0's own"}
+
     if distributed:
         dist.barrier()
         dist.destroy_process_group()
@@ -879,6 +931,7 @@ def main():
         **({"secondary_big_field": big} if big else {}),
         **extra,
         "cpu_affinity": cpu_affinity,
+        **({"dumped_outputs": dumped} if dumped else {}),
     })
 
 

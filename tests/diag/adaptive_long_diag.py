@@ -2,7 +2,9 @@
 (fuzz_cases.truth_adaptive_f64) and of the oracle side by side -- they agree to 1e-6 until the LAST, clamped step, whose length follows the float32 rounding of the
 accumulated z (devices.py:1196: min(h, L - z)): 3e-6 km of fibre, 8e-5 rad of dispersion at the edge of a 512 GHz band.      python tests/diag/adaptive_long_diag.py"""
 import os, sys
-sys.path.insert(0, '/root/repo'); sys.path.insert(0, '/root/repo/tests'); sys.path.insert(0, '/root/repo/tests/diag')
+_HERE = os.path.dirname(os.path.abspath(__file__))
+for _p in (os.path.dirname(os.path.dirname(_HERE)), os.path.dirname(_HERE), _HERE):
+    sys.path.insert(0, _p)
 import numpy as np
 import opticomlib_amd as oa
 from opticomlib_amd import workloads

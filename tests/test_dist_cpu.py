@@ -196,3 +196,32 @@ def test_bench_maps_ranks_to_numa_nodes_through_the_visible_devices_mask():
     vis = [nodes[k] for k in bench.visible_gpu_order(8, {"HIP_VISIBLE_DEVICES": "4,5"})]
     assert bench.plan_affinity(0, 2, vis, cpus, set(range(128))) == set(range(64, 96))
     assert bench.plan_affinity(1, 2, vis, cpus, set(range(128))) == set(range(96, 128))
+
+
+def test_bench_dump_outputs_writes_float_arrays_within_the_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: the whole result when it fits, else the same seeded sample positions of every row; float32 / float64 only."""
+    sys.path.insert(0, ROOT)
+    import bench
+    f = (np.random.default_rng(5).standard_normal((3, 2, 4096)) + 1j * np.random.default_rng(6).standard_normal((3, 2, 4096))).astype(np.complex64)
+    assert bench.dump_outputs(str(tmp_path / "all"), f) == ["field"]
+    y = np.load(tmp_path / "all" / "field.npy")
+    assert y.dtype == np.float32 and y.shape == (3, 2, 4096, 2)
+    np.testing.assert_array_equal(y[..., 0] + 1j * y[..., 1], f)
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 3 * 2 * 4096 * 8 // 5)
+    for d in ("s1", "s2"):
+        assert bench.dump_outputs(str(tmp_path / d), f) == ["sample_index", "field"]
+        assert sum(os.path.getsize(tmp_path / d / n) for n in os.listdir(tmp_path / d)) <= bench.DUMP_MAX_BYTES
+    idx = np.load(tmp_path / "s1" / "sample_index.npy")
+    assert idx.dtype == np.float64 and np.all(np.diff(idx) > 0)
+    np.testing.assert_array_equal(idx, np.load(tmp_path / "s2" / "sample_index.npy"))
+    y = np.load(tmp_path / "s1" / "field.npy")
+    assert y.dtype == np.float32 and y.shape == (3, 2, idx.size, 2)
+    np.testing.assert_array_equal(y[..., 0] + 1j * y[..., 1], f[..., idx.astype(np.int64)])
+
+
+def test_bench_steps_must_be_positive():
+    sys.path.insert(0, ROOT)
+    import bench
+    assert bench.parse_args(["--steps", "3", "--warmup", "0"]).steps == 3
+    with pytest.raises(SystemExit):
+        bench.parse_args(["--steps", "0"])

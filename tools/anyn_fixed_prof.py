@@ -1,6 +1,6 @@
 """Where the fixed costs of a FIBER() call on a long length that is not a power of two go (cProfile of 2-step calls: transfers and pinned allocations, 2.3 ms).  GPU box."""
 import os, sys, time, cProfile, pstats
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
 import opticomlib_amd as oa
 from opticomlib_amd import workloads

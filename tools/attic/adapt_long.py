@@ -1,6 +1,6 @@
 import os, sys, time
 import numpy as np
-sys.path.insert(0, '/root/repo')
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from opticomlib_amd import _lib, devices, workloads
 n = 1 << 20; dt = 1.0 / (16 * 32e9)
 a = workloads.qpsk_field(n, seed=1, power_w=10e-3).astype(np.complex64)
