@@ -31,6 +31,12 @@
  *   utils.py:1791-1981 (DAC: pulses, upfir)        ssfm_load_pulse / _load_padded / _load_symbols, ssfm_table_from_field,
  *                                                  ssfm_apply_table, ssfm_device_axpb (real part: `is_complex` flag)
  *   devices.py:480-510 (LASER), :762-778 (MZM)     ssfm_laser (+ ssfm_device_cumsum, ssfm_device_reduce), ssfm_mzm
+ *   devices.py:1635-1868 (GET_EYE)                ssfm_eye_prepare (truncate, np.roll), ssfm_eye_resample_stage (scipy.signal.resample around
+ *                                                  ssfm_chirp_fourier), ssfm_eye_estimate (KMeans, shortest_int, find_nearest; with
+ *                                                  ssfm_device_sort_f64), ssfm_eye_levels (masked mean / std, gaussian_kde argmin)
+ *   devices.py:1871-1891 (SAMPLER), ook.py:63-133  ssfm_device_sample (x[instant::sps], and `x > rth` as uint8)
+ *     (ook.DSP decision)
+ *   ook.py:135-220 (BER_analizer 'counter')        ssfm_device_count_diff
  *   (none: NumPy arrays are the reference's only   ssfm_device_alloc / _free / _copy / _convert / _add
  *     data format)                                 -- device-resident signals between calls
  *
@@ -451,6 +457,31 @@ SSFM_API int ssfm_set_profiling(ssfm_plan* plan, int mode);
 SSFM_API int ssfm_plan_set_tag(ssfm_plan* plan, int which, uint64_t tag);
 SSFM_API int ssfm_plan_get_tag(ssfm_plan* plan, int which, uint64_t* tag);
 SSFM_API int ssfm_kernel_times(ssfm_plan* plan, int64_t counts[2], double total_ms[2]);
+
+/* ---- the OOK receiver (csrc/eye.hip): DEVICE pointers, float64, n <= 2^21.  Every call runs on the default stream of `device` and has
+ * finished its work when it returns (as the library's other default-stream calls), so its outputs may go to any plan's stream. ---- */
+/* Stable in-place sort of n doubles in ascending order (np.sort(kind="stable"); -0 and +0 compare equal). */
+SSFM_API int ssfm_device_sort_f64(int device, double* keys, int64_t n);
+/* out[i] = Re(sig + noise)[(i - shift) mod n] over the first n samples (noise nullable; `is_complex`: complex128 inputs). */
+SSFM_API int ssfm_eye_prepare(int device, const void* sig, const void* noise, int is_complex, int64_t n, int64_t shift, double* out);
+/* scipy.signal.resample(x, m) of a real x of n samples, around the caller's transform: stage 0 x (float64, n) -> complex128;
+ * stage 1 the spectrum X (n) -> Y (m); stage 2 Re(ifft(Y)) (complex128, m) -> float64 times m / n. */
+SSFM_API int ssfm_eye_resample_stage(int device, int stage, const void* src, int64_t n, void* dst, int64_t m);
+/* The eye's levels and crossings from y (n samples, t = tgrid[i mod period], tgrid a HOST array of `period` values) and the
+ * pre-resample values yset: the state block (>= 64 doubles, HOST) and the number of blocking host transfers it took (the t-grid upload
+ * and the state reads: 2 unless a two-means needs more than 24 Lloyd steps). */
+SSFM_API int ssfm_eye_estimate(int device, const double* y, int64_t n, const double* tgrid, int64_t period, const double* yset, int64_t nset,
+                               double* out, int64_t n_out, int64_t* round_trips);
+/* Moments of the clusters above / below y_center and the KDE argmin over linspace(mu0, mu1, npts) of the central samples
+ * (index mod period in [k_lo, k_hi)): the state block (HOST). */
+SSFM_API int ssfm_eye_levels(int device, const double* y, int64_t n, int64_t period, int64_t k_lo, int64_t k_hi, double y_center, int npts,
+                             double* out, int64_t n_out);
+/* With v = x[start + j step] (+ noise[start + j step] when noise is not NULL): vals[j] = v and / or bits[j] = (v > thr), j < count
+ * (either output nullable). */
+SSFM_API int ssfm_device_sample(int device, const double* x, const double* noise, int64_t start, int64_t step, int64_t count, double thr,
+                                double* vals, unsigned char* bits);
+/* *out = number of i < n with a[i] != b[i] (uint8 arrays). */
+SSFM_API int ssfm_device_count_diff(int device, const unsigned char* a, const unsigned char* b, int64_t n, int64_t* out);
 
 #ifdef __cplusplus
 }

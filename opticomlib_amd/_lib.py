@@ -84,6 +84,13 @@ SYMBOLS = {
     "ssfm_device_shift": (_I, [_I, _VP, _VP, _I64, _I, _D, _D]),
     "ssfm_prbs": (_I, [_I, _VP, _I64, _I, C.c_uint32, C.POINTER(C.c_uint32)]),
     "ssfm_load_qpsk": (_I, [_VP, _I64, _I, _VP, _I64, _I]),
+    "ssfm_device_sort_f64": (_I, [_I, _VP, _I64]),
+    "ssfm_eye_prepare": (_I, [_I, _VP, _VP, _I, _I64, _I64, _VP]),
+    "ssfm_eye_resample_stage": (_I, [_I, _I, _VP, _I64, _VP, _I64]),
+    "ssfm_eye_estimate": (_I, [_I, _VP, _I64, _VP, _I64, _VP, _I64, _VP, _I64, C.POINTER(_I64)]),
+    "ssfm_eye_levels": (_I, [_I, _VP, _I64, _I64, _I64, _I64, _D, _I, _VP, _I64]),
+    "ssfm_device_sample": (_I, [_I, _VP, _VP, _I64, _I64, _I64, _D, _VP, _VP]),
+    "ssfm_device_count_diff": (_I, [_I, _VP, _VP, _I64, C.POINTER(_I64)]),
 }
 
 

@@ -11,6 +11,7 @@ There is deliberately NO CPU fallback: sizes the HIP path does not cover raise
 """
 from __future__ import annotations
 
+import ctypes as C
 import os
 import threading
 import functools
@@ -20,7 +21,7 @@ from collections import OrderedDict
 import numpy as np
 
 from . import _lib, accuracy
-from .typing import NULL, binary_sequence, electrical_signal, gv, optical_signal
+from .typing import NULL, binary_sequence, electrical_signal, eye, gv, optical_signal
 
 _F32 = np.float32
 _CACHE_LOCK = threading.RLock()       # guards the module's small caches (plans, operators, grid powers, chirps) against concurrent callers
@@ -1440,5 +1441,172 @@ def MZM(op_input: optical_signal, el_input, bias: float = 0.0, Vpi: float = 5.0,
     output = _wrap_out(optical_signal, out_s, NULL if out_n is None else out_n, n_pol=op_input.n_pol)
     if BW is not None:
         output = _bpf_on_grid(output, BW, grid, device)
+    output.execution_time = time.time() - t0
+    return back(output)
+
+
+# ------------------------------------------------------------------ the OOK receiver: GET_EYE and SAMPLER (csrc/eye.hip)
+# the state block of ssfm_eye_estimate / ssfm_eye_levels, in the order of eye.hip `enum Slot`
+_EYE_SLOTS = ("C0 C1 T0 Y0 T1 Y1 IT1 DONE1 IT2 DONE2 VM NBOT NTOP TOPSTART BOT0 BOT1 TOP0 TOP1 V25 V75 STATE0 STATE1 YCT YC YL YR NBAND TMEAN MIND "
+              "MU0 MU1 SD0 SD1 N0 N1 NC CMEAN CVAR INVH KDE SINGULAR").split()
+_S = {name: k for k, name in enumerate(_EYE_SLOTS)}
+_EYE_MAX_N = 1 << 21
+
+
+def _real_sum_device(input, n: int, shift: int, dev: int) -> "_lib.DeviceArray":
+    """``np.roll(Re(signal + noise)[:n], shift)`` as a float64 device array (one pass; host inputs are uploaded once)."""
+    raws = [input._raw("signal")] + ([] if input._raw("noise") is NULL else [input._raw("noise")])
+    cplx = any(np.iscomplexobj(np.empty(0, a.dtype)) for a in raws)
+    arrs = [_dev_array(a, np.complex128 if cplx else np.float64, dev) for a in raws]
+    out = _lib.DeviceArray((n,), np.float64, dev)
+    _lib._check(_lib.load().ssfm_eye_prepare(dev, _lib._VP(arrs[0].ptr), _lib._VP(arrs[1].ptr) if len(arrs) > 1 else None, int(cplx), n, int(shift),
+                                             _lib._VP(out.ptr)), "ssfm_eye_prepare")
+    return out
+
+
+def _resample_device(x: "_lib.DeviceArray", m: int, dev: int) -> "_lib.DeviceArray":
+    """``scipy.signal.resample(x, m)`` of a real device signal: the forward and inverse float64 transforms of ``_ChirpZ`` with the
+    spectrum cut or zero-padded between them (csrc/eye.hip k_respectrum)."""
+    n = x.size
+    _, hi = _lib.supported_log2n(_lib.C128, direct=True)
+    if 2 * max(n, m) - 1 > (1 << hi):
+        raise ValueError(f"the device transform takes 2 ... 2^{hi - 1} samples, the resampling needs {n} -> {m} (there is no CPU fallback)")
+    lib = _lib.load()
+    X = _lib.DeviceArray((1, n), np.complex128, dev)
+    _lib._check(lib.ssfm_eye_resample_stage(dev, 0, _lib._VP(x.ptr), n, _lib._VP(X.ptr), n), "ssfm_eye_resample_stage")
+    with _ChirpZ(n, 1, dev) as eng:
+        eng.fourier(X, False)
+    Y = _lib.DeviceArray((1, m), np.complex128, dev)
+    _lib._check(lib.ssfm_eye_resample_stage(dev, 1, _lib._VP(X.ptr), n, _lib._VP(Y.ptr), m), "ssfm_eye_resample_stage")
+    with _ChirpZ(m, 1, dev) as eng:
+        eng.fourier(Y, True)
+    y = _lib.DeviceArray((m,), np.float64, dev)
+    _lib._check(lib.ssfm_eye_resample_stage(dev, 2, _lib._VP(Y.ptr), n, _lib._VP(y.ptr), m), "ssfm_eye_resample_stage")
+    return y
+
+
+def _nearest(levels: np.ndarray, v: float) -> float:
+    return float(levels[np.argmin(np.abs(levels - v))])
+
+
+def GET_EYE(input, nslots: int = 4096, sps_resamp: int = None, *, device=None, _grid=None):
+    """Eye-diagram estimator, reference ``devices.py:1635-1868``: the same truncation, roll, resampling, levels, crossings, cluster
+    moments and KDE threshold, computed on the GPU (csrc/eye.hip).  Returns :class:`~opticomlib_amd.typing.eye`.
+
+    Two-means: a deterministic Lloyd iteration (1-D from (min, max), 2-D from the 25-75 % band split at its mean t) replaces
+    sklearn's KMeans(n_init=10); for an open eye both reach the same fixed point (sklearn stops within its ``tol`` of it).
+
+    Host round trips per call on a device-resident signal (``eye.round_trips``), every blocking host wait counted: the signal's
+    preparation (1); without ``sps_resamp`` nothing more before the estimate, with it the three resampling stages and the two transforms (5); the estimate
+    (the t-grid upload and one state read: 2, and one more read per 24 Lloyd steps beyond the first 24 of a two-means); the
+    moments and threshold (one state read: 1).  So 4 without resampling and 9 with it, for an eye whose two-means converge in
+    24 steps."""
+    t0 = time.time()
+    input, grid, _ = _adopt(input, "electrical_signal")
+    grid = grid if _grid is None else _grid                 # (DSP: the grid of the caller's library)
+    if not isinstance(input, electrical_signal):
+        input = electrical_signal(input)
+    if input.ndim != 1:
+        raise ValueError("`input` must be a 1D-array.")
+    sps, dt = int(grid.sps), grid.dt
+    size = input.size - input.size % (2 * sps)
+    nslots = min(size // sps, int(nslots))
+    if nslots < 2 or nslots % 2:
+        raise ValueError(f"GET_EYE needs an even number of slots >= 2, got {nslots} (signal of {input.size} samples at sps={sps})")
+    n0 = nslots * sps
+    s = int(sps_resamp) if sps_resamp else sps
+    n = nslots * s
+    if max(n0, n) > _EYE_MAX_N:
+        raise ValueError(f"GET_EYE on the device takes up to 2^21 samples, got {max(n0, n)} (there is no CPU fallback)")
+    dev = default_device() if device is None else int(device)
+    lib = _lib.load()
+    x0 = _real_sum_device(input, n0, -sps // 2 + 1, dev)
+    y = _resample_device(x0, n, dev) if sps_resamp else x0
+    waits = 1 + (5 if sps_resamp else 0)                    # ssfm_eye_prepare; the three stages and the two transforms
+    tg = np.linspace(-1, 1 - 1 / s, 2 * s)
+    st = np.zeros(64)
+    trips = _lib._I64(0)
+    _lib._check(lib.ssfm_eye_estimate(dev, _lib._VP(y.ptr), n, _lib._ptr(tg), 2 * s, _lib._VP(x0.ptr), n0, _lib._ptr(st), st.size, C.byref(trips)),
+                "ssfm_eye_estimate")
+    S = lambda name: float(st[_S[name]])
+    for part, count in (("upper", S("NTOP")), ("lower", S("NBOT"))):
+        if count < 2:
+            raise ValueError(f"Computed lag ({int(count) // 2}) must be at least 1: the {part} half of the eye holds {int(count)} samples.")
+    d = {"sps": sps, "dt": dt, "y": y, "_nslots": nslots, "execution_time": 0.0}
+    if sps_resamp:
+        d["sps_resamp"] = int(sps_resamp)
+    d["top_int"] = np.array((S("TOP0"), S("TOP1")))
+    d["bot_int"] = np.array((S("BOT0"), S("BOT1")))
+    if S("NBAND") >= 2:
+        c = np.array([[S("T0"), S("Y0")], [S("T1"), S("Y1")]])
+        left, right = np.argmin(c[:, 0]), np.argmax(c[:, 0])
+        t_left, t_right, t_c = _nearest(tg, c[left, 0]), _nearest(tg, c[right, 0]), _nearest(tg, c[:, 0].mean())
+        d.update(y_left=S("YL"), y_right=S("YR"), _v25=S("V25"), _v75=S("V75"))
+    else:                                                   # the reference's `except ValueError` branch
+        t_left, t_right, t_c = -0.5, 0.5, 0.0
+        d.update(y_left=None, y_right=None, _v25=None, _v75=None)
+    t_dist = t_right - t_left
+    t_span0, t_span1 = t_c - 0.05 * t_dist, t_c + 0.05 * t_dist
+    d.update(t_left=t_left, t_right=t_right, t_opt=t_c, t_dist=t_dist, t_span0=t_span0, t_span1=t_span1, _y_center=S("YC"))
+    k_c = int(np.abs(tg - t_c).argmin())                    # the first index of the minimum of |t - t_center| lies in the first period
+    instant = k_c - s // 2 + 1
+    d["i"] = int(instant / sps_resamp * sps) if sps_resamp else int(instant)
+    ks = np.nonzero((t_span0 < tg) & (tg < t_span1))[0]
+    k_lo, k_hi = (int(ks[0]), int(ks[-1]) + 1) if ks.size else (0, 0)
+    lv = np.zeros(64)
+    _lib._check(lib.ssfm_eye_levels(dev, _lib._VP(y.ptr), n, 2 * s, k_lo, k_hi, S("YC"), 500, _lib._ptr(lv), lv.size), "ssfm_eye_levels")
+    L = lambda name: float(lv[_S[name]])
+    mu0, mu1, s0, s1 = L("MU0"), L("MU1"), L("SD0"), L("SD1")
+    d.update(mu0=mu0, mu1=mu1, s0=s0, s1=s1)
+    d["threshold"] = None if L("SINGULAR") else float(np.linspace(mu0, mu1, 500)[int(L("KDE"))])
+    with np.errstate(divide="ignore", invalid="ignore"):
+        d["er"] = 10 * np.log10(mu1 / mu0) if mu0 > 0 else np.inf if mu0 == 0 else np.nan
+    d["eye_h"] = mu1 - 3 * s1 - mu0 - 3 * s0
+    d["round_trips"] = waits + int(trips.value) + 1
+    d["execution_time"] = time.time() - t0
+    return eye(**d)
+
+
+def _slice_count(n: int, instant: int, step: int):
+    start, stop, step = slice(int(instant), None, int(step)).indices(n)
+    return start, len(range(start, stop, step))
+
+
+def _sample_device(a, instant: int, step: int, dev: int, thr=None, noise=None):
+    """``a[instant::step]`` of a float64 array (host or device) gathered on the device; with ``thr`` the uint8 decision
+    ``a + noise > thr`` at those samples instead (``noise``: None or a float64 array of the same length)."""
+    x = _dev_array(a, np.float64, dev)
+    nz = None if noise is None else _dev_array(noise, np.float64, dev)
+    start, count = _slice_count(x.size, instant, step)
+    out = _lib.DeviceArray((max(count, 1),), np.uint8 if thr is not None else np.float64, dev)
+    vals, bits = (None, _lib._VP(out.ptr)) if thr is not None else (_lib._VP(out.ptr), None)
+    _lib._check(_lib.load().ssfm_device_sample(dev, _lib._VP(x.ptr), None if nz is None else _lib._VP(nz.ptr), start, int(step), count,
+                                               float(thr or 0.0), vals, bits), "ssfm_device_sample")
+    if count == 0:
+        return np.empty(0, np.uint8 if thr is not None else np.float64)
+    return out
+
+
+def SAMPLER(input, instant: int, *, device=None):
+    """Digital sampler, reference ``devices.py:1871-1891``: ``input[instant::gv.sps]`` of signal and noise, gathered on the GPU
+    (real signals; a complex signal is sliced where it lies)."""
+    t0 = time.time()
+    input, grid, back = _adopt(input, "electrical_signal")
+    if not isinstance(input, electrical_signal):
+        input = electrical_signal(input)
+    dev = default_device() if device is None else int(device)
+    sps = int(grid.sps)
+    outs = []
+    for a in (input._raw("signal"), input._raw("noise")):
+        if a is NULL:
+            outs.append(NULL)
+        elif np.iscomplexobj(np.empty(0, a.dtype)):
+            outs.append((a.to_host() if _on_device(a) else np.asarray(a))[instant::sps])
+        else:
+            outs.append(_sample_device(a, instant, sps, dev))
+    if any(isinstance(o, np.ndarray) for o in outs):
+        output = electrical_signal(*[o.to_host() if _on_device(o) else o for o in outs])
+    else:
+        output = _wrap_out(electrical_signal, outs[0], outs[1])
     output.execution_time = time.time() - t0
     return back(output)

@@ -480,3 +480,53 @@ class optical_signal:
     def __repr__(self):
         where = " [device]" if self.on_device else ""
         return f"optical_signal(n_pol={self.n_pol}, size={self.size}, dtype={self._raw('signal').dtype}, noise={'NULL' if self._raw('noise') is NULL else 'array'}){where}"
+
+
+class eye:
+    """Eye-diagram parameters: what ``GET_EYE`` returns, with the reference's attribute names (``typing.py`` class ``eye``; no ``plot``).
+
+    ``y`` (the possibly resampled, rolled signal) stays on the GPU until it is read; ``t``, ``y_25_75``, ``y_top`` and ``y_bot`` are
+    formed from it on first access (NaN outside their masks, as in the reference)."""
+
+    y = _LazyArray()
+
+    def __init__(self, **kw):
+        y = kw.pop("y", None)
+        self.__dict__.update(kw)
+        self.y = y
+        self._cache = {}
+
+    def _tgrid(self):
+        s = getattr(self, "sps_resamp", None) or self.sps
+        return np.linspace(-1, 1 - 1 / s, 2 * s)
+
+    def _masked(self, name, keep):
+        if name not in self._cache:
+            y = self.y.copy()
+            y[~keep(y)] = np.nan
+            self._cache[name] = y
+        return self._cache[name]
+
+    @property
+    def t(self):
+        if "t" not in self._cache:
+            self._cache["t"] = np.kron(np.ones(self._nslots // 2), self._tgrid())
+        return self._cache["t"]
+
+    @property
+    def y_25_75(self):
+        if self._v25 is None:                              # the fallback branch: no band
+            return None
+        return self._masked("y_25_75", lambda y: (y > self._v25) & (y < self._v75))
+
+    @property
+    def y_top(self):
+        return self._masked("y_top", lambda y: (y > self._y_center) & (self.t_span0 < self.t) & (self.t < self.t_span1))
+
+    @property
+    def y_bot(self):
+        return self._masked("y_bot", lambda y: (y < self._y_center) & (self.t_span0 < self.t) & (self.t < self.t_span1))
+
+    def __repr__(self):
+        return (f"eye(sps={self.sps}, t_opt={self.t_opt}, i={self.i}, mu0={self.mu0:.6g}, mu1={self.mu1:.6g}, s0={self.s0:.3g}, "
+                f"s1={self.s1:.3g}, threshold={self.threshold})")
