@@ -36,7 +36,14 @@
  *                                                  ssfm_device_sort_f64), ssfm_eye_levels (masked mean / std, gaussian_kde argmin)
  *   devices.py:1871-1891 (SAMPLER), ook.py:63-133  ssfm_device_sample (x[instant::sps], and `x > rth` as uint8)
  *     (ook.DSP decision)
- *   ook.py:135-220 (BER_analizer 'counter')        ssfm_device_count_diff
+ *   ook.py:135-220 (BER_analizer 'counter'),       ssfm_device_count_diff
+ *     ppm.py:418-474 (the same for PPM)
+ *   ppm.py:27-80 (PPM_ENCODER)                     ssfm_ppm_encode
+ *   ppm.py:83-125 (PPM_DECODER)                    ssfm_ppm_decode (count, scan, scatter: any input)
+ *   ppm.py:198-258 (SDD), :309-416 (ppm.DSP:       ssfm_ppm_decide (x[sps//2 :: sps] per symbol: argmax, or `> rth` with the ON count)
+ *     SAMPLER + `y > rth`)
+ *   ppm.py:128-195 (HDD)                           ssfm_ppm_decide (ON counts), ssfm_ppm_faulty (the faulty symbols in ascending order, for
+ *                                                  the host's NumPy draws), ssfm_ppm_resolve (the draws applied, or Philox draws on the device)
  *   (none: NumPy arrays are the reference's only   ssfm_device_alloc / _free / _copy / _convert / _add
  *     data format)                                 -- device-resident signals between calls
  *
@@ -482,6 +489,31 @@ SSFM_API int ssfm_device_sample(int device, const double* x, const double* noise
                                 double* vals, unsigned char* bits);
 /* *out = number of i < n with a[i] != b[i] (uint8 arrays). */
 SSFM_API int ssfm_device_count_diff(int device, const unsigned char* a, const unsigned char* b, int64_t n, int64_t* out);
+
+/* ---- the PPM receiver (csrc/ppm.hip): DEVICE pointers, uint8 bits / slots (0 or 1), float64 samples.  M is a power of two, 2 ... 2^16
+ * (the encoder takes any M >= 2), k = floor(log2 M); nsym < 2^31.  Every call runs on the default stream of `device` and has finished its
+ * work when it returns. ----
+ * ssfm_ppm_encode: slots[s M + j] = (the k bits[s k ...] of symbol s, MSB first, read j), nsym symbols (nonzero bits count as 1). */
+SSFM_API int ssfm_ppm_encode(int device, const unsigned char* bits, int64_t nsym, int M, unsigned char* slots);
+/* Every nonzero slot at position p of the n slots emits the k bits of p mod M, in order.  bits NULL: *n_bits = the number of output bits (one
+ * blocking read); else the bits (at most `cap`) go to `bits` and n_bits is not used. */
+SSFM_API int ssfm_ppm_decode(int device, const unsigned char* slots, int64_t n, int M, unsigned char* bits, int64_t cap, int64_t* n_bits);
+/* The slot samples v(q) = x[start + q step] (+ noise[...], nullable; `is_u8`: x holds uint8 values, read as v != 0, no noise) of nsym symbols
+ * of M slots.  hard = 0: the symbol's value is np.argmax of its M samples (first index on ties, NaN the maximum).  hard = 1: the slots with
+ * v > thr are ON; counts[s] = their number, and a symbol with exactly one ON slot takes that slot as its value.  A symbol with a value writes
+ * its k bits to bits[s k ...] and / or its one-hot slots to slots[s M ...] (either nullable, not both); the others are left to ssfm_ppm_resolve. */
+SSFM_API int ssfm_ppm_decide(int device, const void* x, const double* noise, int is_u8, int64_t start, int64_t step, int64_t nsym, int M, int hard,
+                             double thr, unsigned char* bits, unsigned char* slots, int* counts);
+/* The symbols s with counts[s] != 1 in ascending order: idx[r] = s, cnt[r] = counts[s] (both with room for nsym); *n_faulty = their number
+ * (one blocking read). */
+SSFM_API int ssfm_ppm_faulty(int device, const int* counts, int64_t nsym, int* idx, int* cnt, int64_t* n_faulty);
+/* HDD's choice for the symbols whose count is not 1 (same x / noise / is_u8 / start / step / thr as ssfm_ppm_decide): an empty symbol turns
+ * slot r ON, a symbol with more than one ON slot keeps its r-th ON slot (0-based, in slot order).  idx not NULL: the n_list symbols idx[f]
+ * with r = draws[f] (the caller's draws); idx NULL: every such symbol, with r = floor(u bound / 2^32), u the first word of
+ * Philox4x32-10(key = seed, counter = (symbol, stream)), bound = M or the count.  Writes bits and / or one-hot slots as ssfm_ppm_decide. */
+SSFM_API int ssfm_ppm_resolve(int device, const void* x, const double* noise, int is_u8, int64_t start, int64_t step, int64_t nsym, int M, double thr,
+                              const int* counts, const int* idx, const int* draws, int64_t n_list, uint64_t seed, uint64_t stream, unsigned char* bits,
+                              unsigned char* slots);
 
 #ifdef __cplusplus
 }

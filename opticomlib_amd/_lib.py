@@ -91,6 +91,11 @@ SYMBOLS = {
     "ssfm_eye_levels": (_I, [_I, _VP, _I64, _I64, _I64, _I64, _D, _I, _VP, _I64]),
     "ssfm_device_sample": (_I, [_I, _VP, _VP, _I64, _I64, _I64, _D, _VP, _VP]),
     "ssfm_device_count_diff": (_I, [_I, _VP, _VP, _I64, C.POINTER(_I64)]),
+    "ssfm_ppm_encode": (_I, [_I, _VP, _I64, _I, _VP]),
+    "ssfm_ppm_decode": (_I, [_I, _VP, _I64, _I, _VP, _I64, C.POINTER(_I64)]),
+    "ssfm_ppm_decide": (_I, [_I, _VP, _VP, _I, _I64, _I64, _I64, _I, _I, _D, _VP, _VP, _VP]),
+    "ssfm_ppm_faulty": (_I, [_I, _VP, _I64, _VP, _VP, C.POINTER(_I64)]),
+    "ssfm_ppm_resolve": (_I, [_I, _VP, _VP, _I, _I64, _I64, _I64, _I, _D, _VP, _VP, _VP, _I64, C.c_uint64, C.c_uint64, _VP, _VP]),
 }
 
 

@@ -281,17 +281,7 @@ extern "C" int ssfm_device_mem_info(int device, size_t* free_bytes, size_t* tota
 // the output come from pair p, so a buffer's content depends only on (seed, stream), not on the launch shape.
 namespace {
 
-__device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, unsigned k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0];
-        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c[2];
-        const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n1 = (unsigned)p1;
-        const unsigned n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1, n3 = (unsigned)p0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-}
+using ssfm::philox4x32_10;
 
 __global__ __launch_bounds__(256) void k_randn(double* __restrict__ out, long long n, unsigned long long seed, unsigned long long stream, double mean, double std) {
     const long long pairs = (n + 1) / 2;

@@ -60,6 +60,20 @@ SSFM_INTERNAL int64_t plan_length(ssfm_plan* plan, int* batch, int* precision);
 // hipMalloc / hipFree pair per call -- hipFree waits for the whole device and stalls the streams of every other plan
 SSFM_INTERNAL int plan_workspace(ssfm_plan* plan, int slot, size_t bytes, void** out);
 
+// Philox4x32-10 (Salmon et al., SC'11): ten rounds on the counter `c` under the key (k0, k1) -- the documented device generator of
+// ssfm_device_randn (device_mem.hip) and of the PPM tie-breaking with rng="device" (ppm.hip).
+__device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, unsigned k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned long long p0 = (unsigned long long)0xD2511F53u * c[0];
+        const unsigned long long p1 = (unsigned long long)0xCD9E8D57u * c[2];
+        const unsigned n0 = (unsigned)(p1 >> 32) ^ c[1] ^ k0, n1 = (unsigned)p1;
+        const unsigned n2 = (unsigned)(p0 >> 32) ^ c[3] ^ k1, n3 = (unsigned)p0;
+        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+}
+
 }  // namespace ssfm
 
 #define HIP_TRY(expr)                                                                               \

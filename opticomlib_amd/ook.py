@@ -2,7 +2,7 @@
 
 ``DSP`` runs on the GPU end to end (optional ``LPF``, ``GET_EYE``, the decision at ``gv.sps // 2``) and returns its bits in GPU
 memory; ``BER_analizer('counter')`` compares two device-resident sequences there.  ``THRESHOLD_EST`` and the estimator are a few
-host scalars, as in the reference.
+host scalars, as in the reference, and so is ``theory_BER``.
 """
 from __future__ import annotations
 
@@ -16,7 +16,7 @@ from . import _lib
 from .devices import GET_EYE, LPF, _adopt, _dev_array, _real_sum_device, _sample_device, default_device
 from .typing import NULL, binary_sequence, electrical_signal
 
-__all__ = ["THRESHOLD_EST", "DSP", "BER_analizer"]
+__all__ = ["THRESHOLD_EST", "DSP", "BER_analizer", "theory_BER"]
 
 
 def _Q(x):
@@ -83,3 +83,14 @@ def BER_analizer(mode: Literal["counter", "estimator"], *, device=None, **kargs)
         return 0.5 * (_Q((e.mu1 - um) / e.s1) + _Q((um - e.mu0) / e.s0))
     else:
         raise TypeError("Invalid mode. Use `counter` or `estimator`.")
+
+
+def theory_BER(mu1, s0, s1):
+    """Theoretical bit error probability of OOK (reference ``ook.py:222-256``): ``0.5 min(Q((mu1 - r)/s1) + Q(r/s0))`` over
+    ``linspace(0, mu1, 1000)``, vectorised over ``mu1``, ``s0`` and ``s1`` as the reference does."""
+    @np.vectorize
+    def fun(mu1_, s0_, s1_):
+        r = np.linspace(0, mu1_, 1000)
+        return 0.5 * np.min(_Q((mu1_ - r) / s1_) + _Q(r / s0_))
+
+    return fun(mu1, s0, s1)
