@@ -44,6 +44,10 @@
  *     SAMPLER + `y > rth`)
  *   ppm.py:128-195 (HDD)                           ssfm_ppm_decide (ON counts), ssfm_ppm_faulty (the faulty symbols in ascending order, for
  *                                                  the host's NumPy draws), ssfm_ppm_resolve (the draws applied, or Philox draws on the device)
+ *   devices.py:1894-2173 (FBG)                     ssfm_fbg_solve (solve_ivp RK45 over every bin), ssfm_fbg_delay (filtfilt correction),
+ *                                                  ssfm_chirp_transfer / the plan's transfer (the filtering)
+ *   devices.py:513-612 (PM)                        ssfm_pm
+ *   devices.py:1558-1632 (ADC)                     ssfm_eye_resample_stage (scipy.signal.resample), ssfm_shortest_int, ssfm_adc_quantize
  *   (none: NumPy arrays are the reference's only   ssfm_device_alloc / _free / _copy / _convert / _add
  *     data format)                                 -- device-resident signals between calls
  *
@@ -514,6 +518,32 @@ SSFM_API int ssfm_ppm_faulty(int device, const int* counts, int64_t nsym, int* i
 SSFM_API int ssfm_ppm_resolve(int device, const void* x, const double* noise, int is_u8, int64_t start, int64_t step, int64_t nsym, int M, double thr,
                               const int* counts, const int* idx, const int* draws, int64_t n_list, uint64_t seed, uint64_t stream, unsigned char* bits,
                               unsigned char* slots);
+
+/* ---- FBG, PM and ADC (csrc/fbg.hip, csrc/transmitter.hip, csrc/eye.hip) ---- */
+/* The apodizations of devices.py:2058-2078; CUSTOM: p(z) comes from the caller's ssfm_fbg_apo_fn. */
+enum ssfm_fbg_apodization { SSFM_FBG_UNIFORM = 0, SSFM_FBG_RCOS = 1, SSFM_FBG_GAUSSIAN = 2, SSFM_FBG_PARABOLIC = 3, SSFM_FBG_CUSTOM = 4 };
+/* p[j] = apodization(z[j]) for j < count; nonzero return aborts the solve. */
+typedef int (*ssfm_fbg_apo_fn)(const double* z, int count, double* p, void* user);
+/* ssfm_fbg_solve: the coupled-mode equations of devices.py:2030-2091, dR/dz = j(sig R + k S), dS/dz = -j(sig S + k R), sig = delta + s p - F z
+ * (k, s times p(z) unless uniform), from z = 1/2 (R = 1, S = 0) to -1/2, with the step control of scipy's solve_ivp(method="RK45", rtol, atol)
+ * over all bins at once.  delta / s / kappa: HOST float64 (n each, n <= 2^22); H: DEVICE complex128 (n), = S / R at z = -1/2.
+ * info (HOST, 3): accepted steps (len(sol.t) - 1), attempted steps, blocking host waits.  SSFM_ERR_STATE when the step size falls below
+ * scipy's min_step.  The built-in apodizations wait for the device once per 32 attempted steps; CUSTOM once per attempted step (p at the
+ * six stage positions t + c h is evaluated on the host and uploaded). */
+SSFM_API int ssfm_fbg_solve(int device, int64_t n, const double* delta, const double* s, const double* kappa, double F, int apodization,
+                            double rtol, double atol, ssfm_fbg_apo_fn apo_fn, void* apo_user, void* H, int64_t* info);
+/* ssfm_fbg_delay: with `apply`, H[i] *= exp(-j w_i tau 1e-12), w = 2 pi fftshift(fftfreq(n, dt)) (the filtfilt correction of devices.py:2160-2163);
+ * then H_natural = ifftshift(H), the transfer table of the filtering.  DEVICE H (fftshift order, n <= 2^22) and H_natural (distinct). */
+SSFM_API int ssfm_fbg_delay(int device, void* H, void* H_natural, int64_t n, double dt, double tau, int apply);
+/* ssfm_pm: out = in exp(j theta), theta = drive pi / Vpi (+ drive_noise pi / Vpi), devices.py:598-609; complex128 fields (n_pol rows of n),
+ * float64 or (drive_complex) complex128 drive of n samples; every row gets the same phase.  DEVICE pointers; out_noise with in_noise. */
+SSFM_API int ssfm_pm(int device, void* out_sig, void* out_noise, const void* in_sig, const void* in_noise, int n_pol, int64_t n, const void* drive,
+                     const void* drive_noise, int drive_complex, double Vpi);
+/* ssfm_shortest_int: utils.shortest_int(x, percent) of a DEVICE float64 array (sorted copy, lag = int(n percent / 100) >= 1); out: HOST (2). */
+SSFM_API int ssfm_shortest_int(int device, const double* x, int64_t n, double percent, double* out);
+/* ssfm_adc_quantize: code = rint((x - vmin) / (vmax - vmin) levels) (NumPy round: half to even); as_volts = 0: int64 codes, 1: float64
+ * code / levels (vmax - vmin) + vmin (devices.py:1618-1627).  DEVICE x and out. */
+SSFM_API int ssfm_adc_quantize(int device, const double* x, int64_t n, double vmin, double vmax, int64_t levels, int as_volts, void* out);
 
 #ifdef __cplusplus
 }

@@ -96,6 +96,11 @@ SYMBOLS = {
     "ssfm_ppm_decide": (_I, [_I, _VP, _VP, _I, _I64, _I64, _I64, _I, _I, _D, _VP, _VP, _VP]),
     "ssfm_ppm_faulty": (_I, [_I, _VP, _I64, _VP, _VP, C.POINTER(_I64)]),
     "ssfm_ppm_resolve": (_I, [_I, _VP, _VP, _I, _I64, _I64, _I64, _I, _D, _VP, _VP, _VP, _I64, C.c_uint64, C.c_uint64, _VP, _VP]),
+    "ssfm_fbg_solve": (_I, [_I, _I64, _VP, _VP, _VP, _D, _I, _D, _D, _VP, _VP, _VP, C.POINTER(_I64)]),
+    "ssfm_fbg_delay": (_I, [_I, _VP, _VP, _I64, _D, _D, _I]),
+    "ssfm_pm": (_I, [_I, _VP, _VP, _VP, _VP, _I, _I64, _VP, _VP, _I, _D]),
+    "ssfm_shortest_int": (_I, [_I, _VP, _I64, _D, _VP]),
+    "ssfm_adc_quantize": (_I, [_I, _VP, _I64, _D, _D, _I64, _I, _VP]),
 }
 
 
@@ -281,14 +286,14 @@ def host_empty(shape, dtype, limit: int = 256 << 20) -> np.ndarray:
 class DeviceArray:
     """A C-contiguous array in the HBM of one GPU: what a signal object holds between device calls.
 
-    ``dtype`` is complex64, complex128, float64 or uint8 (bit sequences).  The buffer goes back to the library's
+    ``dtype`` is complex64, complex128, float64, uint8 (bit sequences) or int64 (ADC codes).  The buffer goes back to the library's
     pool when the object is collected.  ``__cuda_array_interface__`` lets torch / RCCL use the memory where it lies."""
 
     def __init__(self, shape, dtype, device: int = 0):
         self.shape = tuple(int(d) for d in np.atleast_1d(shape)) if not isinstance(shape, tuple) else tuple(int(d) for d in shape)
         self.dtype = np.dtype(dtype)
-        if self.dtype not in (np.dtype(np.complex64), np.dtype(np.complex128), np.dtype(np.float64), np.dtype(np.uint8)):
-            raise TypeError(f"DeviceArray supports complex64, complex128, float64 and uint8, not {self.dtype}")
+        if self.dtype not in (np.dtype(np.complex64), np.dtype(np.complex128), np.dtype(np.float64), np.dtype(np.uint8), np.dtype(np.int64)):
+            raise TypeError(f"DeviceArray supports complex64, complex128, float64, uint8 and int64, not {self.dtype}")
         self.device = int(device)
         self.nbytes = int(np.prod(self.shape)) * self.dtype.itemsize
         self.ptr = 0

@@ -316,13 +316,19 @@ __global__ void k_bounds(const double* __restrict__ sorted, long long n, double*
     st[S_NTOP] = (double)(n - lo);
 }
 
+// lag = int(len * percent / 100) of utils.shortest_int (len / 2 at 50 %)
+__device__ __forceinline__ long long shortest_lag(long long len, double percent) {
+#pragma clang fp contract(off)
+    return (long long)((double)len * percent / 100.0);
+}
+
 // shortest_int (reference utils.py:1497-1537) on the sorted run [a, a + len): pass 1 the minimum of x[i + lag] - x[i], pass 2 the count and
 // the sum of the indices within 1e-10 of it
 template <int PASS>
-__global__ __launch_bounds__(kThreads) void k_shortest(const double* __restrict__ sorted, const double* __restrict__ st, int top, double* __restrict__ part) {
+__global__ __launch_bounds__(kThreads) void k_shortest(const double* __restrict__ sorted, const double* __restrict__ st, int top, double percent, double* __restrict__ part) {
     __shared__ double lds[2][kThreads];
     const long long a = top ? (long long)st[S_TOPSTART] : 0, len = (long long)(top ? st[S_NTOP] : st[S_NBOT]);
-    const long long lag = len / 2, m = len - lag;
+    const long long lag = shortest_lag(len, percent), m = len - lag;
     const double mind = st[S_MIND];
     double v[2] = {PASS == 1 ? INFINITY : 0.0, 0.0};
     if (len >= 2)
@@ -346,7 +352,7 @@ __global__ __launch_bounds__(kThreads) void k_shortest(const double* __restrict_
 }
 
 template <int PASS>
-__global__ __launch_bounds__(kThreads) void k_shortest_fold(const double* __restrict__ sorted, const double* __restrict__ part, int top, double* __restrict__ st) {
+__global__ __launch_bounds__(kThreads) void k_shortest_fold(const double* __restrict__ sorted, const double* __restrict__ part, int top, double percent, double* __restrict__ st) {
     __shared__ double lds[2][kThreads];
     const long long a = top ? (long long)st[S_TOPSTART] : 0, len = (long long)(top ? st[S_NTOP] : st[S_NBOT]);
     if (PASS == 1) {
@@ -366,7 +372,7 @@ __global__ __launch_bounds__(kThreads) void k_shortest_fold(const double* __rest
     if (threadIdx.x) return;
     double lo = NAN, hi = NAN;
     if (len >= 2 && v[0] >= 1.0) {
-        const long long lag = len / 2;
+        const long long lag = shortest_lag(len, percent);
         const long long idx = v[0] > 1.0 ? (long long)(v[1] / v[0]) : (long long)v[1];     // int(np.mean(i)) on ties
         lo = sorted[a + idx];
         hi = sorted[a + idx + lag];
@@ -703,10 +709,10 @@ extern "C" int ssfm_eye_estimate(int device, const double* y, int64_t n, const d
     auto after1 = [&] {                                            // everything from vm to the start of the 2-D two-means
         hipLaunchKernelGGL(k_bounds, dim3(1), dim3(1), 0, 0, (const double*)sorted, N, S);
         for (int top = 0; top < 2; ++top) {
-            hipLaunchKernelGGL(k_shortest<1>, R, B, 0, 0, (const double*)sorted, (const double*)S, top, P);
-            hipLaunchKernelGGL(k_shortest_fold<1>, dim3(1), B, 0, 0, (const double*)sorted, (const double*)P, top, S);
-            hipLaunchKernelGGL(k_shortest<2>, R, B, 0, 0, (const double*)sorted, (const double*)S, top, P);
-            hipLaunchKernelGGL(k_shortest_fold<2>, dim3(1), B, 0, 0, (const double*)sorted, (const double*)P, top, S);
+            hipLaunchKernelGGL(k_shortest<1>, R, B, 0, 0, (const double*)sorted, (const double*)S, top, 50.0, P);
+            hipLaunchKernelGGL(k_shortest_fold<1>, dim3(1), B, 0, 0, (const double*)sorted, (const double*)P, top, 50.0, S);
+            hipLaunchKernelGGL(k_shortest<2>, R, B, 0, 0, (const double*)sorted, (const double*)S, top, 50.0, P);
+            hipLaunchKernelGGL(k_shortest_fold<2>, dim3(1), B, 0, 0, (const double*)sorted, (const double*)P, top, 50.0, S);
         }
         hipLaunchKernelGGL(k_levels, dim3(1), dim3(1), 0, 0, S);
         hipLaunchKernelGGL(k_nearest, R, B, 0, 0, yset, (long long)nset, (const double*)S, (int)S_YC, P);
@@ -810,5 +816,63 @@ extern "C" int ssfm_device_count_diff(int device, const unsigned char* a, const 
     HIP_TRY(hipMemcpy(&h, acc, sizeof(h), hipMemcpyDeviceToHost));
     s.drained = true;
     *out = (int64_t)h;
+    return SSFM_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ ADC (devices.py:1558-1632)
+namespace {
+
+__global__ __launch_bounds__(kThreads) void k_quantize(const double* __restrict__ x, long long n, double vmin, double vmax, long long levels, int as_volts,
+                                                       void* __restrict__ out) {
+#pragma clang fp contract(off)
+    const double span = vmax - vmin, L = (double)levels;
+    for (long long i = (long long)blockIdx.x * kThreads + threadIdx.x; i < n; i += (long long)gridDim.x * kThreads) {
+        const double q = rint((x[i] - vmin) / span * L);                  // np.round: half to even
+        const long long code = (long long)q;                              // .astype(int)
+        if (as_volts) ((double*)out)[i] = (double)code / L * span + vmin;
+        else ((long long*)out)[i] = code;
+    }
+}
+
+}  // namespace
+
+extern "C" int ssfm_shortest_int(int device, const double* x, int64_t n, double percent, double* out) {
+    const long long lag = (long long)((double)n * percent / 100.0);
+    if (!x || !out || n < 2 || n > kMaxN || !(percent > 0 && percent <= 100) || lag < 1 || lag >= n)
+        return fail(SSFM_ERR_INVALID, "ssfm_shortest_int: n=%lld percent=%g (lag %lld: 1 ... n - 1; n <= 2^21)", (long long)n, percent, lag);
+    if (int rc = use(device)) return rc;
+    Scratch s(device);
+    void *sorted, *tmp, *hist, *part, *st;
+    if (int rc = s.get(sizeof(double) * n, &sorted)) return rc;
+    if (int rc = s.get(sizeof(double) * n, &tmp)) return rc;
+    if (int rc = s.get(sizeof(unsigned) * 256 * ((n + kTile - 1) / kTile + 1), &hist)) return rc;
+    if (int rc = s.get(sizeof(double) * kRedBlocks * kPartStride, &part)) return rc;
+    if (int rc = s.get(sizeof(double) * 64, &st)) return rc;
+    double init[64] = {};
+    init[S_NBOT] = (double)n;                                      // the whole sorted copy is the run [0, n)
+    HIP_TRY(hipMemcpy(st, init, sizeof(init), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpyAsync(sorted, x, sizeof(double) * n, hipMemcpyDeviceToDevice, 0));
+    if (int rc = radix_sort((double*)sorted, (double*)tmp, (unsigned*)hist, n)) return rc;
+    double* S = (double*)st;
+    double* P = (double*)part;
+    const dim3 R(kRedBlocks), B(kThreads);
+    hipLaunchKernelGGL(k_shortest<1>, R, B, 0, 0, (const double*)sorted, (const double*)S, 0, percent, P);
+    hipLaunchKernelGGL(k_shortest_fold<1>, dim3(1), B, 0, 0, (const double*)sorted, (const double*)P, 0, percent, S);
+    hipLaunchKernelGGL(k_shortest<2>, R, B, 0, 0, (const double*)sorted, (const double*)S, 0, percent, P);
+    hipLaunchKernelGGL(k_shortest_fold<2>, dim3(1), B, 0, 0, (const double*)sorted, (const double*)P, 0, percent, S);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpy(init, S, sizeof(init), hipMemcpyDeviceToHost));
+    s.drained = true;
+    out[0] = init[S_BOT0];
+    out[1] = init[S_BOT1];
+    return SSFM_OK;
+}
+
+extern "C" int ssfm_adc_quantize(int device, const double* x, int64_t n, double vmin, double vmax, int64_t levels, int as_volts, void* out) {
+    if (!x || !out || n < 1 || levels < 1) return fail(SSFM_ERR_INVALID, "ssfm_adc_quantize: n=%lld levels=%lld", (long long)n, (long long)levels);
+    if (int rc = use(device)) return rc;
+    hipLaunchKernelGGL(k_quantize, dim3(grid_for(n)), dim3(kThreads), 0, 0, x, (long long)n, vmin, vmax, (long long)levels, as_volts, out);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
     return SSFM_OK;
 }

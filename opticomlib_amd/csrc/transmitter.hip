@@ -231,3 +231,51 @@ extern "C" int ssfm_device_shift(int device, void* dst, const void* src, int64_t
     return SSFM_OK;
 }
 
+
+// ------------------------------------------------------------------------------------------------ PM (devices.py:598-609)
+// out = in exp(j theta); theta = v pi / Vpi + vn pi / Vpi (the reference adds the drive's signal and noise after scaling each); a complex drive
+// gives exp(-Im theta) cis(Re theta)
+namespace {
+
+__global__ __launch_bounds__(256) void k_pm(double2* __restrict__ out_s, double2* __restrict__ out_n, const double2* __restrict__ in_s, const double2* __restrict__ in_n,
+                                            int n_pol, long long n, const double* __restrict__ v, const double* __restrict__ vn, int drive_complex, double Vpi) {
+#pragma clang fp contract(off)
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x) {
+        double tr, ti = 0.0;
+        if (drive_complex) {
+            tr = v[2 * i] * M_PI / Vpi;
+            ti = v[2 * i + 1] * M_PI / Vpi;
+            if (vn) { tr = tr + vn[2 * i] * M_PI / Vpi; ti = ti + vn[2 * i + 1] * M_PI / Vpi; }
+        } else {
+            tr = v[i] * M_PI / Vpi;
+            if (vn) tr = tr + vn[i] * M_PI / Vpi;
+        }
+        double s, c;
+        sincos(tr, &s, &c);
+        const double m = drive_complex ? exp(-ti) : 1.0;
+        const double hr = m * c, hi = m * s;
+        for (int p = 0; p < n_pol; ++p) {
+            const long long o = (long long)p * n + i;
+            const double2 a = in_s[o];
+            out_s[o] = make_double2(a.x * hr - a.y * hi, a.x * hi + a.y * hr);
+            if (in_n) {
+                const double2 b = in_n[o];
+                out_n[o] = make_double2(b.x * hr - b.y * hi, b.x * hi + b.y * hr);
+            }
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int ssfm_pm(int device, void* out_sig, void* out_noise, const void* in_sig, const void* in_noise, int n_pol, int64_t n, const void* drive,
+                       const void* drive_noise, int drive_complex, double Vpi) {
+    if (!out_sig || !in_sig || !drive || n < 1 || n_pol < 1 || n_pol > 2) return fail(SSFM_ERR_INVALID, "ssfm_pm: bad argument");
+    if ((in_noise == nullptr) != (out_noise == nullptr)) return fail(SSFM_ERR_INVALID, "ssfm_pm: in_noise and out_noise must be given together");
+    if (int rc = use_dev(device)) return rc;
+    hipLaunchKernelGGL(k_pm, dim3(blocks_of(n)), dim3(256), 0, 0, (double2*)out_sig, (double2*)out_noise, (const double2*)in_sig, (const double2*)in_noise, n_pol,
+                       (long long)n, (const double*)drive, (const double*)drive_noise, drive_complex, Vpi);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipDeviceSynchronize());
+    return SSFM_OK;
+}
