@@ -311,8 +311,10 @@ __global__ __launch_bounds__(256) void k_sum3(double* __restrict__ out, const do
     }
 }
 
-// dst = a * factor (+ b) over `n` doubles (complex arrays are passed as 2n doubles); b nullable
+// dst = a * factor (+ b) over `n` doubles (complex arrays are passed as 2n doubles); b nullable.  Not contracted: a product, then a sum,
+// bit for bit NumPy's `a * factor + b`
 __global__ __launch_bounds__(256) void k_scale_add(double* __restrict__ dst, const double* __restrict__ a, double factor, const double* __restrict__ b, long long n) {
+#pragma clang fp contract(off)
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (long long)gridDim.x * blockDim.x)
         dst[i] = b ? a[i] * factor + b[i] : a[i] * factor;
 }

@@ -54,6 +54,7 @@ static_assert(S_COUNT <= 64, "state block");
 
 __device__ __forceinline__ unsigned long long order_key(double v) {
     unsigned long long u = (unsigned long long)__double_as_longlong(v);
+    if ((u & 0x7fffffffffffffffull) > 0x7ff0000000000000ull) return ~0ull;   // every NaN, of either sign, after +inf (np.sort), in input order
     if (u == 0x8000000000000000ull) u = 0;                         // -0 orders as +0 (NumPy compares them equal): the sort stays stable over both
     return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
 }

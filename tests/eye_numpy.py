@@ -29,9 +29,9 @@ def find_nearest(levels: np.ndarray, v: float) -> float:
     return float(levels[np.argmin(np.abs(levels - v))])
 
 
-def shortest_int(x: np.ndarray) -> np.ndarray:
+def shortest_int(x: np.ndarray, percent: float = 50) -> np.ndarray:
     x = np.sort(x)
-    lag = int(len(x) * 50 / 100)
+    lag = int(len(x) * percent / 100)
     if lag < 1:
         raise ValueError(f"Computed lag ({lag}) must be at least 1.")
     diff = x[lag:] - x[:-lag]

@@ -21,6 +21,53 @@ def decode(slots, M):
     return ((p[:, None] >> np.arange(k)[::-1]) & 1).astype(np.uint8).ravel()
 
 
+def bits_of(v, k):
+    """The k bits (MSB first) of every symbol value in v, flattened."""
+    return ((np.asarray(v, np.int64)[:, None] >> np.arange(k)[::-1]) & 1).astype(np.uint8).ravel()
+
+
+def one_hot(v, M):
+    out = np.zeros((len(v), M), np.uint8)
+    out[np.arange(len(v)), v] = 1
+    return out.ravel()
+
+
+def faulty(counts):
+    """ssfm_ppm_faulty: the symbols whose ON count is not 1, ascending, and their counts."""
+    idx = np.nonzero(np.asarray(counts) != 1)[0]
+    return idx, np.asarray(counts)[idx]
+
+
+def resolve(on, idx, draws):
+    """HDD's choice for the symbols idx with draws r: an empty symbol takes slot r, a multi-ON symbol its r-th ON slot."""
+    on = np.asarray(on, dtype=bool)[idx]
+    r = np.asarray(draws, np.int64)
+    rank = np.cumsum(on, axis=1) - 1                   # rank of every ON slot within its symbol
+    pick = np.argmax(on & (rank == r[:, None]), axis=1)
+    return np.where(on.any(axis=1), pick, r)
+
+
+def philox4x32_10(c0, c1, c2, c3, k0, k1):
+    """Philox4x32-10 (Salmon et al., SC'11), vectorised over uint64 arrays of 32-bit counter words; returns the four output words."""
+    M32 = np.uint64(0xFFFFFFFF)
+    c = [np.asarray(w, np.uint64) & M32 for w in (c0, c1, c2, c3)]
+    k0, k1 = np.uint64(k0 & 0xFFFFFFFF), np.uint64(k1 & 0xFFFFFFFF)
+    for _ in range(10):
+        p0 = np.uint64(0xD2511F53) * c[0]
+        p1 = np.uint64(0xCD9E8D57) * c[2]
+        c = [((p1 >> np.uint64(32)) ^ c[1] ^ k0) & M32, p1 & M32, ((p0 >> np.uint64(32)) ^ c[3] ^ k1) & M32, p0 & M32]
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & M32, (k1 + np.uint64(0xBB67AE85)) & M32
+    return c
+
+
+def device_draws(idx, bounds, seed, stream):
+    """ssfm_ppm_resolve's device draws: r = floor(u bound / 2^32), u the first word of Philox4x32-10(key = seed, counter = (symbol, stream))."""
+    s = np.asarray(idx, np.uint64)
+    u = philox4x32_10(s, s >> np.uint64(32), np.full(s.shape, stream & 0xFFFFFFFF, np.uint64), np.full(s.shape, stream >> 32, np.uint64),
+                      seed & 0xFFFFFFFF, seed >> 32)[0]
+    return ((u * np.asarray(bounds, np.uint64)) >> np.uint64(32)).astype(np.int64)
+
+
 def hdd(slots, M):
     """HDD on a 0 / 1 slot sequence: the one-hot symbols (a new array; the input is not written)."""
     s = (np.asarray(slots) != 0).reshape(-1, M).astype(np.uint8)

@@ -165,3 +165,10 @@ def test_the_new_entry_points_are_declared_bound_and_exported():
         assert f"SSFM_API int {s}(" in hdr and s in _lib.SYMBOLS and s in names, s
     assert "#define SSFM_ABI_VERSION 3" in hdr
     assert "ppm.hip" in open(os.path.join(ROOT, "opticomlib_amd", "csrc", "Makefile")).read()
+
+
+def test_philox_restatement_known_answers():
+    # Random123's published known-answer vectors for philox4x32_10 (the generator of ppm.HDD's rng="device")
+    assert [int(w) for w in pn.philox4x32_10(0, 0, 0, 0, 0, 0)] == [0x6627E8D5, 0xE169C58D, 0xBC57AC4C, 0x9B00DBD8]
+    f = 0xFFFFFFFF
+    assert [int(w) for w in pn.philox4x32_10(f, f, f, f, f, f)] == [0x408F276D, 0x41C83B0E, 0xA20BC7C6, 0x6D5451FD]
