@@ -48,6 +48,7 @@ enum Slot {
     S_YC, S_YL, S_YR,                              // nearest values in the pre-resample set
     S_NBAND, S_TMEAN, S_MIND,
     S_MU0, S_MU1, S_SD0, S_SD1, S_N0, S_N1, S_NC, S_CMEAN, S_CVAR, S_INVH, S_KDE, S_SINGULAR,
+    S_NONFINITE,                                   // the signal holds a NaN or an infinity (sklearn's KMeans.fit rejects it)
     S_COUNT
 };
 static_assert(S_COUNT <= 64, "state block");
@@ -296,10 +297,13 @@ __global__ __launch_bounds__(kThreads) void k_lloyd_fold(const double* __restric
 }
 
 // ------------------------------------------------------------------------------------------------ levels from the sorted copy
+// a -inf sorts first, a +inf or any NaN last: the two ends of the sorted copy tell whether every sample is finite
 __global__ void k_init_1d(const double* __restrict__ sorted, long long n, double* __restrict__ st) {
     for (int k = 0; k < S_COUNT; ++k) st[k] = 0.0;
-    st[S_C0] = sorted[0];                                          // (min, max): the documented initialisation of the 1-D two-means
-    st[S_C1] = sorted[n - 1];
+    const double lo = sorted[0], hi = sorted[n - 1];
+    st[S_C0] = lo;                                                 // (min, max): the documented initialisation of the 1-D two-means
+    st[S_C1] = hi;
+    st[S_NONFINITE] = isfinite(lo) && isfinite(hi) ? 0.0 : 1.0;
 }
 
 // vm and the extents of {x < vm} (a prefix of the sorted copy) and {x > vm} (a suffix): two binary searches
@@ -489,7 +493,8 @@ __global__ __launch_bounds__(kThreads) void k_moments_fold(const double* __restr
         st[S_SD0] = sqrt(v[1] / st[S_N0]);
         const double nc = st[S_NC], var = v[2] / (nc - 1.0);
         st[S_CVAR] = var;
-        const bool ok = nc >= 2.0 && var > 0.0 && isfinite(var);
+        // (a NaN end of the grid, an empty top or bottom cluster, is no threshold either: scipy's evaluate raises on it)
+        const bool ok = nc >= 2.0 && var > 0.0 && isfinite(var) && isfinite(st[S_MU0]) && isfinite(st[S_MU1]);
         st[S_SINGULAR] = ok ? 0.0 : 1.0;
         st[S_INVH] = ok ? 1.0 / (sqrt(var) * pow(nc, -0.2)) : 0.0;
     }
@@ -740,6 +745,11 @@ extern "C" int ssfm_eye_estimate(int device, const double* y, int64_t n, const d
     lloyd2();
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipMemcpy(out, S, sizeof(double) * S_COUNT, hipMemcpyDeviceToHost));
+    if (out[S_NONFINITE] != 0.0) {                                // no further looks: the caller raises (the state is not an estimate)
+        s.drained = true;
+        if (round_trips) *round_trips = trips;
+        return SSFM_OK;
+    }
     while (out[S_DONE1] == 0.0) {
         lloyd1();
         after1();

@@ -1449,7 +1449,7 @@ def MZM(op_input: optical_signal, el_input, bias: float = 0.0, Vpi: float = 5.0,
 # ------------------------------------------------------------------ the OOK receiver: GET_EYE and SAMPLER (csrc/eye.hip)
 # the state block of ssfm_eye_estimate / ssfm_eye_levels, in the order of eye.hip `enum Slot`
 _EYE_SLOTS = ("C0 C1 T0 Y0 T1 Y1 IT1 DONE1 IT2 DONE2 VM NBOT NTOP TOPSTART BOT0 BOT1 TOP0 TOP1 V25 V75 STATE0 STATE1 YCT YC YL YR NBAND TMEAN MIND "
-              "MU0 MU1 SD0 SD1 N0 N1 NC CMEAN CVAR INVH KDE SINGULAR").split()
+              "MU0 MU1 SD0 SD1 N0 N1 NC CMEAN CVAR INVH KDE SINGULAR NONFINITE").split()
 _S = {name: k for k, name in enumerate(_EYE_SLOTS)}
 _EYE_MAX_N = 1 << 21
 
@@ -1501,7 +1501,10 @@ def GET_EYE(input, nslots: int = 4096, sps_resamp: int = None, *, device=None, _
     preparation (1); without ``sps_resamp`` nothing more before the estimate, with it the three resampling stages and the two transforms (5); the estimate
     (the t-grid upload and one state read: 2, and one more read per 24 Lloyd steps beyond the first 24 of a two-means); the
     moments and threshold (one state read: 1).  So 4 without resampling and 9 with it, for an eye whose two-means converge in
-    24 steps."""
+    24 steps.
+
+    A signal that holds NaN or infinity (after the resampling) raises ``ValueError``, as the reference's ``KMeans.fit`` does: the ends of
+    the sorted copy flag it on the device, and the estimate stops at its first state read."""
     t0 = time.time()
     input, grid, _ = _adopt(input, "electrical_signal")
     grid = grid if _grid is None else _grid                 # (DSP: the grid of the caller's library)
@@ -1530,6 +1533,8 @@ def GET_EYE(input, nslots: int = 4096, sps_resamp: int = None, *, device=None, _
     _lib._check(lib.ssfm_eye_estimate(dev, _lib._VP(y.ptr), n, _lib._ptr(tg), 2 * s, _lib._VP(x0.ptr), n0, _lib._ptr(st), st.size, C.byref(trips)),
                 "ssfm_eye_estimate")
     S = lambda name: float(st[_S[name]])
+    if S("NONFINITE"):
+        raise ValueError("GET_EYE: the signal holds NaN or infinity (the two-means take finite samples only)")
     for part, count in (("upper", S("NTOP")), ("lower", S("NBOT"))):
         if count < 2:
             raise ValueError(f"Computed lag ({int(count) // 2}) must be at least 1: the {part} half of the eye holds {int(count)} samples.")
@@ -1853,6 +1858,9 @@ def FBG(input: optical_signal, neff: float = 1.45, v: float = 1.0, landa_D: floa
     input, grid, back = _adopt(input, "optical_signal")
     if not isinstance(input, optical_signal):
         raise TypeError("`input` must be of type 'optical_signal'.")
+    _, hi = _lib.supported_log2n(_lib.C128, direct=True)
+    if 2 * input.size - 1 > (1 << hi):                     # the filtering's chirp-z plan (M >= 2n - 1): checked before the solve
+        raise ValueError(f"FBG on the device filters up to 2^{hi - 1} samples, got {input.size} (there is no CPU fallback)")
     c, pi = _C_LIGHT, np.pi
     landa_D, L, dneff, vdneff = _fbg_design(neff, v, landa_D, fc, kL, L, N, dneff, vdneff)
 

@@ -6,6 +6,9 @@ The two-means, as on the device:
   * 2-D: the points of the 25-75 % band split at their mean t (t >= mean: cluster 1), then Lloyd on (t - ct)^2 + (y - cy)^2;
   * an iteration recomputes the centres from the assignment (an empty cluster keeps its centre) and stops when they no longer change,
     or after 300 updates (sklearn's max_iter).
+With ``updates=True`` each two-means also returns how many times its centres changed; ``get_eye`` reports both counts as ``_updates1`` /
+``_updates2`` (what the device's host loop of 24-step chunks depends on).  A signal that holds NaN or infinity raises ValueError, as
+sklearn's input validation does in the reference's ``KMeans.fit``.
 """
 from __future__ import annotations
 
@@ -40,8 +43,9 @@ def shortest_int(x: np.ndarray, percent: float = 50) -> np.ndarray:
     return np.array((x[i], x[i + lag]))
 
 
-def two_means_1d(x: np.ndarray):
+def two_means_1d(x: np.ndarray, updates: bool = False):
     c = np.array([x.min(), x.max()])
+    u = 0
     for _ in range(LLOYD_MAX):
         one = np.abs(x - c[1]) < np.abs(x - c[0])
         new = c.copy()
@@ -52,10 +56,11 @@ def two_means_1d(x: np.ndarray):
         if np.array_equal(new, c):
             break
         c = new
-    return c
+        u += 1
+    return (c, u) if updates else c
 
 
-def two_means_2d(t: np.ndarray, y: np.ndarray):
+def two_means_2d(t: np.ndarray, y: np.ndarray, updates: bool = False):
     """Centres (2, 2) as rows (t, y)."""
     def means(one, c):
         new = c.copy()
@@ -70,13 +75,15 @@ def two_means_2d(t: np.ndarray, y: np.ndarray):
         c[0] = c[1]
     if not one.any():
         c[1] = c[0]
+    u = 0
     for _ in range(LLOYD_MAX):
         one = (t - c[1, 0]) ** 2 + (y - c[1, 1]) ** 2 < (t - c[0, 0]) ** 2 + (y - c[0, 1]) ** 2
         new = means(one, c)
         if np.array_equal(new, c):
             break
         c = new
-    return c
+        u += 1
+    return (c, u) if updates else c
 
 
 def kde_argmin(y: np.ndarray, mu0: float, mu1: float, npts: int = 500):
@@ -105,7 +112,10 @@ def get_eye(x: np.ndarray, sps: int, nslots: int = 4096, sps_resamp=None) -> dic
     tg = t_grid(s)
     t = np.kron(np.ones(nslots // 2), tg)
     d["y"], d["t"] = x, t
-    c = two_means_1d(x)
+    if not np.isfinite(x).all():
+        raise ValueError("Input X contains NaN or infinity.")
+    c, d["_updates1"] = two_means_1d(x, updates=True)
+    d["_updates2"] = 0
     vm = np.mean(c)
     d["top_int"] = top = shortest_int(x[x > vm])
     d["bot_int"] = bot = shortest_int(x[x < vm])
@@ -114,7 +124,7 @@ def get_eye(x: np.ndarray, sps: int, nslots: int = 4096, sps_resamp=None) -> dic
     v75, v25 = s1 - 0.25 * d01, s0 + 0.25 * d01
     band = (x > v25) & (x < v75)
     if band.sum() >= 2:
-        cc = two_means_2d(t[band], x[band])
+        cc, d["_updates2"] = two_means_2d(t[band], x[band], updates=True)
         left, right = np.argmin(cc[:, 0]), np.argmax(cc[:, 0])
         d["t_left"] = t_left = find_nearest(tg, cc[left, 0])
         d["t_right"] = t_right = find_nearest(tg, cc[right, 0])

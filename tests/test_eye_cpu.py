@@ -135,3 +135,31 @@ def test_restatement_building_blocks():
     assert en.find_nearest(np.array([0.0, 1.0, 2.0]), 0.5) == 0.0                       # ties to the lower value
     c = en.two_means_1d(np.r_[np.zeros(10), np.ones(10)])
     np.testing.assert_array_equal(c, [0.0, 1.0])
+
+
+def test_restatement_counts_its_lloyd_updates():
+    # (0, 10) -> (1, 10): one update, then the step that finds the centres unchanged
+    c, u = en.two_means_1d(np.array([0.0, 1.0, 2.0, 10.0]), updates=True)
+    np.testing.assert_array_equal(c, [1.0, 10.0])
+    assert u == 1
+    c, u = en.two_means_1d(np.r_[np.zeros(10), np.ones(10)], updates=True)
+    assert u == 0
+    x = np.random.default_rng(0).exponential(1.0, 1 << 20)                 # far outliers: many small moves of the upper centre
+    c, u = en.two_means_1d(x, updates=True)
+    np.testing.assert_array_equal(c, en.two_means_1d(x))
+    assert u > 24
+    t = np.tile(np.linspace(-1, 1, 8, endpoint=False), 4)
+    cc, u2 = en.two_means_2d(t, np.arange(t.size, dtype=float), updates=True)
+    np.testing.assert_array_equal(cc, en.two_means_2d(t, np.arange(t.size, dtype=float)))
+    assert u2 >= 1
+
+
+@pytest.mark.parametrize("bad", [np.nan, np.inf, -np.inf])
+@pytest.mark.parametrize("resamp", [None, 32])
+def test_restatement_refuses_non_finite_samples(bad, resamp):
+    x = np.tile(np.r_[np.zeros(16), np.ones(16)], 32)
+    x[7] = bad
+    with pytest.raises(ValueError, match="NaN or infinity"):
+        en.get_eye(x, 16, 64, resamp)
+    x[7] = 0.0
+    assert en.get_eye(x, 16, 64, resamp)["_updates1"] >= 0                 # a finite signal goes through
