@@ -48,6 +48,9 @@
  *                                                  ssfm_chirp_transfer / the plan's transfer (the filtering)
  *   devices.py:513-612 (PM)                        ssfm_pm
  *   devices.py:1558-1632 (ADC)                     ssfm_eye_resample_stage (scipy.signal.resample), ssfm_shortest_int, ssfm_adc_quantize
+ *   utils.py:2048-2079 (get_psd; also the          ssfm_welch (nperseg a power of two of 16 ... 8192, or < 16), and for every other nperseg
+ *     signals' .psd(), typing.py:1850-1970:        ssfm_welch_frames / ssfm_welch_accumulate around ssfm_chirp_fourier, then ssfm_welch_finish
+ *     scipy.signal.welch)
  *   (none: NumPy arrays are the reference's only   ssfm_device_alloc / _free / _copy / _convert / _add
  *     data format)                                 -- device-resident signals between calls
  *
@@ -544,6 +547,23 @@ SSFM_API int ssfm_shortest_int(int device, const double* x, int64_t n, double pe
 /* ssfm_adc_quantize: code = rint((x - vmin) / (vmax - vmin) levels) (NumPy round: half to even); as_volts = 0: int64 codes, 1: float64
  * code / levels (vmax - vmin) + vmin (devices.py:1618-1627).  DEVICE x and out. */
 SSFM_API int ssfm_adc_quantize(int device, const double* x, int64_t n, double vmin, double vmax, int64_t levels, int as_volts, void* out);
+
+/* Welch's PSD as get_psd computes it (scipy.signal.welch, periodic Hann window, noverlap = nperseg / 2, nfft = nperseg, no detrend, two-sided,
+ * mean over the nseg = (n - noverlap) / (nperseg - noverlap) segments).  Input: `rows` rows of `n` elements, `ld` elements apart, DEVICE memory,
+ * read in place; dtype SSFM_C64, SSFM_C128 or SSFM_F64_REAL.  All arithmetic is float64.  `out` (HOST) receives rows x nperseg values, fftshifted,
+ * float32 with `out_f32`, else float64.  No float atomics: two calls on the same input give the same bits.  Default stream; each call has finished
+ * its work when it returns.
+ *   ssfm_welch             the whole estimate for nperseg = 2^m, 16 <= nperseg <= 8192, or nperseg < 16 (SSFM_ERR_INVALID otherwise):
+ *                          two launches and one host wait; out = factor / nseg * sum |X|^2 (factor = 1 / sum(window)^2); rows <= 65535
+ *   ssfm_welch_frames      any nperseg: frames (DEVICE, chunk x nperseg complex128) <- the windowed segments first ... first + count - 1
+ *                          (segment g is segment g % nseg of row g / nseg), zero from `count` up to `chunk`
+ *   ssfm_welch_accumulate  acc (DEVICE, rows x nperseg float64) += |frames|^2 of the chunk's segments, per row in segment order
+ *   ssfm_welch_finish      out = factor * acc, fftshifted (factor = 1 / (nseg sum(window)^2)) */
+SSFM_API int ssfm_welch(int device, const void* x, int dtype, int64_t rows, int64_t n, int64_t ld, int64_t nperseg, double factor, int out_f32, void* out);
+SSFM_API int ssfm_welch_frames(int device, const void* x, int dtype, int64_t rows, int64_t n, int64_t ld, int64_t nperseg, int64_t first, int64_t count,
+                               int64_t chunk, void* frames);
+SSFM_API int ssfm_welch_accumulate(int device, const void* frames, int64_t nperseg, int64_t rows, int64_t nseg, int64_t first, int64_t count, void* acc);
+SSFM_API int ssfm_welch_finish(int device, const void* acc, int64_t rows, int64_t nperseg, double factor, int out_f32, void* out);
 
 #ifdef __cplusplus
 }

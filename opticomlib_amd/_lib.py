@@ -101,6 +101,10 @@ SYMBOLS = {
     "ssfm_pm": (_I, [_I, _VP, _VP, _VP, _VP, _I, _I64, _VP, _VP, _I, _D]),
     "ssfm_shortest_int": (_I, [_I, _VP, _I64, _D, _VP]),
     "ssfm_adc_quantize": (_I, [_I, _VP, _I64, _D, _D, _I64, _I, _VP]),
+    "ssfm_welch": (_I, [_I, _VP, _I, _I64, _I64, _I64, _I64, _D, _I, _VP]),
+    "ssfm_welch_frames": (_I, [_I, _VP, _I, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _VP]),
+    "ssfm_welch_accumulate": (_I, [_I, _VP, _I64, _I64, _I64, _I64, _I64, _VP]),
+    "ssfm_welch_finish": (_I, [_I, _VP, _I64, _I64, _D, _I, _VP]),
 }
 
 

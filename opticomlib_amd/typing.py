@@ -8,7 +8,8 @@
                        ``.w()``, ``.to_numpy()`` with the reference's shape -> ``n_pol`` rules
                        (``typing.py:2124-2196``).
 
-Operators, plotting, PSD, eye diagrams etc. are out of scope.
+``electrical_signal.psd()`` / ``optical_signal.psd()`` plot the Welch spectrum of :func:`opticomlib_amd.get_psd` (computed on the
+GPU; matplotlib is imported when the method is called).  Operators, the other plots, eye diagrams etc. are out of scope.
 """
 from __future__ import annotations
 
@@ -268,6 +269,13 @@ class electrical_signal:
     def to_numpy(self) -> np.ndarray:
         return np.asarray(self.signal + self.noise)
 
+    def psd(self, fmt='-', mode='x', n=None, xlabel=None, ylabel=None, yscale='dbm', grid=False, hold=True, show=False, **kwargs):
+        """Plot the power spectral density (reference ``typing.py:1850-1970``): Welch's estimate of the first ``n`` samples
+        (default ``min(size, gv.t.size)``) with ``nperseg = min(2048, n)`` at ``fs = gv.fs * 1e-9`` [GHz], computed on the GPU.
+        ``yscale``: ``'dbm'`` or ``'linear'`` (mW); ``mode``: ``'x'``, ``'y'`` or ``'both'`` polarisations.  Returns ``self``."""
+        from .utils import plot_psd
+        return plot_psd(self, fmt, mode, n, xlabel, ylabel, yscale, grid, hold, show, **kwargs)
+
     def __repr__(self):
         return f"electrical_signal(size={self.size}, dtype={self._raw('signal').dtype}, noise={'NULL' if self._raw('noise') is NULL else 'array'})"
 
@@ -391,6 +399,13 @@ class optical_signal:
     def to_numpy(self) -> np.ndarray:
         """``signal + noise`` (reference ``typing.py:1593-1597``)."""
         return np.asarray(self.signal + self.noise)
+
+    def psd(self, fmt='-', mode='x', n=None, xlabel=None, ylabel=None, yscale='dbm', grid=False, hold=True, show=False, **kwargs):
+        """Plot the power spectral density (reference ``typing.py:1850-1970``): Welch's estimate of the first ``n`` samples
+        (default ``min(size, gv.t.size)``) with ``nperseg = min(2048, n)`` at ``fs = gv.fs * 1e-9`` [GHz], computed on the GPU.
+        ``yscale``: ``'dbm'`` or ``'linear'`` (mW); ``mode``: ``'x'``, ``'y'`` or ``'both'`` polarisations.  Returns ``self``."""
+        from .utils import plot_psd
+        return plot_psd(self, fmt, mode, n, xlabel, ylabel, yscale, grid, hold, show, **kwargs)
 
     def w(self, shift: bool = False) -> np.ndarray:
         """Angular frequency grid [rad/s], FFT order (reference ``typing.py:1628-1644``)."""
