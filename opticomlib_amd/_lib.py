@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("SSFM_LIB") or os.path.join(_HERE, "_ssfm_amd.so")   # SSFM_LIB: dev override
 
 C64, C128 = 0, 1
+COPY_H2D, COPY_D2H, COPY_D2D, COPY_ZERO = 0, 1, 2, 3        # ssfm_device_copy: host -> device, device -> host, device -> device, zero the bytes
 F64_REAL = 2                           # ssfm_device_convert only: real float64 values
 HOST_PINNED = -1                       # ssfm_device_alloc / _free: a page-locked host buffer
 REDUCE_MEAN, REDUCE_MEAN2, REDUCE_POWER, REDUCE_MIN = 0, 1, 2, 3      # ssfm_device_reduce
@@ -166,6 +167,22 @@ def _check(rc, what):
         raise SsfmError(f"{what} failed (status {rc}): {msg}")
 
 
+class _Api:
+    """``api.ssfm_X(...)``: the C entry point ``ssfm_X`` with its status checked -- :class:`SsfmError` (``_check``) unless it returns 0."""
+
+    def __getattr__(self, name):
+        fn = getattr(load(), name)
+
+        def call(*args):
+            _check(fn(*args), name)
+        call.__name__ = name
+        setattr(self, name, call)          # (kept: the next call finds it without __getattr__)
+        return call
+
+
+api = _Api()
+
+
 def _check_filter(rc, what):
     """An input shorter than the padding is the caller's ValueError in SciPy (``sosfiltfilt`` / ``_validate_pad``), and so
     it is here; everything else is a library failure."""
@@ -185,7 +202,7 @@ def device_count() -> int:
 def supported_log2n(precision=C64, direct=False):
     """(lo, hi) of log2(samples per row) a plan takes; ``direct``: of the plans whose field buffer is one line (what the chirp-z path and the transfer tables need)."""
     lo, hi = _I(0), _I(0)
-    _check(load().ssfm_supported_log2n(precision, C.byref(lo), C.byref(hi)), "ssfm_supported_log2n")
+    api.ssfm_supported_log2n(precision, C.byref(lo), C.byref(hi))
     return lo.value, (min(hi.value, DIRECT_LOG2_MAX) if direct else hi.value)
 
 
@@ -213,7 +230,7 @@ def sosfiltfilt_device(sos: np.ndarray, zi: np.ndarray, x_ptr: int, y_ptr: int, 
     """The same on DEVICE buffers (raw pointers; float64 or interleaved complex128, ``batch`` rows of ``n``)."""
     sos = np.ascontiguousarray(sos, dtype=np.float64)
     zi = np.ascontiguousarray(zi, dtype=np.float64)
-    _check_filter(load().ssfm_sosfiltfilt(int(device), _ptr(sos), _ptr(zi), sos.shape[0], _VP(x_ptr), _VP(y_ptr), int(n), int(batch),
+    _check_filter(load().ssfm_sosfiltfilt(int(device), _ptr(sos), _ptr(zi), sos.shape[0], x_ptr, y_ptr, int(n), int(batch),
                                           int(bool(is_complex)), 1), "ssfm_sosfiltfilt")
 
 
@@ -225,27 +242,27 @@ def square_law(signal: np.ndarray, noise, r: float, device: int = 0):
     n_pol = 1 if s.ndim == 1 else s.shape[0]
     i_sig = np.empty(n, dtype=np.float64)
     if noise is None:
-        _check(load().ssfm_square_law(int(device), _ptr(s), None, n_pol, n, float(r), 1.0, _ptr(i_sig), None, 0), "ssfm_square_law")
+        api.ssfm_square_law(int(device), _ptr(s), None, n_pol, n, float(r), 1.0, _ptr(i_sig), None, 0)
         return i_sig, None
     nz = np.ascontiguousarray(noise, dtype=np.complex128)
     if nz.shape != s.shape:
         raise ValueError(f"signal and noise shapes differ: {s.shape} vs {nz.shape}")
     i_noise = np.empty(n, dtype=np.float64)
-    _check(load().ssfm_square_law(int(device), _ptr(s), _ptr(nz), n_pol, n, float(r), 1.0, _ptr(i_sig), _ptr(i_noise), 0), "ssfm_square_law")
+    api.ssfm_square_law(int(device), _ptr(s), _ptr(nz), n_pol, n, float(r), 1.0, _ptr(i_sig), _ptr(i_noise), 0)
     return i_sig, i_noise
 
 
 def sosfiltfilt_last_ms(device: int = 0) -> float:
     """Device time [ms] of the kernels of the last filter call on ``device``."""
     ms = C.c_float()
-    _check(load().ssfm_sosfiltfilt_last(int(device), C.byref(ms), None), "ssfm_sosfiltfilt_last")
+    api.ssfm_sosfiltfilt_last(int(device), C.byref(ms), None)
     return float(ms.value)
 
 
 def sosfiltfilt_last_launches(device: int = 0) -> int:
     """Kernel launches of the last filter call on ``device``: 1 (one-launch form) or 3."""
     k = C.c_int()
-    _check(load().ssfm_sosfiltfilt_last(int(device), None, C.byref(k)), "ssfm_sosfiltfilt_last")
+    api.ssfm_sosfiltfilt_last(int(device), None, C.byref(k))
     return int(k.value)
 
 
@@ -260,7 +277,7 @@ class _PinnedBlock:
     def __init__(self, shape, dtype):
         self.nbytes = int(np.prod(shape)) * np.dtype(dtype).itemsize
         p = _VP()
-        _check(load().ssfm_device_alloc(HOST_PINNED, self.nbytes, C.byref(p)), "ssfm_device_alloc")
+        api.ssfm_device_alloc(HOST_PINNED, self.nbytes, C.byref(p))
         self.ptr = int(p.value)
         self.__array_interface__ = {"data": (self.ptr, False), "shape": tuple(shape), "typestr": np.dtype(dtype).str, "version": 3}
 
@@ -302,8 +319,13 @@ class DeviceArray:
         self.nbytes = int(np.prod(self.shape)) * self.dtype.itemsize
         self.ptr = 0
         p = _VP()
-        _check(load().ssfm_device_alloc(self.device, self.nbytes, C.byref(p)), "ssfm_device_alloc")
+        api.ssfm_device_alloc(self.device, self.nbytes, C.byref(p))
         self.ptr = int(p.value)
+
+    @property
+    def _as_parameter_(self):
+        """ctypes passes a DeviceArray as its device pointer wherever the prototype takes a ``void*``."""
+        return self.ptr
 
     # numpy-like metadata (no transfer)
     @property
@@ -336,19 +358,19 @@ class DeviceArray:
     def from_host(cls, a: np.ndarray, dtype=None, device: int = 0) -> "DeviceArray":
         a = np.ascontiguousarray(a, dtype=dtype)
         d = cls(a.shape, a.dtype, device)
-        _check(load().ssfm_device_copy(d.device, _VP(d.ptr), _ptr(a), d.nbytes, 0), "ssfm_device_copy")
+        api.ssfm_device_copy(d.device, d, _ptr(a), d.nbytes, COPY_H2D)
         TRANSFERS["h2d"] += 1
         return d
 
     def to_host(self) -> np.ndarray:
         out = host_empty(self.shape, self.dtype)
-        _check(load().ssfm_device_copy(self.device, _ptr(out), _VP(self.ptr), self.nbytes, 1), "ssfm_device_copy")
+        api.ssfm_device_copy(self.device, _ptr(out), self, self.nbytes, COPY_D2H)
         TRANSFERS["d2h"] += 1
         return out
 
     def copy(self) -> "DeviceArray":
         d = DeviceArray(self.shape, self.dtype, self.device)
-        _check(load().ssfm_device_copy(self.device, _VP(d.ptr), _VP(self.ptr), self.nbytes, 2), "ssfm_device_copy")
+        api.ssfm_device_copy(self.device, d, self, self.nbytes, COPY_D2D)
         return d
 
     def astype(self, dtype) -> "DeviceArray":
@@ -360,7 +382,7 @@ class DeviceArray:
         if self.dtype not in codes or dtype not in codes or codes[dtype] == 2:
             raise TypeError(f"DeviceArray.astype: {self.dtype} -> {dtype} is not supported")
         d = DeviceArray(self.shape, dtype, self.device)
-        _check(load().ssfm_device_convert(self.device, _VP(self.ptr), codes[self.dtype], _VP(d.ptr), codes[dtype], self.size), "ssfm_device_convert")
+        api.ssfm_device_convert(self.device, self, codes[self.dtype], d, codes[dtype], self.size)
         return d
 
     def __add__(self, other: "DeviceArray") -> "DeviceArray":
@@ -368,7 +390,7 @@ class DeviceArray:
             raise TypeError("DeviceArray + DeviceArray needs equal shapes, types and devices")
         codes = {np.dtype(np.complex64): C64, np.dtype(np.complex128): C128}
         d = DeviceArray(self.shape, self.dtype, self.device)
-        _check(load().ssfm_device_add(self.device, _VP(d.ptr), _VP(self.ptr), _VP(other.ptr), codes[self.dtype], self.size), "ssfm_device_add")
+        api.ssfm_device_add(self.device, d, self, other, codes[self.dtype], self.size)
         return d
 
     def __repr__(self):
@@ -380,16 +402,14 @@ def randn_device(shape, std: float, seed: int, stream: int, dtype=np.float64, de
     real and imaginary parts are independent, each of standard deviation ``std``."""
     out = DeviceArray(shape, dtype, device)
     count = out.size * (2 if out.dtype.kind == "c" else 1)
-    _check(load().ssfm_device_randn(out.device, _VP(out.ptr), count, int(seed) & (2 ** 64 - 1), int(stream) & (2 ** 64 - 1), 0.0, float(std)),
-           "ssfm_device_randn")
+    api.ssfm_device_randn(out.device, out, count, int(seed) & (2 ** 64 - 1), int(stream) & (2 ** 64 - 1), 0.0, float(std))
     return out
 
 
 def sum3_device(a, b, c, offset: float, scale: float, like: DeviceArray) -> DeviceArray:
     """``(a + b + c + offset) * scale`` on float64 device arrays (any of a, b, c may be None)."""
     out = DeviceArray(like.shape, np.float64, like.device)
-    p = lambda x: None if x is None else _VP(x.ptr)
-    _check(load().ssfm_device_sum3(like.device, _VP(out.ptr), p(a), p(b), p(c), float(offset), float(scale), out.size), "ssfm_device_sum3")
+    api.ssfm_device_sum3(like.device, out, a, b, c, float(offset), float(scale), out.size)
     return out
 
 
@@ -397,27 +417,27 @@ def scale_add_device(a: DeviceArray, factor: float, b=None) -> DeviceArray:
     """``a * factor (+ b)`` for float64 / complex128 device arrays (real ``factor``)."""
     out = DeviceArray(a.shape, a.dtype, a.device)
     count = a.size * (2 if a.dtype.kind == "c" else 1)
-    _check(load().ssfm_device_scale_add(a.device, _VP(out.ptr), _VP(a.ptr), float(factor), None if b is None else _VP(b.ptr), count), "ssfm_device_scale_add")
+    api.ssfm_device_scale_add(a.device, out, a, float(factor), b, count)
     return out
 
 
 def mean_device(a: DeviceArray, b=None) -> float:
     m = _D()
-    _check(load().ssfm_device_reduce(a.device, REDUCE_MEAN, _VP(a.ptr), None if b is None else _VP(b.ptr), 1, a.size, 0, C.byref(m)), "ssfm_device_reduce")
+    api.ssfm_device_reduce(a.device, REDUCE_MEAN, a, b, 1, a.size, 0, C.byref(m))
     return float(m.value)
 
 
 def axpb_device(a: DeviceArray, alpha: float, beta: float) -> DeviceArray:
     """``a * alpha + beta`` (float64 or complex128 device array; ``beta`` real)."""
     out = DeviceArray(a.shape, a.dtype, a.device)
-    _check(load().ssfm_device_axpb(a.device, _VP(out.ptr), _VP(a.ptr), float(alpha), float(beta), a.size, int(a.dtype.kind == "c")), "ssfm_device_axpb")
+    api.ssfm_device_axpb(a.device, out, a, float(alpha), float(beta), a.size, int(a.dtype.kind == "c"))
     return out
 
 
 def chirp_device(n: int, conj: bool, device: int = 0) -> DeviceArray:
     """``exp(-i pi m^2 / n)`` (or its conjugate), m < n, complex128, generated on the device."""
     out = DeviceArray((int(n),), np.complex128, device)
-    _check(load().ssfm_device_chirp(int(device), _VP(out.ptr), int(n), int(bool(conj))), "ssfm_device_chirp")
+    api.ssfm_device_chirp(int(device), out, int(n), int(bool(conj)))
     return out
 
 
@@ -425,7 +445,7 @@ def mean2_device(a: DeviceArray):
     """``numpy.mean`` of a float64 / complex128 device array (a Python float or complex)."""
     m = (_D * 2)()
     cplx = a.dtype.kind == "c"
-    _check(load().ssfm_device_reduce(a.device, REDUCE_MEAN2, _VP(a.ptr), None, 1, a.size, int(cplx), m), "ssfm_device_reduce")
+    api.ssfm_device_reduce(a.device, REDUCE_MEAN2, a, None, 1, a.size, int(cplx), m)
     return complex(m[0], m[1]) if cplx else float(m[0])
 
 
@@ -433,20 +453,20 @@ def shift_device(a: DeviceArray, value) -> DeviceArray:
     """``a + value`` (float64 / complex128 device array; complex ``value`` for a complex array)."""
     out = DeviceArray(a.shape, a.dtype, a.device)
     v = complex(value)
-    _check(load().ssfm_device_shift(a.device, _VP(out.ptr), _VP(a.ptr), a.size, int(a.dtype.kind == "c"), v.real, v.imag), "ssfm_device_shift")
+    api.ssfm_device_shift(a.device, out, a, a.size, int(a.dtype.kind == "c"), v.real, v.imag)
     return out
 
 
 def zeros_device(shape, dtype, device: int = 0) -> DeviceArray:
     out = DeviceArray(shape, dtype, device)
-    _check(load().ssfm_device_copy(out.device, _VP(out.ptr), None, out.nbytes, 3), "ssfm_device_copy")
+    api.ssfm_device_copy(out.device, out, None, out.nbytes, COPY_ZERO)
     return out
 
 
 def power_device(ptr: int, rows: int, n: int, is_complex: bool, device: int = 0) -> np.ndarray:
     """Mean ``|x|^2`` of each of ``rows`` rows of ``n`` values at device address ``ptr``."""
     out = (_D * int(rows))()
-    _check(load().ssfm_device_reduce(int(device), REDUCE_POWER, _VP(ptr), None, int(rows), int(n), int(bool(is_complex)), out), "ssfm_device_reduce")
+    api.ssfm_device_reduce(int(device), REDUCE_POWER, ptr, None, int(rows), int(n), int(bool(is_complex)), out)
     return np.array(out[:], dtype=np.float64)
 
 
@@ -454,13 +474,13 @@ def prbs_device(order: int, length: int, seed: int, device: int = 0):
     """The reference's LFSR on the device: ``(bits DeviceArray uint8 (length,), final register state)``."""
     out = DeviceArray((int(length),), np.uint8, device)
     last = C.c_uint32(0)
-    _check(load().ssfm_prbs(int(device), _VP(out.ptr), int(length), int(order), C.c_uint32(int(seed)), C.byref(last)), "ssfm_prbs")
+    api.ssfm_prbs(int(device), out, int(length), int(order), C.c_uint32(int(seed)), C.byref(last))
     return out, int(last.value)
 
 
 def real_device(a: DeviceArray) -> DeviceArray:
     out = DeviceArray(a.shape, np.float64, a.device)
-    _check(load().ssfm_device_convert(a.device, _VP(a.ptr), C128, _VP(out.ptr), F64_REAL, a.size), "ssfm_device_convert")
+    api.ssfm_device_convert(a.device, a, C128, out, F64_REAL, a.size)
     return out
 
 
@@ -470,37 +490,35 @@ def mzm_device(sig: DeviceArray, noise, drive: DeviceArray, drive_noise, k, bias
     n_pol = 1 if sig.ndim == 1 else sig.shape[0]
     out_s = DeviceArray(sig.shape, np.complex128, sig.device)
     out_n = None if noise is None else DeviceArray(sig.shape, np.complex128, sig.device)
-    p = lambda x: None if x is None else _VP(x.ptr)
-    _check(load().ssfm_mzm(sig.device, _VP(out_s.ptr), p(out_n), _VP(sig.ptr), p(noise), n_pol, n, _VP(drive.ptr), p(drive_noise),
-                           int(drive.dtype.kind == "c"), float(k), float(bias), float(sqrt_loss), float(half_eta), int(dead_pol)), "ssfm_mzm")
+    api.ssfm_mzm(sig.device, out_s, out_n, sig, noise, n_pol, n, drive, drive_noise,
+                 int(drive.dtype.kind == "c"), float(k), float(bias), float(sqrt_loss), float(half_eta), int(dead_pol))
     return out_s, out_n
 
 
 def cumsum_device(a: DeviceArray) -> DeviceArray:
     """``numpy.cumsum`` of a 1-D float64 device array."""
     out = DeviceArray(a.shape, np.float64, a.device)
-    _check(load().ssfm_device_cumsum(a.device, _VP(out.ptr), _VP(a.ptr), a.size), "ssfm_device_cumsum")
+    api.ssfm_device_cumsum(a.device, out, a, a.size)
     return out
 
 
 def min_device(a: DeviceArray) -> float:
     m = C.c_double()
-    _check(load().ssfm_device_reduce(a.device, REDUCE_MIN, _VP(a.ptr), None, 1, a.size, 0, C.byref(m)), "ssfm_device_reduce")
+    api.ssfm_device_reduce(a.device, REDUCE_MIN, a, None, 1, a.size, 0, C.byref(m))
     return float(m.value)
 
 
 def laser_device(n: int, amp: float, phase, rin, w, step: float, stop: float, device: int = 0) -> DeviceArray:
     """``ssfm_laser``: the CW field with optional phase noise / intensity noise (float64 DeviceArrays) / frequency offset ``w``."""
     out = DeviceArray((n,), np.complex128 if (phase is not None or w is not None) else np.float64, device)
-    p = lambda x: None if x is None else _VP(x.ptr)
-    _check(load().ssfm_laser(int(device), _VP(out.ptr), int(n), float(amp), p(phase), p(rin), int(w is not None), float(w or 0.0), float(step), float(stop)), "ssfm_laser")
+    api.ssfm_laser(int(device), out, int(n), float(amp), phase, rin, int(w is not None), float(w or 0.0), float(step), float(stop))
     return out
 
 
 def device_mem_info(device: int = 0):
     """(free, total, pooled) bytes of HBM on ``device``; ``pooled`` = freed buffers the library keeps for reuse."""
     f, t, p = C.c_size_t(), C.c_size_t(), C.c_size_t()
-    _check(load().ssfm_device_mem_info(int(device), C.byref(f), C.byref(t), C.byref(p)), "ssfm_device_mem_info")
+    api.ssfm_device_mem_info(int(device), C.byref(f), C.byref(t), C.byref(p))
     return int(f.value), int(t.value), int(p.value)
 
 
@@ -510,8 +528,7 @@ def square_law_device(signal: DeviceArray, noise, r: float, post: float = 1.0):
     n_pol = 1 if signal.ndim == 1 else signal.shape[0]
     i_sig = DeviceArray((n,), np.float64, signal.device)
     i_noise = None if noise is None else DeviceArray((n,), np.float64, signal.device)
-    _check(load().ssfm_square_law(signal.device, _VP(signal.ptr), None if noise is None else _VP(noise.ptr), n_pol, n, float(r), float(post),
-                                  _VP(i_sig.ptr), None if noise is None else _VP(i_noise.ptr), 1), "ssfm_square_law")
+    api.ssfm_square_law(signal.device, signal, noise, n_pol, n, float(r), float(post), i_sig, i_noise, 1)
     return i_sig, i_noise
 
 
@@ -520,9 +537,8 @@ class Plan:
 
     def __init__(self, n: int, batch: int, precision: int = C64, device: int = 0):
         self._h = None
-        lib = load()
         h = _VP()
-        _check(lib.ssfm_plan_create(C.byref(h), int(device), int(n), int(batch), int(precision)), "ssfm_plan_create")
+        api.ssfm_plan_create(C.byref(h), int(device), int(n), int(batch), int(precision))
         self._h = h
         self.n, self.batch, self.precision, self.device = int(n), int(batch), int(precision), int(device)
         self.cdtype = _CDTYPE[precision]
@@ -535,11 +551,11 @@ class Plan:
     # what the staging buffers hold is the C plan's knowledge (ssfm_plan_set_tag / _get_tag): 0 operator, 1 / 2 table slots
     def tag(self, which: int) -> int:
         t = C.c_uint64(0)
-        _check(load().ssfm_plan_get_tag(self._h, int(which), C.byref(t)), "ssfm_plan_get_tag")
+        api.ssfm_plan_get_tag(self._h, int(which), C.byref(t))
         return int(t.value)
 
     def set_tag(self, which: int, tag: int):
-        _check(load().ssfm_plan_set_tag(self._h, int(which), C.c_uint64(int(tag) & (2 ** 64 - 1))), "ssfm_plan_set_tag")
+        api.ssfm_plan_set_tag(self._h, int(which), C.c_uint64(int(tag) & (2 ** 64 - 1)))
 
     @property
     def closed(self) -> bool:
@@ -561,34 +577,33 @@ class Plan:
         d = np.ascontiguousarray(dtilde, dtype=self.cdtype)
         if d.shape != (self.n,):
             raise ValueError(f"D~ must have shape ({self.n},), got {d.shape}")
-        _check(load().ssfm_set_linear_operator(self._h, _ptr(d)), "ssfm_set_linear_operator")
+        api.ssfm_set_linear_operator(self._h, _ptr(d))
 
     def set_field(self, field: np.ndarray):
         f = np.ascontiguousarray(field, dtype=self.cdtype).reshape(self.batch, self.n)
-        _check(load().ssfm_set_field(self._h, _ptr(f), 0), "ssfm_set_field")
+        api.ssfm_set_field(self._h, _ptr(f), 0)
 
     def set_field_device(self, dev_ptr: int):
-        _check(load().ssfm_set_field(self._h, C.c_void_p(dev_ptr), 1), "ssfm_set_field")
+        api.ssfm_set_field(self._h, C.c_void_p(dev_ptr), 1)
 
     def get_field(self) -> np.ndarray:
         out = host_empty((self.batch, self.n), self.cdtype)
-        _check(load().ssfm_get_field(self._h, _ptr(out), 0), "ssfm_get_field")
+        api.ssfm_get_field(self._h, _ptr(out), 0)
         return out
 
     def get_field_device(self, dev_ptr: int):
-        _check(load().ssfm_get_field(self._h, C.c_void_p(dev_ptr), 1), "ssfm_get_field")
+        api.ssfm_get_field(self._h, C.c_void_p(dev_ptr), 1)
 
     def copy_into_field(self, byte_offset: int, src_ptr: int, nbytes: int, on_device: bool):
         """Raw copy into the plan's field buffer at ``byte_offset`` (rows of several arrays side by side)."""
-        _check(load().ssfm_synchronize(self._h), "ssfm_synchronize")
-        _check(load().ssfm_device_copy(self.device, _VP(self.field_device_ptr + byte_offset), _VP(src_ptr), nbytes, 2 if on_device else 0),
-               "ssfm_device_copy")
+        api.ssfm_synchronize(self._h)
+        api.ssfm_device_copy(self.device, self.field_device_ptr + byte_offset, src_ptr, nbytes, COPY_D2D if on_device else COPY_H2D)
         TRANSFERS["h2d"] += 0 if on_device else 1
 
     def copy_from_field(self, byte_offset: int, dst_dev_ptr: int, nbytes: int):
         """Raw device-to-device copy out of the plan's field buffer."""
-        _check(load().ssfm_synchronize(self._h), "ssfm_synchronize")
-        _check(load().ssfm_device_copy(self.device, _VP(dst_dev_ptr), _VP(self.field_device_ptr + byte_offset), nbytes, 2), "ssfm_device_copy")
+        api.ssfm_synchronize(self._h)
+        api.ssfm_device_copy(self.device, dst_dev_ptr, self.field_device_ptr + byte_offset, nbytes, COPY_D2D)
 
     @property
     def field_device_ptr(self) -> int:
@@ -604,8 +619,7 @@ class Plan:
         snap = None
         if snapshots:
             snap = host_empty((hs.size + 1, self.batch, self.n), self.cdtype)
-        _check(load().ssfm_propagate_fixed(self._h, float(gamma), _ptr(hs), hs.size,
-                                           _ptr(snap) if snap is not None else None), "ssfm_propagate_fixed")
+        api.ssfm_propagate_fixed(self._h, float(gamma), _ptr(hs), hs.size, _ptr(snap) if snap is not None else None)
         return snap
 
     def propagate_fixed_capture(self, gamma: float, h_schedule, every=None, scalars: bool = False) -> dict:
@@ -630,7 +644,7 @@ class Plan:
         if scalars:
             raw = host_empty((hs.size + 1, self.batch, 2), np.float64)
             cap.scalars = raw.ctypes.data
-        _check(load().ssfm_propagate_fixed_capture(self._h, float(gamma), _ptr(hs), hs.size, C.byref(cap)), "ssfm_propagate_fixed_capture")
+        api.ssfm_propagate_fixed_capture(self._h, float(gamma), _ptr(hs), hs.size, C.byref(cap))
         self.synchronize()
         if raw is not None:
             out["power"], out["peak"] = raw[..., 0].copy(), raw[..., 1].copy()
@@ -640,23 +654,22 @@ class Plan:
         """Adaptive run; returns ``(steps, z float64 (steps + 1,), snapshots or None)``.  A z-resolved capture is taken in
         blocks of at most 256 MiB of page-locked memory (``ssfm_adaptive_run``), so its memory follows the steps actually
         taken, not ``max_steps``."""
-        lib = load()
         steps, done = _I64(0), _I(0)
         if not snapshots:
-            _check(lib.ssfm_adaptive_begin(self._h, float(gamma), float(length), float(phi_max), int(bool(single_step)), int(max_steps), 0), "ssfm_adaptive_begin")
-            _check(lib.ssfm_adaptive_run(self._h, int(max_steps), None, C.byref(steps), C.byref(done)), "ssfm_adaptive_run")
+            api.ssfm_adaptive_begin(self._h, float(gamma), float(length), float(phi_max), int(bool(single_step)), int(max_steps), 0)
+            api.ssfm_adaptive_run(self._h, int(max_steps), None, C.byref(steps), C.byref(done))
             blocks = None
         else:
             blocks = [self.get_field().reshape(1, self.batch, self.n)]                      # the input (devices.py:1150-1152)
-            _check(lib.ssfm_adaptive_begin(self._h, float(gamma), float(length), float(phi_max), int(bool(single_step)), int(max_steps), 1), "ssfm_adaptive_begin")
+            api.ssfm_adaptive_begin(self._h, float(gamma), float(length), float(phi_max), int(bool(single_step)), int(max_steps), 1)
             per = max(1, min(64, (256 << 20) // max(1, self.batch * self.n * np.dtype(self.cdtype).itemsize)))
             while not done.value and steps.value < max_steps:
                 before = steps.value
                 blk = host_empty((per, self.batch, self.n), self.cdtype)
-                _check(lib.ssfm_adaptive_run(self._h, per, _ptr(blk), C.byref(steps), C.byref(done)), "ssfm_adaptive_run")
+                api.ssfm_adaptive_run(self._h, per, _ptr(blk), C.byref(steps), C.byref(done))
                 blocks.append(blk[: steps.value - before])
         z = np.zeros(steps.value + 1, dtype=np.float64)
-        _check(lib.ssfm_adaptive_finish(self._h, C.byref(steps), z.ctypes.data_as(C.POINTER(_D))), "ssfm_adaptive_finish")
+        api.ssfm_adaptive_finish(self._h, C.byref(steps), z.ctypes.data_as(C.POINTER(_D)))
         s = steps.value
         snap = None
         if blocks is not None:
@@ -668,7 +681,6 @@ class Plan:
         after the (1-based, ascending) step numbers ``steps``.  Returns ``(n_steps, z float64 (n_steps + 1,), taken int64 (k,), fields (k, batch, n))`` --
         the input and the end field are not among the snapshots (``get_field`` before and after).  ``fields``: a destination made earlier
         (``host_empty((capacity, batch, n), cdtype)``: page-locking a GiB takes longer than the run)."""
-        lib = load()
         if (every is None) == (steps is None):
             raise ValueError("either `every` or `steps`")
         if steps is not None:
@@ -693,11 +705,11 @@ class Plan:
         cap = AdaptiveCapture(every if want is None else 0, want.ctypes.data_as(C.POINTER(C.c_int64)) if want is not None else None, 0 if want is None else want.size,
                               fields.ctypes.data, capacity, taken.ctypes.data_as(C.POINTER(C.c_int64)), C.pointer(n_taken))
         nsteps, done = _I64(0), _I(0)
-        _check(lib.ssfm_adaptive_begin(self._h, float(gamma), float(length), float(phi_max), 0, int(max_steps), 0), "ssfm_adaptive_begin")
-        _check(lib.ssfm_adaptive_set_capture(self._h, C.byref(cap)), "ssfm_adaptive_set_capture")
-        _check(lib.ssfm_adaptive_run(self._h, int(max_steps), None, C.byref(nsteps), C.byref(done)), "ssfm_adaptive_run")
+        api.ssfm_adaptive_begin(self._h, float(gamma), float(length), float(phi_max), 0, int(max_steps), 0)
+        api.ssfm_adaptive_set_capture(self._h, C.byref(cap))
+        api.ssfm_adaptive_run(self._h, int(max_steps), None, C.byref(nsteps), C.byref(done))
         z = np.zeros(nsteps.value + 1, dtype=np.float64)
-        _check(lib.ssfm_adaptive_finish(self._h, C.byref(nsteps), z.ctypes.data_as(C.POINTER(_D))), "ssfm_adaptive_finish")
+        api.ssfm_adaptive_finish(self._h, C.byref(nsteps), z.ctypes.data_as(C.POINTER(_D)))
         k = int(n_taken.value)
         return nsteps.value, z, taken[:k].copy(), fields[:k]
 
@@ -705,12 +717,12 @@ class Plan:
         h = np.ascontiguousarray(H, dtype=self.cdtype)
         if h.shape != (self.n,):
             raise ValueError(f"H must have shape ({self.n},), got {h.shape}")
-        _check(load().ssfm_apply_transfer(self._h, _ptr(h)), "ssfm_apply_transfer")
+        api.ssfm_apply_transfer(self._h, _ptr(h))
 
     def apply_dispersion(self, dt: float, D_s2: float, want_H: bool = False):
         """DM with H generated on the device; returns natural-order H if ``want_H``."""
         H = np.empty(self.n, dtype=self.cdtype) if want_H else None
-        _check(load().ssfm_apply_dispersion(self._h, float(dt), float(D_s2), _ptr(H) if want_H else None), "ssfm_apply_dispersion")
+        api.ssfm_apply_dispersion(self._h, float(dt), float(D_s2), _ptr(H) if want_H else None)
         return H
 
     # -- building blocks of the chirp-z path (lengths that are not powers of two)
@@ -718,47 +730,47 @@ class Plan:
         h = np.ascontiguousarray(H, dtype=self.cdtype)
         if h.shape != (self.n,):
             raise ValueError(f"H must have shape ({self.n},), got {h.shape}")
-        _check(load().ssfm_transfer_table(self._h, _ptr(h), int(slot)), "ssfm_transfer_table")
+        api.ssfm_transfer_table(self._h, _ptr(h), int(slot))
 
     def apply_table(self, slot: int):
-        _check(load().ssfm_apply_table(self._h, int(slot)), "ssfm_apply_table")
+        api.ssfm_apply_table(self._h, int(slot))
 
     def load_padded(self, src: "DeviceArray"):
         """field <- the float64 / complex128 device array ``src``, zero-padded to the plan length (batch 1)."""
-        _check(load().ssfm_load_padded(self._h, self.n, _VP(src.ptr), int(src.dtype.kind == "c"), src.size), "ssfm_load_padded")
+        api.ssfm_load_padded(self._h, self.n, src, int(src.dtype.kind == "c"), src.size)
 
     def load_symbols(self, sym: "DeviceArray", up: int):
         """field <- the float64 amplitudes ``sym`` zero-stuffed to ``up`` samples per symbol (sample at ``up // 2``)."""
-        _check(load().ssfm_load_symbols(self._h, self.n, _VP(sym.ptr), 0, sym.size, int(up)), "ssfm_load_symbols")
+        api.ssfm_load_symbols(self._h, self.n, sym, 0, sym.size, int(up))
 
     def load_bits(self, bits: "DeviceArray", up: int):
         """field <- device-resident bits (uint8) as amplitudes 0.0 / 1.0, zero-stuffed to ``up`` samples per bit."""
-        _check(load().ssfm_load_symbols(self._h, self.n, _VP(bits.ptr), 1, bits.size, int(up)), "ssfm_load_symbols")
+        api.ssfm_load_symbols(self._h, self.n, bits, 1, bits.size, int(up))
 
     def load_qpsk(self, bits: "DeviceArray", nsym: int, sps: int):
         """field rows <- QPSK-like symbols from device-resident bits (``ssfm_load_qpsk``)."""
-        _check(load().ssfm_load_qpsk(self._h, self.n, self.batch, _VP(bits.ptr), int(nsym), int(sps)), "ssfm_load_qpsk")
+        api.ssfm_load_qpsk(self._h, self.n, self.batch, bits, int(nsym), int(sps))
 
     def chirp_setup(self, n: int):
         """Slots 0 / 1 <- the transfer functions of Bluestein's two convolutions for fields of ``n`` samples, generated and transformed on the device
         (``ssfm_chirp_setup``; the plan's field is consumed)."""
-        _check(load().ssfm_chirp_setup(self._h, self.n, int(n)), "ssfm_chirp_setup")
+        api.ssfm_chirp_setup(self._h, self.n, int(n))
 
     def load_pulse(self, kind: int, npts: int, start: float, step: float, stop: float, pow2m: int, params):
         """field <- one of the DAC's built-in pulses over ``linspace(start, stop, npts)``, zero-padded (``ssfm_load_pulse``)."""
         p = (C.c_double * 7)(*(list(params) + [0.0] * (7 - len(params))))
-        _check(load().ssfm_load_pulse(self._h, self.n, int(kind), int(npts), float(start), float(step), float(stop), int(pow2m), p), "ssfm_load_pulse")
+        api.ssfm_load_pulse(self._h, self.n, int(kind), int(npts), float(start), float(step), float(stop), int(pow2m), p)
 
     def table_from_field(self, slot: int):
-        _check(load().ssfm_table_from_field(self._h, int(slot)), "ssfm_table_from_field")
+        api.ssfm_table_from_field(self._h, int(slot))
 
     def chirp_transfer(self, A: "DeviceArray", chirp: "DeviceArray", tab: "DeviceArray", exponent: bool):
         """Rows of ``A`` (batch, n complex128) <- ifft(fft(row) * tab), or * exp(tab) with ``exponent`` (``ssfm_chirp_transfer``); asynchronous."""
-        _check(load().ssfm_chirp_transfer(self._h, self.n, self.batch, _VP(A.ptr), _VP(chirp.ptr), _VP(tab.ptr), A.shape[-1], 1 if exponent else 0), "ssfm_chirp_transfer")
+        api.ssfm_chirp_transfer(self._h, self.n, self.batch, A, chirp, tab, A.shape[-1], 1 if exponent else 0)
 
     def chirp_fourier(self, A: "DeviceArray", chirp: "DeviceArray", chirp_conj: "DeviceArray", inverse: bool):
         """Rows of ``A`` (batch, n complex128) <- numpy.fft.fft / ifft of the row (``ssfm_chirp_fourier``); asynchronous."""
-        _check(load().ssfm_chirp_fourier(self._h, self.n, self.batch, _VP(A.ptr), _VP(chirp.ptr), _VP(chirp_conj.ptr), A.shape[-1], 1 if inverse else 0), "ssfm_chirp_fourier")
+        api.ssfm_chirp_fourier(self._h, self.n, self.batch, A, chirp, chirp_conj, A.shape[-1], 1 if inverse else 0)
 
     def chirp_propagate(self, A: "DeviceArray", P: "DeviceArray", chirp: "DeviceArray", Dt: "DeviceArray", gamma: float, hs=None, *, length: float = 0.0,
                         phi_max: float = 0.0, f32: bool = True, max_steps: int = 1 << 20):
@@ -769,13 +781,12 @@ class Plan:
             hs = np.ascontiguousarray(hs, dtype=np.float64)
             if hs.size == 0:                       # (length 0: the reference's loop does not run, devices.py:1172)
                 return 0, None
-            _check(load().ssfm_chirp_propagate(self._h, self.n, self.batch, _VP(A.ptr), _VP(P.ptr), _VP(chirp.ptr), _VP(Dt.ptr), A.shape[-1], float(gamma),
-                                               hs.ctypes.data_as(C.POINTER(_D)), hs.size, 0.0, 0.0, 1 if f32 else 0, 1, None, C.byref(steps)), "ssfm_chirp_propagate")
+            api.ssfm_chirp_propagate(self._h, self.n, self.batch, A, P, chirp, Dt, A.shape[-1], float(gamma),
+                                     hs.ctypes.data_as(C.POINTER(_D)), hs.size, 0.0, 0.0, 1 if f32 else 0, 1, None, C.byref(steps))
             return int(steps.value), None
         z = np.zeros(int(max_steps) + 1, dtype=np.float64)
-        _check(load().ssfm_chirp_propagate(self._h, self.n, self.batch, _VP(A.ptr), _VP(P.ptr), _VP(chirp.ptr), _VP(Dt.ptr), A.shape[-1], float(gamma),
-                                           None, 0, float(length), float(phi_max), 1 if f32 else 0, int(max_steps), z.ctypes.data_as(C.POINTER(_D)), C.byref(steps)),
-               "ssfm_chirp_propagate")
+        api.ssfm_chirp_propagate(self._h, self.n, self.batch, A, P, chirp, Dt, A.shape[-1], float(gamma),
+                                 None, 0, float(length), float(phi_max), 1 if f32 else 0, int(max_steps), z.ctypes.data_as(C.POINTER(_D)), C.byref(steps))
         return int(steps.value), z[: int(steps.value) + 1]
 
     def chirp_propagate_c64(self, A: "DeviceArray", chirp: "DeviceArray", Dt: "DeviceArray", gamma: float, hs=None, *, length: float = 0.0, phi_max: float = 0.0,
@@ -790,14 +801,14 @@ class Plan:
             hs = hs[hs != 0.0]
             if hs.size == 0:
                 return True
-            rc = load().ssfm_chirp_propagate_c64(self._h, _VP(A.ptr), _VP(chirp.ptr), _VP(Dt.ptr), A.shape[-1], float(gamma), hs.ctypes.data_as(C.POINTER(_D)), hs.size,
+            rc = load().ssfm_chirp_propagate_c64(self._h, A, chirp, Dt, A.shape[-1], float(gamma), hs.ctypes.data_as(C.POINTER(_D)), hs.size,
                                                  0.0, 0.0, 1, None, C.byref(steps))
             if rc == 2:
                 return False
             _check(rc, "ssfm_chirp_propagate_c64")
             return True
         z = np.zeros(int(max_steps) + 1, np.float64)
-        rc = load().ssfm_chirp_propagate_c64(self._h, _VP(A.ptr), _VP(chirp.ptr), _VP(Dt.ptr), A.shape[-1], float(gamma), None, 0, float(length), float(phi_max),
+        rc = load().ssfm_chirp_propagate_c64(self._h, A, chirp, Dt, A.shape[-1], float(gamma), None, 0, float(length), float(phi_max),
                                              int(max_steps), z.ctypes.data_as(C.POINTER(_D)), C.byref(steps))
         if rc == 2:
             return None
@@ -806,37 +817,37 @@ class Plan:
 
     def debug_fft(self) -> np.ndarray:
         out = host_empty((self.batch, self.n), self.cdtype)
-        _check(load().ssfm_debug(self._h, 0, 0, _ptr(out)), "ssfm_debug")
+        api.ssfm_debug(self._h, 0, 0, _ptr(out))
         return out
 
     def synchronize(self):
-        _check(load().ssfm_synchronize(self._h), "ssfm_synchronize")
+        api.ssfm_synchronize(self._h)
 
     def set_profiling(self, mode: int):
         """0 off, 1 event per launch (per-class times, perturbs), 2 event per 64 launches (pooled, cheap)."""
-        _check(load().ssfm_set_profiling(self._h, int(mode)), "ssfm_set_profiling")
+        api.ssfm_set_profiling(self._h, int(mode))
 
     @property
     def lanes(self) -> int:
         """Row groups a fixed-step run drives on separate streams, as configured at creation (``ssfm_run_info.lanes_configured``)."""
         r = RunInfo()
-        _check(load().ssfm_last_run_info(self._h, C.byref(r), C.sizeof(r)), "ssfm_last_run_info")
+        api.ssfm_last_run_info(self._h, C.byref(r), C.sizeof(r))
         return int(r.lanes_configured)
 
     def kernel_times(self):
         """{'k_time': (launches, total_ms), 'k_freq': (launches, total_ms)} of the last profiled run."""
         cnt = (_I64 * 2)()
         ms = (_D * 2)()
-        _check(load().ssfm_kernel_times(self._h, cnt, ms), "ssfm_kernel_times")
+        api.ssfm_kernel_times(self._h, cnt, ms)
         return {"k_time": (cnt[0], ms[0]), "k_freq": (cnt[1], ms[1])}
 
     def last_run_info(self) -> dict:
         """Which engine the last run took (``ENGINES``), whether it had to be repeated on a fallback, such repeats over the plan's life,
         and whether the plan's lanes share a hardware queue (include/ssfm_amd.h ``ssfm_last_run_info``).  Synchronises first: a one-launch
         run of a medium plan knows at its end whether its workgroups met."""
-        _check(load().ssfm_synchronize(self._h), "ssfm_synchronize")
+        api.ssfm_synchronize(self._h)
         r = RunInfo()
-        _check(load().ssfm_last_run_info(self._h, C.byref(r), C.sizeof(r)), "ssfm_last_run_info")
+        api.ssfm_last_run_info(self._h, C.byref(r), C.sizeof(r))
         return {"engine": ENGINES[r.engine] if 0 <= r.engine < len(ENGINES) else str(r.engine), "fell_back": bool(r.fell_back),
                 "fallbacks_total": int(r.fallbacks_total), "lanes": int(r.lanes), "lanes_share_queue": bool(r.lanes_share_queue),
                 "lanes_remade": int(r.lanes_remade), "lanes_dropped": bool(r.lanes_dropped), "lane_heals": int(r.lane_heals), "lane_alone_us": float(r.lane_alone_us),
@@ -845,9 +856,9 @@ class Plan:
 
     def lane_fault(self, mode: int):
         """Test hook of the lane health check (include/ssfm_amd.h ``ssfm_debug``, SSFM_DEBUG_LANE_FAULT)."""
-        _check(load().ssfm_debug(self._h, 1, int(mode), None), "ssfm_debug")
+        api.ssfm_debug(self._h, 1, int(mode), None)
 
     def last_propagate_ms(self):
         ms, n = C.c_float(0), _I64(0)
-        _check(load().ssfm_last_propagate_ms(self._h, C.byref(ms), C.byref(n)), "ssfm_last_propagate_ms")
+        api.ssfm_last_propagate_ms(self._h, C.byref(ms), C.byref(n))
         return ms.value, n.value

@@ -26,6 +26,7 @@
 #include "ssfm_common.hpp"
 
 using ssfm::fail;
+using ssfm::grid_for;
 
 namespace {
 
@@ -118,7 +119,6 @@ __global__ __launch_bounds__(256) void k_chirp_post(double2* __restrict__ A, con
     }
 }
 
-unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096); }
 
 struct Target {
     double2* F;
@@ -151,7 +151,7 @@ int chirp_pre(ssfm_plan* plan, int64_t plan_n, int batch, const void* A, void* P
     Target t;
     if (int rc = target_of(plan, n, plan_n, batch, &t)) return rc;
     if (!A || !chirp) return fail(SSFM_ERR_INVALID, "ssfm_chirp_pre: NULL argument");
-    hipLaunchKernelGGL(k_chirp_pre, dim3(blocks_for(t.M * batch)), dim3(256), 0, t.stream, (const double2*)A, (double*)P, (const double2*)chirp, t.F,
+    hipLaunchKernelGGL(k_chirp_pre, dim3(grid_for(t.M * batch, 4096)), dim3(256), 0, t.stream, (const double2*)A, (double*)P, (const double2*)chirp, t.F,
                        (long long)n, t.M, batch, gamma, hh, (const ChirpCtl*)nullptr);
     HIP_TRY(hipGetLastError());
     return SSFM_OK;
@@ -161,7 +161,7 @@ int chirp_mid(ssfm_plan* plan, int64_t plan_n, int batch, const void* tab, int64
     Target t;
     if (int rc = target_of(plan, n, plan_n, batch, &t)) return rc;
     if (!tab || mode < 0 || mode > 1) return fail(SSFM_ERR_INVALID, "ssfm_chirp_mid: bad argument");
-    hipLaunchKernelGGL(k_chirp_mid, dim3(blocks_for(t.M * batch)), dim3(256), 0, t.stream, (const double2*)tab, t.F, (long long)n, t.M, batch, h, mode, (const ChirpCtl*)nullptr);
+    hipLaunchKernelGGL(k_chirp_mid, dim3(grid_for(t.M * batch, 4096)), dim3(256), 0, t.stream, (const double2*)tab, t.F, (long long)n, t.M, batch, h, mode, (const ChirpCtl*)nullptr);
     HIP_TRY(hipGetLastError());
     return SSFM_OK;
 }
@@ -171,7 +171,7 @@ int chirp_post(ssfm_plan* plan, int64_t plan_n, int batch, void* A, const void* 
     if (int rc = target_of(plan, n, plan_n, batch, &t)) return rc;
     if (!A || !chirp || (gamma != 0.0 && !P)) return fail(SSFM_ERR_INVALID, "ssfm_chirp_post: NULL argument");
     if (maxbits_dev) HIP_TRY(hipMemsetAsync(maxbits_dev, 0, sizeof(unsigned long long), t.stream));
-    hipLaunchKernelGGL(k_chirp_post, dim3(blocks_for((long long)n * batch)), dim3(256), 0, t.stream, (double2*)A, (const double*)P, (const double2*)chirp,
+    hipLaunchKernelGGL(k_chirp_post, dim3(grid_for((long long)n * batch, 4096)), dim3(256), 0, t.stream, (double2*)A, (const double*)P, (const double2*)chirp,
                        (const double2*)t.F, (long long)n, t.M, batch, gamma, hh, scale, (unsigned long long*)maxbits_dev, (const ChirpCtl*)nullptr);
     HIP_TRY(hipGetLastError());
     return SSFM_OK;
@@ -272,7 +272,7 @@ extern "C" int ssfm_chirp_propagate(ssfm_plan* plan, int64_t plan_n, int batch, 
         const int64_t pn = ssfm::plan_length(plan, &pb, &prec);
         if (prec != SSFM_C128 || pn != plan_n || pb != batch) return fail(SSFM_ERR_INVALID, "ssfm_chirp_propagate: a complex128 plan of %lld x %d is needed", (long long)plan_n, batch);
     }
-    const unsigned gM = blocks_for(t.M * batch), gN = blocks_for((long long)n * batch);
+    const unsigned gM = grid_for(t.M * batch, 4096), gN = grid_for((long long)n * batch, 4096);
     const double scale = 1.0 / (double)n;
     // A step is FIVE launches (seven in adaptive mode): the middle of it -- inverse pass of the first convolution, product with exp(D~ h), forward pass
     // of the second -- is one column launch with the factors from a table (kept while the step size repeats), and the step's two ends -- chirp
@@ -295,7 +295,7 @@ extern "C" int ssfm_chirp_propagate(ssfm_plan* plan, int64_t plan_n, int batch, 
     auto step = [&](double h, const ChirpCtl* ctl, unsigned long long* mb) -> int {
         if (ctl || !mtab_set || std::memcmp(&mtab_h, &h, sizeof(h)) != 0) {
             const long long entries = lean ? (long long)n : t.M;
-            hipLaunchKernelGGL(k_chirp_mktab, dim3(blocks_for(entries)), dim3(256), 0, t.stream, (const double2*)Dt, mtab, (long long)n, entries, h, ctl);
+            hipLaunchKernelGGL(k_chirp_mktab, dim3(grid_for(entries, 4096)), dim3(256), 0, t.stream, (const double2*)Dt, mtab, (long long)n, entries, h, ctl);
             mtab_h = h; mtab_set = true;
         }
         ssfm::ChirpStepIO io;
@@ -347,7 +347,7 @@ extern "C" int ssfm_chirp_propagate(ssfm_plan* plan, int64_t plan_n, int batch, 
                 if (int rc = ssfm::plan_workspace(plan, 3, sizeof(double2) * (size_t)t.M * distinct.size(), reinterpret_cast<void**>(&tabs))) return rc;       // (a slot of its own: `mtab` above stays valid for the step loop below)
                 const void* mulp[4] = {nullptr, nullptr, nullptr, nullptr};
                 for (size_t i = 0; i < distinct.size(); ++i) {
-                    hipLaunchKernelGGL(k_chirp_mktab, dim3(blocks_for(t.M)), dim3(256), 0, t.stream, (const double2*)Dt, tabs + i * (size_t)t.M, (long long)n, t.M, distinct[i],
+                    hipLaunchKernelGGL(k_chirp_mktab, dim3(grid_for(t.M, 4096)), dim3(256), 0, t.stream, (const double2*)Dt, tabs + i * (size_t)t.M, (long long)n, t.M, distinct[i],
                                        (const ChirpCtl*)nullptr, 1.0 / (double)n);
                     mulp[i] = tabs + i * (size_t)t.M;
                 }
@@ -355,12 +355,12 @@ extern "C" int ssfm_chirp_propagate(ssfm_plan* plan, int64_t plan_n, int batch, 
                 // float64 (ssfm_kernels.hpp time_body, H) -- half the bytes of the field per pass, one rounding to complex64 per pass.  SSFM_CHIRP_HALF=0: never.
                 const char* he = std::getenv("SSFM_CHIRP_HALF");
                 const int half = (f32 && t.M >= (1ll << 18) && !(he && he[0] == '0') && ssfm::plan_line_half_ok(plan)) ? 1 : 0;
-                hipLaunchKernelGGL(k_chirp_pre, dim3(blocks_for(t.M * batch)), dim3(256), 0, t.stream, (const double2*)A, (double*)nullptr, (const double2*)chirp, t.F,
+                hipLaunchKernelGGL(k_chirp_pre, dim3(grid_for(t.M * batch, 4096)), dim3(256), 0, t.stream, (const double2*)A, (double*)nullptr, (const double2*)chirp, t.F,
                                    (long long)n, t.M, batch, 0.0, 0.0, (const ChirpCtl*)nullptr, half);
                 HIP_TRY(hipGetLastError());
                 const int rc = ssfm::plan_chirp_line_run(plan, mulp, which.data(), hs, nsteps, gamma, n, half);
                 if (rc == SSFM_OK) {
-                    hipLaunchKernelGGL(k_chirp_post, dim3(blocks_for((long long)n * batch)), dim3(256), 0, t.stream, (double2*)A, (const double*)nullptr, (const double2*)chirp,
+                    hipLaunchKernelGGL(k_chirp_post, dim3(grid_for((long long)n * batch, 4096)), dim3(256), 0, t.stream, (double2*)A, (const double*)nullptr, (const double2*)chirp,
                                        (const double2*)t.F, (long long)n, t.M, batch, 0.0, 0.0, 1.0, (unsigned long long*)nullptr, (const ChirpCtl*)nullptr, half);
                     HIP_TRY(hipGetLastError());
                     HIP_TRY(hipStreamSynchronize(t.stream));
@@ -556,7 +556,7 @@ extern "C" int ssfm_load_padded(ssfm_plan* plan, int64_t plan_n, const void* src
     Target t;
     if (int rc = target_of(plan, 2, plan_n, 1, &t)) return rc;      // (no length relation to check here)
     if (!src_dev || n_src < 1 || n_src > plan_n) return fail(SSFM_ERR_INVALID, "ssfm_load_padded: %lld source samples for a plan of %lld", (long long)n_src, (long long)plan_n);
-    hipLaunchKernelGGL(k_load_padded, dim3(blocks_for(t.M)), dim3(256), 0, t.stream, (const double*)src_dev, src_complex, (long long)n_src, t.F, t.M);
+    hipLaunchKernelGGL(k_load_padded, dim3(grid_for(t.M, 4096)), dim3(256), 0, t.stream, (const double*)src_dev, src_complex, (long long)n_src, t.F, t.M);
     HIP_TRY(hipGetLastError());
     return SSFM_OK;
 }
@@ -569,7 +569,7 @@ extern "C" int ssfm_load_symbols(ssfm_plan* plan, int64_t plan_n, const void* sr
     Target t;
     if (int rc = target_of(plan, 2, plan_n, 1, &t)) return rc;      // (no length relation to check here)
     if (!sym_dev || nsym < 1 || up < 1 || nsym * up > plan_n) return fail(SSFM_ERR_INVALID, "ssfm_load_symbols: %lld symbols x %d samples for a plan of %lld", (long long)nsym, up, (long long)plan_n);
-    hipLaunchKernelGGL(k_load_symbols, dim3(blocks_for(t.M)), dim3(256), 0, t.stream, sym_dev, (long long)nsym, up, t.F, t.M);
+    hipLaunchKernelGGL(k_load_symbols, dim3(grid_for(t.M, 4096)), dim3(256), 0, t.stream, sym_dev, (long long)nsym, up, t.F, t.M);
     HIP_TRY(hipGetLastError());
     return SSFM_OK;
 }
@@ -580,7 +580,7 @@ extern "C" int ssfm_load_pulse(ssfm_plan* plan, int64_t plan_n, int kind, int64_
     if (kind < 0 || kind > 4 || npts < 1 || npts > plan_n || !params) return fail(SSFM_ERR_INVALID, "ssfm_load_pulse: kind %d, %lld points for a plan of %lld", kind, (long long)npts, (long long)plan_n);
     if (kind == 1 && (pow2m < 2 || pow2m > 98 || (pow2m & 1))) return fail(SSFM_ERR_INVALID, "ssfm_load_pulse: gaussian order 2m = %d outside 2 ... 98", pow2m);
     PulseSpec ps{kind, pow2m, (long long)npts, start, step, stop, params[0], params[1], params[2], params[3], params[4], params[5], params[6]};
-    hipLaunchKernelGGL(k_load_pulse, dim3(blocks_for(t.M)), dim3(256), 0, t.stream, ps, t.F, t.M);
+    hipLaunchKernelGGL(k_load_pulse, dim3(grid_for(t.M, 4096)), dim3(256), 0, t.stream, ps, t.F, t.M);
     HIP_TRY(hipGetLastError());
     return SSFM_OK;
 }
@@ -615,8 +615,8 @@ __global__ __launch_bounds__(256) void k_chirp_kernel(double2* __restrict__ F, l
 
 extern "C" int ssfm_device_chirp(int device, void* out_dev, int64_t n, int conj) {
     if (!out_dev || n < 2 || n > (1ll << 30)) return fail(SSFM_ERR_INVALID, "ssfm_device_chirp: bad argument");
-    HIP_TRY(hipSetDevice(device));
-    hipLaunchKernelGGL(k_chirp, dim3(blocks_for(n)), dim3(256), 0, 0, (double2*)out_dev, (long long)n, conj);
+    if (int rc = ssfm::use_device(device)) return rc;
+    hipLaunchKernelGGL(k_chirp, dim3(grid_for(n, 4096)), dim3(256), 0, 0, (double2*)out_dev, (long long)n, conj);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     return SSFM_OK;
@@ -630,7 +630,7 @@ extern "C" int ssfm_chirp_setup(ssfm_plan* plan, int64_t plan_n, int64_t n) {
     if (int rc = target_of(plan, n, plan_n, 1, &t)) return rc;
     if (n > (1ll << 30)) return fail(SSFM_ERR_INVALID, "ssfm_chirp_setup: bad argument");
     for (int which = 0; which < 2; ++which) {
-        hipLaunchKernelGGL(k_chirp_kernel, dim3(blocks_for(t.M)), dim3(256), 0, t.stream, t.F, (long long)n, t.M, which);
+        hipLaunchKernelGGL(k_chirp_kernel, dim3(grid_for(t.M, 4096)), dim3(256), 0, t.stream, t.F, (long long)n, t.M, which);
         HIP_TRY(hipGetLastError());
         if (int rc = ssfm_table_from_field(plan, which)) return rc;
     }

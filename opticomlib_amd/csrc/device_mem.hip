@@ -12,6 +12,9 @@
 #include "ssfm_common.hpp"
 
 using ssfm::fail;
+using ssfm::grid_for;
+using ssfm::kMaxDevices;
+using ssfm::use_device;
 
 namespace {
 
@@ -22,19 +25,10 @@ struct Pool {
     std::unordered_map<size_t, std::vector<void*>> free_by_size;
     size_t cached_bytes = 0;
 };
-constexpr int kMaxDevices = 64;
 constexpr size_t kMaxCachedBytes = size_t(2) << 30;        // per device
 Pool g_pool[kMaxDevices];
 Pool g_host_pool;                                          // page-locked host buffers (ssfm_host_alloc)
 constexpr size_t kMaxCachedHostBytes = size_t(1) << 30;
-
-int use(int device) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count || device >= kMaxDevices)
-        return fail(SSFM_ERR_NO_DEVICE, "device %d not available", device);
-    HIP_TRY(hipSetDevice(device));
-    return SSFM_OK;
-}
 
 template <typename S, typename D>
 __global__ __launch_bounds__(256) void k_convert(const S* __restrict__ src, D* __restrict__ dst, long long count2) {
@@ -51,7 +45,6 @@ template <typename T>
 __global__ __launch_bounds__(256) void k_add(T* __restrict__ dst, const T* __restrict__ a, const T* __restrict__ b, long long count2) {
     for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < count2; i += (long long)gridDim.x * blockDim.x) dst[i] = a[i] + b[i];
 }
-unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192); }
 
 
 // Running sum (numpy.cumsum) of n doubles in three launches: every workgroup scans a tile of 256 x 16 samples and
@@ -138,7 +131,7 @@ int host_free(void* ptr, size_t bytes);
 extern "C" int ssfm_device_alloc(int device, size_t bytes, void** out) {
     if (!out || bytes == 0) return fail(SSFM_ERR_INVALID, "ssfm_device_alloc: bytes=%zu", bytes);
     if (device == SSFM_HOST_PINNED) return host_alloc(bytes, out);
-    if (int rc = use(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     Pool& p = g_pool[device];
     {
         std::lock_guard<std::mutex> lock(p.mu);
@@ -169,7 +162,7 @@ extern "C" int ssfm_device_alloc(int device, size_t bytes, void** out) {
 extern "C" int ssfm_device_free(int device, void* ptr, size_t bytes) {
     if (!ptr) return SSFM_OK;
     if (device == SSFM_HOST_PINNED) return host_free(ptr, bytes);
-    if (int rc = use(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     Pool& p = g_pool[device];
     {
         std::lock_guard<std::mutex> lock(p.mu);
@@ -220,7 +213,7 @@ int host_free(void* ptr, size_t bytes) {
 extern "C" int ssfm_device_copy(int device, void* dst, const void* src, size_t bytes, int kind) {
     if (!dst || (!src && kind != 3)) return fail(SSFM_ERR_INVALID, "ssfm_device_copy: NULL argument");
     if (kind < 0 || kind > 3) return fail(SSFM_ERR_INVALID, "ssfm_device_copy: kind=%d (0 host->device, 1 device->host, 2 device->device, 3 zero bytes)", kind);
-    if (int rc = use(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     if (kind == 3) { HIP_TRY(hipMemset(dst, 0, bytes)); return SSFM_OK; }
     const hipMemcpyKind k = kind == 0 ? hipMemcpyHostToDevice : kind == 1 ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
     HIP_TRY(hipMemcpy(dst, src, bytes, k));
@@ -230,18 +223,18 @@ extern "C" int ssfm_device_copy(int device, void* dst, const void* src, size_t b
 
 extern "C" int ssfm_device_convert(int device, const void* src, int src_precision, void* dst, int dst_precision, int64_t count) {
     if (!dst || !src || count < 1) return fail(SSFM_ERR_INVALID, "ssfm_device_convert: bad argument");
-    if (int rc = use(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     const long long c2 = 2 * (long long)count;
     if (src_precision == SSFM_C64 && dst_precision == SSFM_C128)
-        hipLaunchKernelGGL((k_convert<float, double>), dim3(blocks_for(c2)), dim3(256), 0, 0, (const float*)src, (double*)dst, c2);
+        hipLaunchKernelGGL((k_convert<float, double>), dim3(grid_for(c2, 8192)), dim3(256), 0, 0, (const float*)src, (double*)dst, c2);
     else if (src_precision == SSFM_C128 && dst_precision == SSFM_C64)
-        hipLaunchKernelGGL((k_convert<double, float>), dim3(blocks_for(c2)), dim3(256), 0, 0, (const double*)src, (float*)dst, c2);
+        hipLaunchKernelGGL((k_convert<double, float>), dim3(grid_for(c2, 8192)), dim3(256), 0, 0, (const double*)src, (float*)dst, c2);
     else if (src_precision == SSFM_F64_REAL && dst_precision == SSFM_C128)
-        hipLaunchKernelGGL((k_widen<double>), dim3(blocks_for(count)), dim3(256), 0, 0, (const double*)src, (double*)dst, (long long)count);
+        hipLaunchKernelGGL((k_widen<double>), dim3(grid_for(count, 8192)), dim3(256), 0, 0, (const double*)src, (double*)dst, (long long)count);
     else if (src_precision == SSFM_F64_REAL && dst_precision == SSFM_C64)
-        hipLaunchKernelGGL((k_widen<float>), dim3(blocks_for(count)), dim3(256), 0, 0, (const double*)src, (float*)dst, (long long)count);
+        hipLaunchKernelGGL((k_widen<float>), dim3(grid_for(count, 8192)), dim3(256), 0, 0, (const double*)src, (float*)dst, (long long)count);
     else if (src_precision == SSFM_C128 && dst_precision == SSFM_F64_REAL)
-        hipLaunchKernelGGL(k_real_part, dim3(blocks_for(count)), dim3(256), 0, 0, (double*)dst, (const double2*)src, (long long)count);
+        hipLaunchKernelGGL(k_real_part, dim3(grid_for(count, 8192)), dim3(256), 0, 0, (double*)dst, (const double2*)src, (long long)count);
     else
         return fail(SSFM_ERR_INVALID, "ssfm_device_convert: precisions %d -> %d", src_precision, dst_precision);
     HIP_TRY(hipGetLastError());
@@ -251,10 +244,10 @@ extern "C" int ssfm_device_convert(int device, const void* src, int src_precisio
 
 extern "C" int ssfm_device_add(int device, void* dst, const void* a, const void* b, int precision, int64_t count) {
     if (!dst || !a || !b || count < 1) return fail(SSFM_ERR_INVALID, "ssfm_device_add: bad argument");
-    if (int rc = use(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     const long long c2 = 2 * (long long)count;
-    if (precision == SSFM_C64) hipLaunchKernelGGL(k_add<float>, dim3(blocks_for(c2)), dim3(256), 0, 0, (float*)dst, (const float*)a, (const float*)b, c2);
-    else if (precision == SSFM_C128) hipLaunchKernelGGL(k_add<double>, dim3(blocks_for(c2)), dim3(256), 0, 0, (double*)dst, (const double*)a, (const double*)b, c2);
+    if (precision == SSFM_C64) hipLaunchKernelGGL(k_add<float>, dim3(grid_for(c2, 8192)), dim3(256), 0, 0, (float*)dst, (const float*)a, (const float*)b, c2);
+    else if (precision == SSFM_C128) hipLaunchKernelGGL(k_add<double>, dim3(grid_for(c2, 8192)), dim3(256), 0, 0, (double*)dst, (const double*)a, (const double*)b, c2);
     else return fail(SSFM_ERR_INVALID, "ssfm_device_add: precision %d", precision);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
@@ -263,7 +256,7 @@ extern "C" int ssfm_device_add(int device, void* dst, const void* a, const void*
 
 extern "C" int ssfm_device_mem_info(int device, size_t* free_bytes, size_t* total_bytes, size_t* pooled_bytes) {
     if (!free_bytes || !total_bytes) return fail(SSFM_ERR_INVALID, "ssfm_device_mem_info: NULL argument");
-    if (int rc = use(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     HIP_TRY(hipMemGetInfo(free_bytes, total_bytes));
     if (pooled_bytes) {
         std::lock_guard<std::mutex> lock(g_pool[device].mu);
@@ -333,8 +326,8 @@ __global__ __launch_bounds__(256) void k_sum(const double* __restrict__ a, const
 
 extern "C" int ssfm_device_randn(int device, double* out_dev, int64_t n, uint64_t seed, uint64_t stream, double mean, double std) {
     if (!out_dev || n < 1) return fail(SSFM_ERR_INVALID, "ssfm_device_randn: bad argument");
-    if (int rc = use(device)) return rc;
-    hipLaunchKernelGGL(k_randn, dim3(blocks_for((n + 1) / 2)), dim3(256), 0, 0, out_dev, (long long)n, (unsigned long long)seed, (unsigned long long)stream, mean, std);
+    if (int rc = use_device(device)) return rc;
+    hipLaunchKernelGGL(k_randn, dim3(grid_for((n + 1) / 2, 8192)), dim3(256), 0, 0, out_dev, (long long)n, (unsigned long long)seed, (unsigned long long)stream, mean, std);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     return SSFM_OK;
@@ -342,8 +335,8 @@ extern "C" int ssfm_device_randn(int device, double* out_dev, int64_t n, uint64_
 
 extern "C" int ssfm_device_sum3(int device, double* out_dev, const double* a, const double* b, const double* c, double offset, double scale, int64_t n) {
     if (!out_dev || n < 1) return fail(SSFM_ERR_INVALID, "ssfm_device_sum3: bad argument");
-    if (int rc = use(device)) return rc;
-    hipLaunchKernelGGL(k_sum3, dim3(blocks_for(n)), dim3(256), 0, 0, out_dev, a, b, c, offset, scale, (long long)n);
+    if (int rc = use_device(device)) return rc;
+    hipLaunchKernelGGL(k_sum3, dim3(grid_for(n, 8192)), dim3(256), 0, 0, out_dev, a, b, c, offset, scale, (long long)n);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     return SSFM_OK;
@@ -351,8 +344,8 @@ extern "C" int ssfm_device_sum3(int device, double* out_dev, const double* a, co
 
 extern "C" int ssfm_device_scale_add(int device, double* dst, const double* a, double factor, const double* b, int64_t n) {
     if (!dst || !a || n < 1) return fail(SSFM_ERR_INVALID, "ssfm_device_scale_add: bad argument");
-    if (int rc = use(device)) return rc;
-    hipLaunchKernelGGL(k_scale_add, dim3(blocks_for(n)), dim3(256), 0, 0, dst, a, factor, b, (long long)n);
+    if (int rc = use_device(device)) return rc;
+    hipLaunchKernelGGL(k_scale_add, dim3(grid_for(n, 8192)), dim3(256), 0, 0, dst, a, factor, b, (long long)n);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     return SSFM_OK;
@@ -361,7 +354,7 @@ extern "C" int ssfm_device_scale_add(int device, double* dst, const double* a, d
 namespace ssfm { SSFM_INTERNAL int device_mean(int device, const double* a, const double* b, int64_t n, double* mean_out); SSFM_INTERNAL int device_min(int device, const double* a, int64_t n, double* min_out); }
 int ssfm::device_mean(int device, const double* a, const double* b, int64_t n, double* mean_out) {
     if (!a || !mean_out || n < 1) return fail(SSFM_ERR_INVALID, "ssfm_device_reduce (mean): bad argument");
-    if (int rc = use(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     constexpr int kBlocks = 1024;
     double* partial = nullptr;
     if (int rc = ssfm_device_alloc(device, sizeof(double) * kBlocks, (void**)&partial)) return rc;
@@ -378,7 +371,7 @@ int ssfm::device_mean(int device, const double* a, const double* b, int64_t n, d
 
 extern "C" int ssfm_device_cumsum(int device, double* dst, const double* src, int64_t n) {
     if (!dst || !src || n < 1) return fail(SSFM_ERR_INVALID, "ssfm_device_cumsum: bad argument");
-    if (int rc = use(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     const int ntiles = (int)((n + kScanTile - 1) / kScanTile);
     double* totals = nullptr;
     if (int rc = ssfm_device_alloc(device, sizeof(double) * ntiles, (void**)&totals)) return rc;
@@ -396,7 +389,7 @@ extern "C" int ssfm_device_cumsum(int device, double* dst, const double* src, in
 
 int ssfm::device_min(int device, const double* a, int64_t n, double* min_out) {
     if (!a || !min_out || n < 1) return fail(SSFM_ERR_INVALID, "ssfm_device_reduce (min): bad argument");
-    if (int rc = use(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     constexpr int kBlocks = 1024;
     double* partial = nullptr;
     if (int rc = ssfm_device_alloc(device, sizeof(double) * kBlocks, (void**)&partial)) return rc;

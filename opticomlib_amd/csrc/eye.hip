@@ -22,6 +22,9 @@
 #include "ssfm_common.hpp"
 
 using ssfm::fail;
+using ssfm::grid_for;
+using ssfm::Scratch;
+using ssfm::use_device;
 
 namespace {
 
@@ -612,44 +615,14 @@ __global__ __launch_bounds__(kThreads) void k_count_diff(const unsigned char* __
     if (threadIdx.x == 0) atomicAdd(out, (unsigned long long)v[0]);   // integer atomics: the total does not depend on the order
 }
 
-unsigned grid_for(long long n) {
-    const long long b = (n + kThreads - 1) / kThreads;
-    return (unsigned)(b < 4096 ? (b > 0 ? b : 1) : 4096);
-}
 
-int use(int device) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return fail(SSFM_ERR_NO_DEVICE, "eye: device %d not available", device);
-    HIP_TRY(hipSetDevice(device));
-    return SSFM_OK;
-}
-
-// scratch from the library's pool (ssfm_device_alloc), handed back on every exit
-struct Scratch {
-    int device;
-    void* p[6] = {};
-    size_t b[6] = {};
-    int k = 0;
-    bool drained = false;                                          // set after a blocking copy on the null stream: nothing of ours is in flight
-    explicit Scratch(int d) : device(d) {}
-    int get(size_t bytes, void** out) {
-        if (int rc = ssfm_device_alloc(device, bytes, out)) return rc;
-        p[k] = *out;
-        b[k++] = bytes;
-        return SSFM_OK;
-    }
-    ~Scratch() {
-        if (k && !drained) (void)hipDeviceSynchronize();         // (error paths)
-        for (int i = 0; i < k; ++i) (void)ssfm_device_free(device, p[i], b[i]);
-    }
-};
 
 }  // namespace
 
 // ================================================================================================ C ABI
 extern "C" int ssfm_device_sort_f64(int device, double* keys, int64_t n) {
     if (!keys || n < 1 || n > kMaxN) return fail(SSFM_ERR_INVALID, "ssfm_device_sort_f64: n=%lld (1 ... 2^21)", (long long)n);
-    if (int rc = use(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     Scratch s(device);
     void *tmp, *hist;
     if (int rc = s.get(sizeof(double) * n, &tmp)) return rc;
@@ -662,8 +635,8 @@ extern "C" int ssfm_device_sort_f64(int device, double* keys, int64_t n) {
 
 extern "C" int ssfm_eye_prepare(int device, const void* sig, const void* noise, int is_complex, int64_t n, int64_t shift, double* out) {
     if (!sig || !out || n < 1) return fail(SSFM_ERR_INVALID, "ssfm_eye_prepare: bad argument");
-    if (int rc = use(device)) return rc;
-    hipLaunchKernelGGL(k_prepare, dim3(grid_for(n)), dim3(kThreads), 0, 0, sig, noise, is_complex, (long long)n, (long long)shift, out);
+    if (int rc = use_device(device)) return rc;
+    hipLaunchKernelGGL(k_prepare, dim3(grid_for(n, 4096)), dim3(kThreads), 0, 0, sig, noise, is_complex, (long long)n, (long long)shift, out);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());                              // the consumers (the plans' transforms, LPF, FIBER) run on other streams
     return SSFM_OK;
@@ -671,13 +644,13 @@ extern "C" int ssfm_eye_prepare(int device, const void* sig, const void* noise, 
 
 extern "C" int ssfm_eye_resample_stage(int device, int stage, const void* src, int64_t n, void* dst, int64_t m) {
     if (!src || !dst || n < 1 || m < 1 || stage < 0 || stage > 2) return fail(SSFM_ERR_INVALID, "ssfm_eye_resample_stage: stage=%d n=%lld m=%lld", stage, (long long)n, (long long)m);
-    if (int rc = use(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     if (stage == 0)
-        hipLaunchKernelGGL(k_to_complex, dim3(grid_for(n)), dim3(kThreads), 0, 0, (const double*)src, (long long)n, (double2*)dst);
+        hipLaunchKernelGGL(k_to_complex, dim3(grid_for(n, 4096)), dim3(kThreads), 0, 0, (const double*)src, (long long)n, (double2*)dst);
     else if (stage == 1)
-        hipLaunchKernelGGL(k_respectrum, dim3(grid_for(m)), dim3(kThreads), 0, 0, (const double2*)src, (long long)n, (double2*)dst, (long long)m);
+        hipLaunchKernelGGL(k_respectrum, dim3(grid_for(m, 4096)), dim3(kThreads), 0, 0, (const double2*)src, (long long)n, (double2*)dst, (long long)m);
     else
-        hipLaunchKernelGGL(k_real_scale, dim3(grid_for(m)), dim3(kThreads), 0, 0, (const double2*)src, (long long)m, (double)m / (double)n, (double*)dst);
+        hipLaunchKernelGGL(k_real_scale, dim3(grid_for(m, 4096)), dim3(kThreads), 0, 0, (const double2*)src, (long long)m, (double)m / (double)n, (double*)dst);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());                              // the transforms between the stages run on the plan's (non-blocking) stream
     return SSFM_OK;
@@ -687,7 +660,7 @@ extern "C" int ssfm_eye_estimate(int device, const double* y, int64_t n, const d
                                  int64_t n_out, int64_t* round_trips) {
     if (!y || !tgrid || !yset || !out || n < 2 || n > kMaxN || nset < 1 || period < 2 || period > 4096 || n_out < S_COUNT)
         return fail(SSFM_ERR_INVALID, "ssfm_eye_estimate: n=%lld period=%lld nset=%lld n_out=%lld", (long long)n, (long long)period, (long long)nset, (long long)n_out);
-    if (int rc = use(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     Scratch s(device);
     void *sorted, *tmp, *hist, *part, *st, *tg;
     if (int rc = s.get(sizeof(double) * n, &sorted)) return rc;
@@ -773,7 +746,7 @@ extern "C" int ssfm_eye_levels(int device, const double* y, int64_t n, int64_t p
     if (!y || !out || n < 1 || n > kMaxN || period < 1 || n % period != 0 || k_lo < 0 || k_hi < k_lo || k_hi > period || npts < 2 || npts > kKdeThreads ||
         n_out < S_COUNT)
         return fail(SSFM_ERR_INVALID, "ssfm_eye_levels: n=%lld period=%lld k=[%lld, %lld) npts=%d", (long long)n, (long long)period, (long long)k_lo, (long long)k_hi, npts);
-    if (int rc = use(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     Centre c;
     c.period = (int)period;
     c.k_lo = (int)k_lo;
@@ -805,8 +778,8 @@ extern "C" int ssfm_device_sample(int device, const double* x, const double* noi
                                   unsigned char* bits) {
     if (!x || step < 1 || start < 0 || count < 0 || (!vals && !bits)) return fail(SSFM_ERR_INVALID, "ssfm_device_sample: bad argument");
     if (count == 0) return SSFM_OK;
-    if (int rc = use(device)) return rc;
-    hipLaunchKernelGGL(k_sample, dim3(grid_for(count)), dim3(kThreads), 0, 0, x, noise, (long long)count, (long long)start, (long long)step, thr, vals, bits);
+    if (int rc = use_device(device)) return rc;
+    hipLaunchKernelGGL(k_sample, dim3(grid_for(count, 4096)), dim3(kThreads), 0, 0, x, noise, (long long)count, (long long)start, (long long)step, thr, vals, bits);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());                              // the samples / bits go to callers on other streams
     return SSFM_OK;
@@ -816,12 +789,12 @@ extern "C" int ssfm_device_count_diff(int device, const unsigned char* a, const 
     if (!a || !b || !out || n < 0) return fail(SSFM_ERR_INVALID, "ssfm_device_count_diff: bad argument");
     *out = 0;
     if (n == 0) return SSFM_OK;
-    if (int rc = use(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     Scratch s(device);
     void* acc;
     if (int rc = s.get(sizeof(unsigned long long), &acc)) return rc;
     HIP_TRY(hipMemsetAsync(acc, 0, sizeof(unsigned long long), 0));
-    hipLaunchKernelGGL(k_count_diff, dim3(grid_for(n) < 1024 ? grid_for(n) : 1024), dim3(kThreads), 0, 0, a, b, (long long)n, (unsigned long long*)acc);
+    hipLaunchKernelGGL(k_count_diff, dim3(grid_for(n, 1024)), dim3(kThreads), 0, 0, a, b, (long long)n, (unsigned long long*)acc);
     HIP_TRY(hipGetLastError());
     unsigned long long h = 0;
     HIP_TRY(hipMemcpy(&h, acc, sizeof(h), hipMemcpyDeviceToHost));
@@ -851,7 +824,7 @@ extern "C" int ssfm_shortest_int(int device, const double* x, int64_t n, double 
     const long long lag = (long long)((double)n * percent / 100.0);
     if (!x || !out || n < 2 || n > kMaxN || !(percent > 0 && percent <= 100) || lag < 1 || lag >= n)
         return fail(SSFM_ERR_INVALID, "ssfm_shortest_int: n=%lld percent=%g (lag %lld: 1 ... n - 1; n <= 2^21)", (long long)n, percent, lag);
-    if (int rc = use(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     Scratch s(device);
     void *sorted, *tmp, *hist, *part, *st;
     if (int rc = s.get(sizeof(double) * n, &sorted)) return rc;
@@ -881,8 +854,8 @@ extern "C" int ssfm_shortest_int(int device, const double* x, int64_t n, double 
 
 extern "C" int ssfm_adc_quantize(int device, const double* x, int64_t n, double vmin, double vmax, int64_t levels, int as_volts, void* out) {
     if (!x || !out || n < 1 || levels < 1) return fail(SSFM_ERR_INVALID, "ssfm_adc_quantize: n=%lld levels=%lld", (long long)n, (long long)levels);
-    if (int rc = use(device)) return rc;
-    hipLaunchKernelGGL(k_quantize, dim3(grid_for(n)), dim3(kThreads), 0, 0, x, (long long)n, vmin, vmax, (long long)levels, as_volts, out);
+    if (int rc = use_device(device)) return rc;
+    hipLaunchKernelGGL(k_quantize, dim3(grid_for(n, 4096)), dim3(kThreads), 0, 0, x, (long long)n, vmin, vmax, (long long)levels, as_volts, out);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     return SSFM_OK;

@@ -24,6 +24,8 @@
 #include "ssfm_common.hpp"
 
 using ssfm::fail;
+using ssfm::Scratch;
+using ssfm::use_device;
 
 namespace {
 
@@ -354,30 +356,6 @@ __global__ __launch_bounds__(kThreads) void k_delay(cd* __restrict__ H, cd* __re
     Hnat[(i + n - n / 2) % n] = a;                           // ifftshift: Hnat[j] = H[(j + n/2) % n]
 }
 
-struct Scratch {
-    int device;
-    void* p[6] = {};
-    size_t b[6] = {};
-    int k = 0;
-    explicit Scratch(int d) : device(d) {}
-    int get(size_t bytes, void** out) {
-        if (int rc = ssfm_device_alloc(device, bytes, out)) return rc;
-        p[k] = *out;
-        b[k++] = bytes;
-        return SSFM_OK;
-    }
-    ~Scratch() {
-        if (k) (void)hipDeviceSynchronize();
-        for (int i = 0; i < k; ++i) (void)ssfm_device_free(device, p[i], b[i]);
-    }
-};
-
-int use(int device) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return fail(SSFM_ERR_NO_DEVICE, "fbg: device %d not available", device);
-    HIP_TRY(hipSetDevice(device));
-    return SSFM_OK;
-}
 
 }  // namespace
 
@@ -387,7 +365,7 @@ extern "C" int ssfm_fbg_solve(int device, int64_t n, const double* delta, const 
     if (!delta || !s || !kappa || !H || !info || n < 1 || n > kMaxN || apodization < SSFM_FBG_UNIFORM || apodization > SSFM_FBG_CUSTOM ||
         (apodization == SSFM_FBG_CUSTOM && !apo_fn) || !(rtol > 0) || !(atol >= 0))
         return fail(SSFM_ERR_INVALID, "ssfm_fbg_solve: n=%lld (1 ... 2^22) apodization=%d rtol=%g atol=%g", (long long)n, apodization, rtol, atol);
-    if (int rc = use(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     const int nb = (int)((n + kThreads - 1) / kThreads);
     Scratch sc(device);
     void *coef, *yb, *fb, *part, *stb, *pvb;
@@ -468,7 +446,7 @@ extern "C" int ssfm_fbg_solve(int device, int64_t n, const double* delta, const 
 
 extern "C" int ssfm_fbg_delay(int device, void* H, void* H_natural, int64_t n, double dt, double tau, int apply) {
     if (!H || !H_natural || H == H_natural || n < 1 || n > kMaxN) return fail(SSFM_ERR_INVALID, "ssfm_fbg_delay: n=%lld", (long long)n);
-    if (int rc = use(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     hipLaunchKernelGGL(k_delay, dim3((unsigned)((n + kThreads - 1) / kThreads)), dim3(kThreads), 0, 0, (cd*)H, (cd*)H_natural, (long long)n, dt, tau, apply);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());

@@ -13,6 +13,9 @@
 #include "ssfm_common.hpp"
 
 using ssfm::fail;
+using ssfm::grid_for;
+using ssfm::kMaxDevices;
+using ssfm::use_device;
 
 namespace {
 
@@ -39,7 +42,7 @@ __global__ __launch_bounds__(256) void k_square_law(const double2* __restrict__ 
     }
 }
 
-struct Scratch {
+struct Workspace {
     std::mutex mu;
     void* buf[4] = {nullptr, nullptr, nullptr, nullptr};
     size_t cap[4] = {0, 0, 0, 0};
@@ -51,8 +54,7 @@ struct Scratch {
         return e;
     }
 };
-constexpr int kMaxDevices = 64;
-Scratch g_scratch[kMaxDevices];
+Workspace g_ws[kMaxDevices];
 
 }  // namespace
 
@@ -61,11 +63,8 @@ int square_law_device(int device, const void* sig, const void* noise, int n_pol,
     if (!sig || !i_sig) return fail(SSFM_ERR_INVALID, "ssfm_square_law: NULL argument");
     if ((noise == nullptr) != (i_noise == nullptr)) return fail(SSFM_ERR_INVALID, "ssfm_square_law: noise and i_noise must be given together");
     if (n_pol < 1 || n_pol > 2 || n < 1) return fail(SSFM_ERR_INVALID, "ssfm_square_law: n_pol=%d n=%lld", n_pol, (long long)n);
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count)
-        return fail(SSFM_ERR_NO_DEVICE, "ssfm_square_law: device %d not available", device);
-    HIP_TRY(hipSetDevice(device));
-    const unsigned blocks = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    if (int rc = use_device(device)) return rc;
+    const unsigned blocks = grid_for(n, 4096);
     if (noise)
         hipLaunchKernelGGL(k_square_law<true>, dim3(blocks), dim3(256), 0, 0, (const double2*)sig, (const double2*)noise, n_pol, (long long)n, r, post, i_sig, i_noise);
     else
@@ -82,11 +81,8 @@ extern "C" int ssfm_square_law(int device, const void* sig, const void* noise, i
     if (!sig || !i_sig) return fail(SSFM_ERR_INVALID, "ssfm_square_law: NULL argument");
     if ((noise == nullptr) != (i_noise == nullptr)) return fail(SSFM_ERR_INVALID, "ssfm_square_law: noise and i_noise must be given together");
     if (n_pol < 1 || n_pol > 2 || n < 1) return fail(SSFM_ERR_INVALID, "ssfm_square_law: n_pol=%d n=%lld", n_pol, (long long)n);
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count || device >= kMaxDevices)
-        return fail(SSFM_ERR_NO_DEVICE, "ssfm_square_law: device %d not available", device);
-    HIP_TRY(hipSetDevice(device));
-    Scratch& w = g_scratch[device];
+    if (int rc = use_device(device)) return rc;
+    Workspace& w = g_ws[device];
     std::lock_guard<std::mutex> lock(w.mu);
     const size_t in_bytes = sizeof(double2) * (size_t)n * n_pol, out_bytes = sizeof(double) * (size_t)n;
     HIP_TRY(w.need(0, in_bytes));
@@ -97,7 +93,7 @@ extern "C" int ssfm_square_law(int device, const void* sig, const void* noise, i
         HIP_TRY(w.need(3, out_bytes));
         HIP_TRY(hipMemcpy(w.buf[1], noise, in_bytes, hipMemcpyHostToDevice));
     }
-    const unsigned blocks = (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096);
+    const unsigned blocks = grid_for(n, 4096);
     if (noise)
         hipLaunchKernelGGL(k_square_law<true>, dim3(blocks), dim3(256), 0, 0, (const double2*)w.buf[0], (const double2*)w.buf[1], n_pol, (long long)n, r, post,
                            (double*)w.buf[2], (double*)w.buf[3]);

@@ -22,6 +22,9 @@
 #include "ssfm_common.hpp"
 
 using ssfm::fail;
+using ssfm::grid_for;
+using ssfm::Scratch;
+using ssfm::use_device;
 using ssfm::philox4x32_10;
 
 namespace {
@@ -32,17 +35,7 @@ constexpr int kPerThread = 16;                     // items per thread of a coun
 constexpr int kTile = kThreads * kPerThread;       // items per tile
 constexpr int kMaxM = 1 << 16;
 
-unsigned grid_for(long long n) {
-    const long long b = (n + kThreads - 1) / kThreads;
-    return (unsigned)(b < 4096 ? (b > 0 ? b : 1) : 4096);
-}
 
-int use(int device) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return fail(SSFM_ERR_NO_DEVICE, "ppm: device %d not available", device);
-    HIP_TRY(hipSetDevice(device));
-    return SSFM_OK;
-}
 
 int log2_of(int M) {
     int k = 0;
@@ -275,25 +268,6 @@ __global__ __launch_bounds__(kThreads) void k_resolve(const void* __restrict__ x
     }
 }
 
-struct Scratch {
-    int device;
-    void* p[2] = {};
-    size_t b[2] = {};
-    int k = 0;
-    bool drained = false;
-    explicit Scratch(int d) : device(d) {}
-    int get(size_t bytes, void** out) {
-        if (int rc = ssfm_device_alloc(device, bytes, out)) return rc;
-        p[k] = *out;
-        b[k++] = bytes;
-        return SSFM_OK;
-    }
-    ~Scratch() {
-        if (k && !drained) (void)hipDeviceSynchronize();           // (error paths)
-        for (int i = 0; i < k; ++i) (void)ssfm_device_free(device, p[i], b[i]);
-    }
-};
-
 bool pow2_ok(int M) { return M >= 2 && M <= kMaxM && (M & (M - 1)) == 0; }
 
 // count + scan of a predicate over n items: offs (ntiles + 1 entries) in scratch
@@ -325,8 +299,8 @@ unsigned decide_grid(long long nsym, int M) {
 extern "C" int ssfm_ppm_encode(int device, const unsigned char* bits, int64_t nsym, int M, unsigned char* slots) {
     if (!bits || !slots || nsym < 0 || M < 2 || M > kMaxM) return fail(SSFM_ERR_INVALID, "ssfm_ppm_encode: nsym=%lld M=%d", (long long)nsym, M);
     if (nsym == 0) return SSFM_OK;
-    if (int rc = use(device)) return rc;
-    hipLaunchKernelGGL(k_encode, dim3(grid_for(nsym * M)), dim3(kThreads), 0, 0, bits, (long long)nsym, M, log2_of(M), slots);
+    if (int rc = use_device(device)) return rc;
+    hipLaunchKernelGGL(k_encode, dim3(grid_for(nsym * M, 4096)), dim3(kThreads), 0, 0, bits, (long long)nsym, M, log2_of(M), slots);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());                              // the slots go to callers on other streams (DAC)
     return SSFM_OK;
@@ -336,7 +310,7 @@ extern "C" int ssfm_ppm_decode(int device, const unsigned char* slots, int64_t n
     if (!slots || n < 0 || !pow2_ok(M) || (!bits && !n_bits) || cap < 0) return fail(SSFM_ERR_INVALID, "ssfm_ppm_decode: n=%lld M=%d", (long long)n, M);
     if (n_bits && !bits) *n_bits = 0;
     if (n == 0) return SSFM_OK;
-    if (int rc = use(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     Scratch s(device);
     long long ntiles, *offs;
     if (int rc = count_scan(s, NonZero{slots}, n, &ntiles, &offs)) return rc;
@@ -360,7 +334,7 @@ extern "C" int ssfm_ppm_decide(int device, const void* x, const double* noise, i
     if (!x || start < 0 || step < 1 || nsym < 0 || nsym > INT32_MAX || !pow2_ok(M) || (!bits && !slots) || (hard && !counts) || (is_u8 && noise))
         return fail(SSFM_ERR_INVALID, "ssfm_ppm_decide: nsym=%lld M=%d hard=%d", (long long)nsym, M, hard);
     if (nsym == 0) return SSFM_OK;
-    if (int rc = use(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     const unsigned blocks = decide_grid(nsym, M);
     const int k = log2_of(M);
     const long long a = start, b = step, c = nsym;
@@ -380,7 +354,7 @@ extern "C" int ssfm_ppm_faulty(int device, const int* counts, int64_t nsym, int*
     if (!counts || !idx || !cnt || !n_faulty || nsym < 0 || nsym > INT32_MAX) return fail(SSFM_ERR_INVALID, "ssfm_ppm_faulty: nsym=%lld", (long long)nsym);
     *n_faulty = 0;
     if (nsym == 0) return SSFM_OK;
-    if (int rc = use(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     Scratch s(device);
     long long ntiles, *offs;
     if (int rc = count_scan(s, Faulty{counts}, nsym, &ntiles, &offs)) return rc;
@@ -402,13 +376,13 @@ extern "C" int ssfm_ppm_resolve(int device, const void* x, const double* noise, 
         return fail(SSFM_ERR_INVALID, "ssfm_ppm_resolve: nsym=%lld M=%d n_list=%lld", (long long)nsym, M, (long long)n_list);
     const long long n = idx ? n_list : nsym;
     if (n == 0) return SSFM_OK;
-    if (int rc = use(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     const int k = log2_of(M);
     if (is_u8)
-        hipLaunchKernelGGL(k_resolve<true>, dim3(grid_for(n)), dim3(kThreads), 0, 0, x, noise, (long long)start, (long long)step, (long long)nsym, M, k, thr, counts, idx,
+        hipLaunchKernelGGL(k_resolve<true>, dim3(grid_for(n, 4096)), dim3(kThreads), 0, 0, x, noise, (long long)start, (long long)step, (long long)nsym, M, k, thr, counts, idx,
                            draws, (long long)n_list, (unsigned long long)seed, (unsigned long long)stream, bits, slots);
     else
-        hipLaunchKernelGGL(k_resolve<false>, dim3(grid_for(n)), dim3(kThreads), 0, 0, x, noise, (long long)start, (long long)step, (long long)nsym, M, k, thr, counts, idx,
+        hipLaunchKernelGGL(k_resolve<false>, dim3(grid_for(n, 4096)), dim3(kThreads), 0, 0, x, noise, (long long)start, (long long)step, (long long)nsym, M, k, thr, counts, idx,
                            draws, (long long)n_list, (unsigned long long)seed, (unsigned long long)stream, bits, slots);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());

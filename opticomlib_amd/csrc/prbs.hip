@@ -17,6 +17,7 @@
 #include "ssfm_common.hpp"
 
 using ssfm::fail;
+using ssfm::grid_for;
 namespace ssfm { SSFM_INTERNAL int plan_load_bits(ssfm_plan* plan, int64_t plan_n, const void* bits_dev, int64_t nbits, int up); }
 
 namespace {
@@ -107,11 +108,10 @@ __global__ __launch_bounds__(256) void k_load_qpsk(const uint8_t* __restrict__ b
 
 std::mutex g_jump_mu;
 struct JumpCache { int order; Jump* dev; };
-JumpCache g_jump[8][8] = {};          // [device][slot]
+JumpCache g_jump[ssfm::kMaxDevices][8] = {};          // [device][slot]
 
 int jump_for(int device, int order, int t1, int t2, const Jump** out) {
     std::lock_guard<std::mutex> lk(g_jump_mu);
-    if (device < 0 || device >= 8) return fail(SSFM_ERR_INVALID, "ssfm_prbs: device %d", device);
     for (auto& c : g_jump[device])
         if (c.dev && c.order == order) { *out = c.dev; return SSFM_OK; }
     Jump* h = new (std::nothrow) Jump();
@@ -129,7 +129,6 @@ int jump_for(int device, int order, int t1, int t2, const Jump** out) {
     return fail(SSFM_ERR_INVALID, "ssfm_prbs: jump-table cache full");
 }
 
-unsigned blocks_for(long long n) { return (unsigned)((n + 255) / 256 < 4096 ? (n + 255) / 256 : 4096); }
 
 }  // namespace
 
@@ -138,7 +137,7 @@ extern "C" int ssfm_prbs(int device, void* bits_dev, int64_t len, int order, uin
     if (!taps_of(order, &t1, &t2)) return fail(SSFM_ERR_INVALID, "ssfm_prbs: order %d is not one of 7, 9, 11, 15, 20, 23, 31", order);
     if (!bits_dev || len < 1 || len >= (1ll << kPowers)) return fail(SSFM_ERR_INVALID, "ssfm_prbs: %lld bits", (long long)len);
     if (seed == 0 || (order < 32 && (seed >> order) != 0)) return fail(SSFM_ERR_INVALID, "ssfm_prbs: seed %u is not a state of %d bits", seed, order);
-    HIP_TRY(hipSetDevice(device));
+    if (int rc = ssfm::use_device(device)) return rc;
     const Jump* jump = nullptr;
     if (int rc = jump_for(device, order, t1, t2, &jump)) return rc;
     uint32_t* fs_dev = nullptr;
@@ -159,7 +158,7 @@ int ssfm::plan_load_bits(ssfm_plan* plan, int64_t plan_n, const void* bits_dev, 
     double2* F = static_cast<double2*>(ssfm::plan_field(plan));
     if (!F || !bits_dev || nbits < 1 || up < 1 || nbits * up > plan_n)
         return fail(SSFM_ERR_INVALID, "ssfm_load_symbols: %lld bits x %d samples for a plan of %lld", (long long)nbits, up, (long long)plan_n);
-    hipLaunchKernelGGL(k_load_bits, dim3(blocks_for(plan_n)), dim3(256), 0, static_cast<hipStream_t>(ssfm::plan_stream(plan)), (const uint8_t*)bits_dev,
+    hipLaunchKernelGGL(k_load_bits, dim3(grid_for(plan_n, 4096)), dim3(256), 0, static_cast<hipStream_t>(ssfm::plan_stream(plan)), (const uint8_t*)bits_dev,
                        (long long)nbits, up, F, (long long)plan_n);
     HIP_TRY(hipGetLastError());
     return SSFM_OK;
@@ -170,7 +169,7 @@ extern "C" int ssfm_load_qpsk(ssfm_plan* plan, int64_t plan_n, int rows, const v
     double2* F = static_cast<double2*>(ssfm::plan_field(plan));
     if (!F || !bits_dev || nsym < 1 || sps < 1 || rows < 1 || nsym * sps > plan_n)
         return fail(SSFM_ERR_INVALID, "ssfm_load_qpsk: %lld symbols x %d samples for a plan of %lld", (long long)nsym, sps, (long long)plan_n);
-    hipLaunchKernelGGL(k_load_qpsk, dim3(blocks_for(plan_n * rows)), dim3(256), 0, static_cast<hipStream_t>(ssfm::plan_stream(plan)), (const uint8_t*)bits_dev,
+    hipLaunchKernelGGL(k_load_qpsk, dim3(grid_for(plan_n * rows, 4096)), dim3(256), 0, static_cast<hipStream_t>(ssfm::plan_stream(plan)), (const uint8_t*)bits_dev,
                        (long long)nsym, rows, sps, F, (long long)plan_n);
     HIP_TRY(hipGetLastError());
     return SSFM_OK;

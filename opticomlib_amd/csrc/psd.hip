@@ -23,6 +23,9 @@
 #include "wgfft.hpp"
 
 using ssfm::fail;
+using ssfm::grid_for;
+using ssfm::Scratch;
+using ssfm::use_device;
 using ssfm::cf32;
 using ssfm::cf64;
 
@@ -304,44 +307,12 @@ __global__ __launch_bounds__(kThreads) void k_welch_accumulate(const cf64* __res
     }
 }
 
-unsigned grid_for(long long n) {
-    const long long b = (n + kThreads - 1) / kThreads;
-    return (unsigned)(b < 2048 ? (b > 0 ? b : 1) : 2048);
-}
 
-int use(int device) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return fail(SSFM_ERR_NO_DEVICE, "welch: device %d not available", device);
-    HIP_TRY(hipSetDevice(device));
-    return SSFM_OK;
-}
-
-// scratch from the library's pool, handed back on every exit
-struct Scratch {
-    int device;
-    void* p = nullptr;
-    size_t b = 0;
-    bool drained = false;                  // set after the blocking copy of the result: nothing of ours is in flight
-    explicit Scratch(int d) : device(d) {}
-    int get(size_t bytes, void** out) {
-        if (int rc = ssfm_device_alloc(device, bytes, out)) return rc;
-        p = *out;
-        b = bytes;
-        return SSFM_OK;
-    }
-    ~Scratch() {
-        if (p) {
-            if (!drained) (void)hipDeviceSynchronize();        // (error paths)
-            (void)ssfm_device_free(device, p, b);
-        }
-    }
-};
 
 // route 1's tables, per device and line length: generated on the device once, kept for the life of the process (at most 10 x 200 KiB per device)
-constexpr int kMaxDevices = 64;
 struct Tables { cf64* tw = nullptr; double* win = nullptr; };
 std::mutex g_tab_mu;
-Tables g_tab[kMaxDevices][kMaxLog2 + 1];
+Tables g_tab[ssfm::kMaxDevices][kMaxLog2 + 1];
 
 template <int L> int make_tables(Tables& t) {
     constexpr int E = welch_points(L);
@@ -353,7 +324,6 @@ template <int L> int make_tables(Tables& t) {
     return SSFM_OK;
 }
 int tables(int device, int log2L, Tables* out) {
-    if (device >= kMaxDevices) return fail(SSFM_ERR_INVALID, "welch: device %d beyond the table cache", device);
     std::lock_guard<std::mutex> lock(g_tab_mu);
     Tables& t = g_tab[device][log2L];
     if (!t.tw) {
@@ -440,7 +410,7 @@ extern "C" int ssfm_welch(int device, const void* x, int dtype, int64_t rows, in
     while ((int64_t(1) << log2L) < nperseg) ++log2L;
     if (!(nperseg <= kDirectMax || (pow2 && log2L >= kMinLog2 && log2L <= kMaxLog2)))
         return fail(SSFM_ERR_INVALID, "ssfm_welch: nperseg=%lld takes the chirp-z route (ssfm_welch_frames)", (long long)nperseg);
-    if (int rc = use(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     const long long P = nperseg, noverlap = P / 2, step = P - noverlap, nseg = (n - noverlap) / step;
     const long long spw = per_group(rows, nseg, nperseg <= kDirectMax ? kThreads : 2 * welch_lines((int)nperseg));
     const long long G = (nseg + spw - 1) / spw;
@@ -475,8 +445,8 @@ extern "C" int ssfm_welch_frames(int device, const void* x, int dtype, int64_t r
         first + count > rows * nseg)
         return fail(SSFM_ERR_INVALID, "ssfm_welch_frames: rows=%lld n=%lld nperseg=%lld first=%lld count=%lld chunk=%lld", (long long)rows, (long long)n,
                     (long long)nperseg, (long long)first, (long long)count, (long long)chunk);
-    if (int rc = use(device)) return rc;
-    const dim3 grid(grid_for(chunk * P));
+    if (int rc = use_device(device)) return rc;
+    const dim3 grid(grid_for(chunk * P, 2048));
     if (dtype == SSFM_C64) hipLaunchKernelGGL(k_welch_frames<cf32>, grid, dim3(kThreads), 0, 0, (const cf32*)x, (long long)ld, P, step, nseg, (long long)first, (long long)count, (long long)chunk, (cf64*)frames);
     else if (dtype == SSFM_C128) hipLaunchKernelGGL(k_welch_frames<cf64>, grid, dim3(kThreads), 0, 0, (const cf64*)x, (long long)ld, P, step, nseg, (long long)first, (long long)count, (long long)chunk, (cf64*)frames);
     else hipLaunchKernelGGL(k_welch_frames<double>, grid, dim3(kThreads), 0, 0, (const double*)x, (long long)ld, P, step, nseg, (long long)first, (long long)count, (long long)chunk, (cf64*)frames);
@@ -489,7 +459,7 @@ extern "C" int ssfm_welch_accumulate(int device, const void* frames, int64_t npe
     if (!frames || !acc || nperseg < 1 || rows < 1 || nseg < 1 || first < 0 || count < 1 || first + count > rows * nseg)
         return fail(SSFM_ERR_INVALID, "ssfm_welch_accumulate: nperseg=%lld rows=%lld nseg=%lld first=%lld count=%lld", (long long)nperseg, (long long)rows,
                     (long long)nseg, (long long)first, (long long)count);
-    if (int rc = use(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     const long long row0 = first / nseg, row1 = (first + count - 1) / nseg;
     hipLaunchKernelGGL(k_welch_accumulate, dim3((unsigned)((nperseg + kBins - 1) / kBins), (unsigned)(row1 - row0 + 1)), dim3(kThreads), 0, 0,
                        (const cf64*)frames, (long long)nperseg, (long long)nseg, (long long)first, (long long)count, row0, (double*)acc);
@@ -500,7 +470,7 @@ extern "C" int ssfm_welch_accumulate(int device, const void* frames, int64_t npe
 
 extern "C" int ssfm_welch_finish(int device, const void* acc, int64_t rows, int64_t nperseg, double factor, int out_f32, void* out) {
     if (!acc || !out || rows < 1 || rows > 65535 || nperseg < 1) return fail(SSFM_ERR_INVALID, "ssfm_welch_finish: rows=%lld nperseg=%lld", (long long)rows, (long long)nperseg);
-    if (int rc = use(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     Scratch s(device);
     void* buf;
     if (int rc = s.get((size_t)(rows * nperseg) * (out_f32 ? 4 : 8), &buf)) return rc;

@@ -47,6 +47,7 @@
 #include "ssfm_common.hpp"
 
 using ssfm::fail;
+using ssfm::kMaxDevices;
 
 namespace {
 
@@ -142,7 +143,6 @@ struct Workspace {
         return e;
     }
 };
-constexpr int kMaxDevices = 64;
 Workspace g_ws[kMaxDevices];
 
 template <int K> void matmul(const double* A, const double* B, double* C) {
@@ -268,10 +268,7 @@ int sosfiltfilt_impl(int device, const double* sos, const double* zi, int n_sect
     if (n <= edge) return fail(SSFM_ERR_INVALID, "The length of the input vector x must be greater than padlen, which is %d.", edge);
     if (is_complex && on_device && ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(y)) & 15))
         return fail(SSFM_ERR_INVALID, "ssfm_sosfiltfilt_device: complex buffers must be 16-byte aligned");
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count || device >= kMaxDevices)
-        return fail(SSFM_ERR_NO_DEVICE, "ssfm_sosfiltfilt: device %d not available", device);
-    HIP_TRY(hipSetDevice(device));
+    if (int rc = ssfm::use_device(device)) return rc;
     Workspace& w = g_ws[device];
     std::lock_guard<std::mutex> lock(w.mu);
     const double* xd = static_cast<const double*>(x);

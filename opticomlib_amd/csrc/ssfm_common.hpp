@@ -1,4 +1,4 @@
-// ssfm_common.hpp -- error reporting shared by the translation units of _ssfm_amd.so
+// ssfm_common.hpp -- error reporting, the device check, grid sizes and per-call scratch shared by the translation units of _ssfm_amd.so
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -83,3 +83,50 @@ __device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, uns
             return ssfm::fail(SSFM_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_),  \
                               __FILE__, __LINE__);                                                  \
     } while (0)
+
+namespace ssfm {
+
+constexpr int kMaxDevices = 64;          // the per-device pools, caches and workspaces hold this many devices
+
+// The device check of every `int device` entry point: the device exists and fits the per-device tables; it is then the calling thread's device.
+inline int use_device(int device) {
+    int count = 0;
+    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count || device >= kMaxDevices)
+        return fail(SSFM_ERR_NO_DEVICE, "device %d not available", device);
+    HIP_TRY(hipSetDevice(device));
+    return SSFM_OK;
+}
+
+// Workgroups of 256 threads for a grid-stride loop over n items: one per 256 items, at least one, at most `cap`.  The cap is the call site's own:
+// where per-block partials are folded (eye, FBG, PSD) a different grid changes the order of the sums.
+inline unsigned grid_for(long long n, long long cap) {
+    const long long b = (n + 255) / 256;
+    return (unsigned)(b < cap ? (b > 0 ? b : 1) : cap);
+}
+
+// Per-call scratch from the library's pool (ssfm_device_alloc), handed back on every exit.  The device is synchronised first unless the caller has
+// marked the scratch `drained` (nothing of the call is in flight any more, e.g. after a blocking copy on the null stream).
+struct Scratch {
+    static constexpr int kSlots = 6;
+    int device;
+    void* p[kSlots] = {};
+    size_t b[kSlots] = {};
+    int k = 0;
+    bool drained = false;
+    explicit Scratch(int d) : device(d) {}
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    int get(size_t bytes, void** out) {
+        if (k == kSlots) return fail(SSFM_ERR_INVALID, "scratch: more than %d buffers", kSlots);
+        if (int rc = ssfm_device_alloc(device, bytes, out)) return rc;
+        p[k] = *out;
+        b[k++] = bytes;
+        return SSFM_OK;
+    }
+    ~Scratch() {
+        if (k && !drained) (void)hipDeviceSynchronize();
+        for (int i = 0; i < k; ++i) (void)ssfm_device_free(device, p[i], b[i]);
+    }
+};
+
+}  // namespace ssfm

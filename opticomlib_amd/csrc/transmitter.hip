@@ -9,16 +9,11 @@
 #include "ssfm_common.hpp"
 
 using ssfm::fail;
+using ssfm::grid_for;
+using ssfm::use_device;
 
 namespace {
 
-int use_dev(int device) {
-    int count = 0;
-    if (hipGetDeviceCount(&count) != hipSuccess || device < 0 || device >= count) return fail(SSFM_ERR_NO_DEVICE, "device %d not available", device);
-    HIP_TRY(hipSetDevice(device));
-    return SSFM_OK;
-}
-unsigned blocks_of(long long n) { return (unsigned)((n + 255) / 256 < 8192 ? (n + 255) / 256 : 8192); }
 
 // drive: float64 (drive_complex = 0) or complex128 (1: a chirped / Gaussian DAC output); noise of the drive likewise
 __global__ __launch_bounds__(256) void k_mzm(double2* __restrict__ out_s, double2* __restrict__ out_n, const double2* __restrict__ in_s, const double2* __restrict__ in_n,
@@ -107,8 +102,8 @@ extern "C" int ssfm_mzm(int device, void* out_sig, void* out_noise, const void* 
                         const void* drive_noise, int drive_complex, double k, double bias, double sqrt_loss, double half_eta, int dead_pol) {
     if (!out_sig || !in_sig || !drive || n < 1 || n_pol < 1 || n_pol > 2) return fail(SSFM_ERR_INVALID, "ssfm_mzm: bad argument");
     if ((in_noise == nullptr) != (out_noise == nullptr)) return fail(SSFM_ERR_INVALID, "ssfm_mzm: in_noise and out_noise must be given together");
-    if (int rc = use_dev(device)) return rc;
-    hipLaunchKernelGGL(k_mzm, dim3(blocks_of(n)), dim3(256), 0, 0, (double2*)out_sig, (double2*)out_noise, (const double2*)in_sig, (const double2*)in_noise, n_pol,
+    if (int rc = use_device(device)) return rc;
+    hipLaunchKernelGGL(k_mzm, dim3(grid_for(n, 8192)), dim3(256), 0, 0, (double2*)out_sig, (double2*)out_noise, (const double2*)in_sig, (const double2*)in_noise, n_pol,
                        (long long)n, (const double*)drive, (const double*)drive_noise, drive_complex, k, bias, sqrt_loss, half_eta, dead_pol);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
@@ -117,8 +112,8 @@ extern "C" int ssfm_mzm(int device, void* out_sig, void* out_noise, const void* 
 
 extern "C" int ssfm_device_axpb(int device, void* dst, const void* src, double alpha, double beta, int64_t n, int is_complex) {
     if (!dst || !src || n < 1) return fail(SSFM_ERR_INVALID, "ssfm_device_axpb: bad argument");
-    if (int rc = use_dev(device)) return rc;
-    hipLaunchKernelGGL(k_axpb, dim3(blocks_of(n)), dim3(256), 0, 0, (double*)dst, (const double*)src, alpha, beta, (long long)n, is_complex);
+    if (int rc = use_device(device)) return rc;
+    hipLaunchKernelGGL(k_axpb, dim3(grid_for(n, 8192)), dim3(256), 0, 0, (double*)dst, (const double*)src, alpha, beta, (long long)n, is_complex);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     return SSFM_OK;
@@ -126,8 +121,8 @@ extern "C" int ssfm_device_axpb(int device, void* dst, const void* src, double a
 
 extern "C" int ssfm_laser(int device, void* out, int64_t n, double amp, const double* phase, const double* rin, int has_df, double w, double step, double stop) {
     if (!out || n < 1) return fail(SSFM_ERR_INVALID, "ssfm_laser: bad argument");
-    if (int rc = use_dev(device)) return rc;
-    hipLaunchKernelGGL(k_laser, dim3(blocks_of(n)), dim3(256), 0, 0, (double*)out, (long long)n, amp, phase, rin, has_df, w, step, stop);
+    if (int rc = use_device(device)) return rc;
+    hipLaunchKernelGGL(k_laser, dim3(grid_for(n, 8192)), dim3(256), 0, 0, (double*)out, (long long)n, amp, phase, rin, has_df, w, step, stop);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     return SSFM_OK;
@@ -184,7 +179,7 @@ int reduce_sum(int device, const double* a, long long n, int stride, int offset,
 namespace {
 int device_mean2(int device, const void* src, int64_t n, int is_complex, double* out) {
     if (!src || !out || n < 1) return fail(SSFM_ERR_INVALID, "ssfm_device_reduce (mean2): bad argument");
-    if (int rc = use_dev(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     const int stride = is_complex ? 2 : 1;
     for (int k = 0; k < stride; ++k) {
         double s = 0.0;
@@ -196,7 +191,7 @@ int device_mean2(int device, const void* src, int64_t n, int is_complex, double*
 
 int device_power(int device, const void* src, int rows, int64_t n, int is_complex, double* out) {
     if (!src || !out || n < 1 || rows < 1) return fail(SSFM_ERR_INVALID, "ssfm_device_reduce (power): bad argument");
-    if (int rc = use_dev(device)) return rc;
+    if (int rc = use_device(device)) return rc;
     const int stride = is_complex ? 2 : 1;
     for (int r = 0; r < rows; ++r) {
         double s = 0.0;
@@ -224,8 +219,8 @@ extern "C" int ssfm_device_reduce(int device, int kind, const void* a, const voi
 }
 extern "C" int ssfm_device_shift(int device, void* dst, const void* src, int64_t n, int is_complex, double re, double im) {
     if (!dst || !src || n < 1) return fail(SSFM_ERR_INVALID, "ssfm_device_shift: bad argument");
-    if (int rc = use_dev(device)) return rc;
-    hipLaunchKernelGGL(k_shift, dim3(blocks_of(n)), dim3(256), 0, 0, (double*)dst, (const double*)src, (long long)n, is_complex, re, im);
+    if (int rc = use_device(device)) return rc;
+    hipLaunchKernelGGL(k_shift, dim3(grid_for(n, 8192)), dim3(256), 0, 0, (double*)dst, (const double*)src, (long long)n, is_complex, re, im);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());
     return SSFM_OK;
@@ -272,8 +267,8 @@ extern "C" int ssfm_pm(int device, void* out_sig, void* out_noise, const void* i
                        const void* drive_noise, int drive_complex, double Vpi) {
     if (!out_sig || !in_sig || !drive || n < 1 || n_pol < 1 || n_pol > 2) return fail(SSFM_ERR_INVALID, "ssfm_pm: bad argument");
     if ((in_noise == nullptr) != (out_noise == nullptr)) return fail(SSFM_ERR_INVALID, "ssfm_pm: in_noise and out_noise must be given together");
-    if (int rc = use_dev(device)) return rc;
-    hipLaunchKernelGGL(k_pm, dim3(blocks_of(n)), dim3(256), 0, 0, (double2*)out_sig, (double2*)out_noise, (const double2*)in_sig, (const double2*)in_noise, n_pol,
+    if (int rc = use_device(device)) return rc;
+    hipLaunchKernelGGL(k_pm, dim3(grid_for(n, 8192)), dim3(256), 0, 0, (double2*)out_sig, (double2*)out_noise, (const double2*)in_sig, (const double2*)in_noise, n_pol,
                        (long long)n, (const double*)drive, (const double*)drive_noise, drive_complex, Vpi);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipDeviceSynchronize());

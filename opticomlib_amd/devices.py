@@ -133,6 +133,29 @@ def _dev_array(x, dtype, dev: int) -> "_lib.DeviceArray":
     return _lib.DeviceArray.from_host(np.asarray(x), dtype, dev)
 
 
+def _stack_rows(arrays, dtype, dev: int, shape=None) -> "_lib.DeviceArray":
+    """``arrays`` (host arrays or DeviceArrays of one shape, ``(rows, n)`` or ``(n,)``) one after the other in ONE new device buffer of
+    ``dtype`` on GPU ``dev``: ``(k rows, n)`` for k arrays, or ``shape`` when given (blocks beyond the arrays are left unset)."""
+    if shape is None:
+        shape = (len(arrays) * int(np.prod(arrays[0].shape[:-1], dtype=np.int64)), arrays[0].shape[-1])
+    buf = _lib.DeviceArray(shape, dtype, dev)
+    for k, a in enumerate(arrays):
+        d = _dev_array(a, dtype, dev)
+        if (k + 1) * d.nbytes > buf.nbytes:
+            raise ValueError(f"{len(arrays)} arrays of {d.shape} do not fit a buffer of {buf.shape}")
+        _lib.api.ssfm_device_copy(dev, buf.ptr + k * d.nbytes, d, d.nbytes, _lib.COPY_D2D)
+    return buf
+
+
+def _row_block(buf: "_lib.DeviceArray", k: int, shape) -> "_lib.DeviceArray":
+    """Block ``k`` of a :func:`_stack_rows` buffer of arrays of ``shape``, as a new DeviceArray of that shape."""
+    out = _lib.DeviceArray(shape, buf.dtype, buf.device)
+    if (k + 1) * out.nbytes > buf.nbytes:
+        raise ValueError(f"block {k} of {shape} lies beyond a buffer of {buf.shape}")
+    _lib.api.ssfm_device_copy(buf.device, out, buf.ptr + k * out.nbytes, out.nbytes, _lib.COPY_D2D)
+    return out
+
+
 def _wrap_out(cls, sig, noi, **kw):
     """Signal object around device results; materialised at once when KEEP_ON_DEVICE is off."""
     out = cls.from_device(sig, noi, **kw)
@@ -320,6 +343,17 @@ class _ChirpZ:
         return A
 
 
+def _chirpz_transfer(raws, H, exponent: bool, dev: int):
+    """``ifft(fft(x) H)`` (or ``* exp(H)`` with ``exponent``) of every row of the arrays ``raws`` (signal, then noise: one shape) on the
+    chirp-z engine (any length): the rows stacked in one buffer, transformed in place, split back into new device arrays of that shape."""
+    shape = tuple(raws[0].shape)
+    buf = _stack_rows(raws, np.complex128, dev)
+    with _ChirpZ(shape[-1], buf.shape[0], dev) as eng:
+        eng.transfer(buf, H, exponent=exponent)
+        eng.plan.synchronize()
+    return [_row_block(buf, k, shape) for k in range(len(raws))]
+
+
 def _fourier(obj, domain, shift=False):
     """``signal('w')`` / ``signal('t')`` of the reference's signal classes (``typing.py:1421-1462``): fft or ifft of
     signal and noise along the last axis -- on the device, for any length from 2 to 2^21 (complex128 chirp-z
@@ -336,27 +370,25 @@ def _fourier(obj, domain, shift=False):
     if n < 2 or 2 * n - 1 > (1 << hi):
         raise ValueError(f"the device transform takes 2 ... 2^{hi - 1} samples per row, got {n} (there is no CPU fallback)")
     single = all(np.dtype(a.dtype) in (np.dtype(np.complex64), np.dtype(np.float32)) for a in raws)   # NumPy >= 2 keeps single precision
-    buf = _lib.DeviceArray((rows * len(raws), n), np.complex128, dev)
-    row_bytes = rows * n * 16
-    cp = lambda dst, src, nbytes: _lib._check(_lib.load().ssfm_device_copy(dev, _lib._VP(dst), _lib._VP(src), nbytes, 2), "ssfm_device_copy")
-    for k, a in enumerate(raws):
-        cp(buf.ptr + k * row_bytes, _dev_array(a, np.complex128, dev).ptr, row_bytes)
-    with _ChirpZ(n, rows * len(raws), dev) as eng:
+    buf = _stack_rows(raws, np.complex128, dev)
+    with _ChirpZ(n, buf.shape[0], dev) as eng:
         res = eng.fourier(buf, inverse)
+    cp = lambda dst, src, nbytes: _lib.api.ssfm_device_copy(dev, dst, src, nbytes, _lib.COPY_D2D)
     outs = []
     s_ = n // 2
     for k in range(len(raws)):
-        o = _lib.DeviceArray(shape, np.complex128, dev)
-        for r in range(rows):
-            src, dst = res.ptr + k * row_bytes + r * n * 16, o.ptr + r * n * 16
-            if not shift:
-                cp(dst, src, n * 16)
-            elif not inverse:                                   # fftshift: out[(i + n//2) % n] = in[i]
-                cp(dst + s_ * 16, src, (n - s_) * 16)
-                cp(dst, src + (n - s_) * 16, s_ * 16)
-            else:                                               # ifftshift: out[i] = in[(i + n//2) % n]
-                cp(dst, src + s_ * 16, (n - s_) * 16)
-                cp(dst + (n - s_) * 16, src, s_ * 16)
+        if not shift:
+            o = _row_block(res, k, shape)
+        else:
+            o = _lib.DeviceArray(shape, np.complex128, dev)
+            for r in range(rows):
+                src, dst = res.ptr + (k * rows + r) * n * 16, o.ptr + r * n * 16
+                if not inverse:                                 # fftshift: out[(i + n//2) % n] = in[i]
+                    cp(dst + s_ * 16, src, (n - s_) * 16)
+                    cp(dst, src + (n - s_) * 16, s_ * 16)
+                else:                                           # ifftshift: out[i] = in[(i + n//2) % n]
+                    cp(dst, src + s_ * 16, (n - s_) * 16)
+                    cp(dst + (n - s_) * 16, src, s_ * 16)
         outs.append(o.astype(np.complex64) if single else o)
     kw = {"n_pol": obj.n_pol} if isinstance(obj, optical_signal) else {}
     return _wrap_out(type(obj), outs[0], outs[1] if len(outs) > 1 else NULL, **kw)
@@ -865,19 +897,7 @@ def DM(input: optical_signal, D: float, retH: bool = False, *, device=None):
         w = np.fft.fftfreq(n, float(grid.dt)) * 2 * np.pi           # typing.py:1641
         phase = 1j * w ** 2 * D / 2                                 # the exponential itself is taken on the device
         Hd = _lib.DeviceArray.from_host(phase, np.complex128, dev)
-        nrow = rows * (2 if has_noise else 1)
-        buf = _lib.DeviceArray((nrow, n), np.complex128, dev)
-        for k, a in enumerate([raw_s, raw_n] if has_noise else [raw_s]):
-            d = _dev_array(a, np.complex128, dev)
-            _lib._check(_lib.load().ssfm_device_copy(dev, _lib._VP(buf.ptr + k * rows * n * 16), _lib._VP(d.ptr), rows * n * 16, 2), "ssfm_device_copy")
-        with _ChirpZ(n, nrow, dev) as eng:
-            eng.transfer(buf, Hd, exponent=True)
-            eng.plan.synchronize()
-        outs = []
-        for k in range(2 if has_noise else 1):
-            o = _lib.DeviceArray(shape, np.complex128, dev)
-            _lib._check(_lib.load().ssfm_device_copy(dev, _lib._VP(o.ptr), _lib._VP(buf.ptr + k * rows * n * 16), rows * n * 16, 2), "ssfm_device_copy")
-            outs.append(o)
+        outs = _chirpz_transfer([raw_s, raw_n] if has_noise else [raw_s], Hd, True, dev)
         output = _wrap_out(optical_signal, outs[0], outs[1] if has_noise else NULL, n_pol=input.n_pol)
         output.execution_time = time.time() - t0
         if retH:
@@ -1145,7 +1165,7 @@ def EDFA(input: optical_signal, G: float, NF: float, BW: float = None, *, device
             return _lib.scale_add_device(d, g)
         out2 = _lib.zeros_device((2, n), np.complex128, dev)                      # empty y polarisation
         x = _lib.scale_add_device(d, g)
-        _lib._check(_lib.load().ssfm_device_copy(dev, _lib._VP(out2.ptr), _lib._VP(x.ptr), n * 16, 2), "ssfm_device_copy")
+        _lib.api.ssfm_device_copy(dev, out2, x, n * 16, _lib.COPY_D2D)
         return out2
     sig = two_rows(raw_s)
     P_ase = _idb(NF) * h * grid.f0 * (_idb(G) - 1) * grid.fs
@@ -1460,8 +1480,7 @@ def _real_sum_device(input, n: int, shift: int, dev: int) -> "_lib.DeviceArray":
     cplx = any(np.iscomplexobj(np.empty(0, a.dtype)) for a in raws)
     arrs = [_dev_array(a, np.complex128 if cplx else np.float64, dev) for a in raws]
     out = _lib.DeviceArray((n,), np.float64, dev)
-    _lib._check(_lib.load().ssfm_eye_prepare(dev, _lib._VP(arrs[0].ptr), _lib._VP(arrs[1].ptr) if len(arrs) > 1 else None, int(cplx), n, int(shift),
-                                             _lib._VP(out.ptr)), "ssfm_eye_prepare")
+    _lib.api.ssfm_eye_prepare(dev, arrs[0], arrs[1] if len(arrs) > 1 else None, int(cplx), n, int(shift), out)
     return out
 
 
@@ -1472,17 +1491,16 @@ def _resample_device(x: "_lib.DeviceArray", m: int, dev: int) -> "_lib.DeviceArr
     _, hi = _lib.supported_log2n(_lib.C128, direct=True)
     if 2 * max(n, m) - 1 > (1 << hi):
         raise ValueError(f"the device transform takes 2 ... 2^{hi - 1} samples, the resampling needs {n} -> {m} (there is no CPU fallback)")
-    lib = _lib.load()
     X = _lib.DeviceArray((1, n), np.complex128, dev)
-    _lib._check(lib.ssfm_eye_resample_stage(dev, 0, _lib._VP(x.ptr), n, _lib._VP(X.ptr), n), "ssfm_eye_resample_stage")
+    _lib.api.ssfm_eye_resample_stage(dev, 0, x, n, X, n)
     with _ChirpZ(n, 1, dev) as eng:
         eng.fourier(X, False)
     Y = _lib.DeviceArray((1, m), np.complex128, dev)
-    _lib._check(lib.ssfm_eye_resample_stage(dev, 1, _lib._VP(X.ptr), n, _lib._VP(Y.ptr), m), "ssfm_eye_resample_stage")
+    _lib.api.ssfm_eye_resample_stage(dev, 1, X, n, Y, m)
     with _ChirpZ(m, 1, dev) as eng:
         eng.fourier(Y, True)
     y = _lib.DeviceArray((m,), np.float64, dev)
-    _lib._check(lib.ssfm_eye_resample_stage(dev, 2, _lib._VP(Y.ptr), n, _lib._VP(y.ptr), m), "ssfm_eye_resample_stage")
+    _lib.api.ssfm_eye_resample_stage(dev, 2, Y, n, y, m)
     return y
 
 
@@ -1523,15 +1541,13 @@ def GET_EYE(input, nslots: int = 4096, sps_resamp: int = None, *, device=None, _
     if max(n0, n) > _EYE_MAX_N:
         raise ValueError(f"GET_EYE on the device takes up to 2^21 samples, got {max(n0, n)} (there is no CPU fallback)")
     dev = default_device() if device is None else int(device)
-    lib = _lib.load()
     x0 = _real_sum_device(input, n0, -sps // 2 + 1, dev)
     y = _resample_device(x0, n, dev) if sps_resamp else x0
     waits = 1 + (5 if sps_resamp else 0)                    # ssfm_eye_prepare; the three stages and the two transforms
     tg = np.linspace(-1, 1 - 1 / s, 2 * s)
     st = np.zeros(64)
     trips = _lib._I64(0)
-    _lib._check(lib.ssfm_eye_estimate(dev, _lib._VP(y.ptr), n, _lib._ptr(tg), 2 * s, _lib._VP(x0.ptr), n0, _lib._ptr(st), st.size, C.byref(trips)),
-                "ssfm_eye_estimate")
+    _lib.api.ssfm_eye_estimate(dev, y, n, _lib._ptr(tg), 2 * s, x0, n0, _lib._ptr(st), st.size, C.byref(trips))
     S = lambda name: float(st[_S[name]])
     if S("NONFINITE"):
         raise ValueError("GET_EYE: the signal holds NaN or infinity (the two-means take finite samples only)")
@@ -1560,7 +1576,7 @@ def GET_EYE(input, nslots: int = 4096, sps_resamp: int = None, *, device=None, _
     ks = np.nonzero((t_span0 < tg) & (tg < t_span1))[0]
     k_lo, k_hi = (int(ks[0]), int(ks[-1]) + 1) if ks.size else (0, 0)
     lv = np.zeros(64)
-    _lib._check(lib.ssfm_eye_levels(dev, _lib._VP(y.ptr), n, 2 * s, k_lo, k_hi, S("YC"), 500, _lib._ptr(lv), lv.size), "ssfm_eye_levels")
+    _lib.api.ssfm_eye_levels(dev, y, n, 2 * s, k_lo, k_hi, S("YC"), 500, _lib._ptr(lv), lv.size)
     L = lambda name: float(lv[_S[name]])
     mu0, mu1, s0, s1 = L("MU0"), L("MU1"), L("SD0"), L("SD1")
     d.update(mu0=mu0, mu1=mu1, s0=s0, s1=s1)
@@ -1585,9 +1601,8 @@ def _sample_device(a, instant: int, step: int, dev: int, thr=None, noise=None):
     nz = None if noise is None else _dev_array(noise, np.float64, dev)
     start, count = _slice_count(x.size, instant, step)
     out = _lib.DeviceArray((max(count, 1),), np.uint8 if thr is not None else np.float64, dev)
-    vals, bits = (None, _lib._VP(out.ptr)) if thr is not None else (_lib._VP(out.ptr), None)
-    _lib._check(_lib.load().ssfm_device_sample(dev, _lib._VP(x.ptr), None if nz is None else _lib._VP(nz.ptr), start, int(step), count,
-                                               float(thr or 0.0), vals, bits), "ssfm_device_sample")
+    vals, bits = (None, out) if thr is not None else (out, None)
+    _lib.api.ssfm_device_sample(dev, x, nz, start, int(step), count, float(thr or 0.0), vals, bits)
     if count == 0:
         return np.empty(0, np.uint8 if thr is not None else np.float64)
     return out
@@ -1654,8 +1669,7 @@ def PM(op_input: optical_signal, el_input, Vpi: float = 5.0, *, device=None) -> 
     noi = None if raw_n is NULL else _dev_array(raw_n, np.complex128, dev)
     out_s = _lib.DeviceArray(shape, np.complex128, dev)
     out_n = None if noi is None else _lib.DeviceArray(shape, np.complex128, dev)
-    p = lambda x: None if x is None else _lib._VP(x.ptr)
-    _lib._check(_lib.load().ssfm_pm(dev, p(out_s), p(out_n), p(sig), p(noi), n_pol, n, p(v), p(vn), int(cplx), float(Vpi)), "ssfm_pm")
+    _lib.api.ssfm_pm(dev, out_s, out_n, sig, noi, n_pol, n, v, vn, int(cplx), float(Vpi))
     output = _wrap_out(optical_signal, out_s, NULL if out_n is None else out_n, n_pol=op_input.n_pol)
     output.execution_time = time.time() - t0
     return back(output)
@@ -1672,7 +1686,7 @@ def _shortest_int_device(x: "_lib.DeviceArray", percent: float, dev: int):
     if n > _EYE_MAX_N:
         raise ValueError(f"shortest_int on the device takes up to 2^21 samples, got {n} (there is no CPU fallback)")
     out = np.zeros(2)
-    _lib._check(_lib.load().ssfm_shortest_int(dev, _lib._VP(x.ptr), n, float(percent), _lib._ptr(out)), "ssfm_shortest_int")
+    _lib.api.ssfm_shortest_int(dev, x, n, float(percent), _lib._ptr(out))
     return float(out[0]), float(out[1])
 
 
@@ -1700,8 +1714,7 @@ def ADC(input, fs: float = None, n: int = 8, otype: str = "v", *, device=None) -
     vmin, vmax = _shortest_int_device(x, 99.99, dev)
     levels = 2 ** int(n) - 1
     out = _lib.DeviceArray((x.size,), np.float64 if otype == "v" else np.int64, dev)
-    _lib._check(_lib.load().ssfm_adc_quantize(dev, _lib._VP(x.ptr), x.size, vmin, vmax, levels, int(otype == "v"), _lib._VP(out.ptr)),
-                "ssfm_adc_quantize")
+    _lib.api.ssfm_adc_quantize(dev, x, x.size, vmin, vmax, levels, int(otype == "v"), out)
     output = _wrap_out(electrical_signal, out, NULL)
     output.execution_time = time.time() - t0
     return back(output)
@@ -1904,8 +1917,7 @@ def FBG(input: optical_signal, neff: float = 1.45, v: float = 1.0, landa_D: floa
     n = λ.size
     Hd = _lib.DeviceArray((n,), np.complex128, dev)
     info = (_lib._I64 * 3)()
-    rc = _lib.load().ssfm_fbg_solve(dev, n, _lib._ptr(δ), _lib._ptr(s), _lib._ptr(k), float(F), apo, float(rtol), float(atol), apo_fn, None,
-                                    _lib._VP(Hd.ptr), info)
+    rc = _lib.load().ssfm_fbg_solve(dev, n, _lib._ptr(δ), _lib._ptr(s), _lib._ptr(k), float(F), apo, float(rtol), float(atol), apo_fn, None, Hd, info)
     if failure:
         raise failure[0]
     _lib._check(rc, "ssfm_fbg_solve")
@@ -1917,28 +1929,12 @@ def FBG(input: optical_signal, neff: float = 1.45, v: float = 1.0, landa_D: floa
 
     tau = _fbg_tau(H, grid.fs, ic) if filtfilt else 0.0
     Hnat = _lib.DeviceArray((n,), np.complex128, dev)
-    _lib._check(_lib.load().ssfm_fbg_delay(dev, _lib._VP(Hd.ptr), _lib._VP(Hnat.ptr), n, float(grid.dt), tau, int(bool(filtfilt))), "ssfm_fbg_delay")
+    _lib.api.ssfm_fbg_delay(dev, Hd, Hnat, n, float(grid.dt), tau, int(bool(filtfilt)))
 
-    # signal rows, then noise rows: ifft(fft(x) ifftshift(H)) on the chirp-z engine (any length)
+    # ifft(fft(x) ifftshift(H)) on the chirp-z engine (any length)
     raw_s, raw_n = input._raw("signal"), input._raw("noise")
-    shape = tuple(raw_s.shape)
-    rows = 1 if len(shape) == 1 else shape[0]
-    has_noise = raw_n is not NULL
-    nrow = rows * (2 if has_noise else 1)
-    row_bytes = rows * n * 16
-    buf = _lib.DeviceArray((nrow, n), np.complex128, dev)
-    for j, a in enumerate([raw_s, raw_n] if has_noise else [raw_s]):
-        d = _dev_array(a, np.complex128, dev)
-        _lib._check(_lib.load().ssfm_device_copy(dev, _lib._VP(buf.ptr + j * row_bytes), _lib._VP(d.ptr), row_bytes, 2), "ssfm_device_copy")
-    with _ChirpZ(n, nrow, dev) as eng:
-        eng.transfer(buf, Hnat, exponent=False)
-        eng.plan.synchronize()
-    outs = []
-    for j in range(2 if has_noise else 1):
-        o = _lib.DeviceArray(shape, np.complex128, dev)
-        _lib._check(_lib.load().ssfm_device_copy(dev, _lib._VP(o.ptr), _lib._VP(buf.ptr + j * row_bytes), row_bytes, 2), "ssfm_device_copy")
-        outs.append(o)
-    output = _wrap_out(optical_signal, outs[0], outs[1] if has_noise else NULL, n_pol=input.n_pol)
+    outs = _chirpz_transfer([raw_s] if raw_n is NULL else [raw_s, raw_n], Hnat, False, dev)
+    output = _wrap_out(optical_signal, outs[0], outs[1] if len(outs) > 1 else NULL, n_pol=input.n_pol)
     if retH:
         return back(output), Hd.to_host()
     output.execution_time = time.time() - t0

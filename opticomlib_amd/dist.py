@@ -188,7 +188,7 @@ def gather_results(local: Sequence, n_units: int, to_all: bool = True, on_device
     import torch
     import torch.distributed as dist
     if _device_backend():
-        from .devices import default_device
+        from .devices import _stack_rows, default_device
         dev = local[0].device if is_dev else default_device()
         meta = [None]
         if rank == 0:
@@ -198,11 +198,7 @@ def gather_results(local: Sequence, n_units: int, to_all: bool = True, on_device
         shape, dtstr = meta[0]
         dt = np.dtype(dtstr)
         # this rank's units side by side in one device block
-        block = _lib.DeviceArray((max(len(local), 1),) + tuple(shape), dt, dev)
-        nb = int(np.prod(shape)) * dt.itemsize
-        for k, a in enumerate(local):
-            d = a if isinstance(a, _lib.DeviceArray) else _lib.DeviceArray.from_host(np.asarray(a), dt, dev)
-            _lib._check(_lib.load().ssfm_device_copy(dev, _lib._VP(block.ptr + k * nb), _lib._VP(d.ptr), nb, 2), "ssfm_device_copy")
+        block = _stack_rows(local, dt, dev, shape=(max(len(local), 1),) + tuple(shape))
         out = gather_device(block.ptr, len(local), shape, dt, n_units, dev, to_all=to_all, owner=block)
         if out is None:
             return None
@@ -281,7 +277,7 @@ def propagate_channels(fields, dt: float, to_all: bool = True, dbp: bool = False
     ``fields`` may also be a ``_lib.DeviceArray`` holding THIS rank's units (generated on the device).
     """
     from . import _lib
-    from .devices import DBP, FIBER, _check_size, _is_fast_size, _precision_code, default_device, get_plan, linear_operator, step_schedule
+    from .devices import DBP, FIBER, _check_size, _is_fast_size, _precision_code, _stack_rows, default_device, get_plan, linear_operator, step_schedule
     from .typing import optical_signal
 
     kw = dict(fiber_kw)
@@ -365,7 +361,7 @@ def propagate_channels(fields, dt: float, to_all: bool = True, dbp: bool = False
             if local_dev:
                 nb = int(np.prod(unit_shape)) * fields.dtype.itemsize
                 d = _lib.DeviceArray(unit_shape, fields.dtype, dev)
-                _lib._check(_lib.load().ssfm_device_copy(dev, _lib._VP(d.ptr), _lib._VP(fields.ptr + k * nb), nb, 2), "ssfm_device_copy")
+                _lib.api.ssfm_device_copy(dev, d, fields.ptr + k * nb, nb, _lib.COPY_D2D)
                 x = optical_signal.from_device(d)
             else:
                 x = optical_signal(fields[u])
@@ -374,10 +370,5 @@ def propagate_channels(fields, dt: float, to_all: bool = True, dbp: bool = False
                 y = DBP(y, device=dev, **kw)
             local.append(y._raw("signal"))
     if ws == 1 and on_device and not _device_backend():
-        blk = _lib.DeviceArray((n_units,) + unit_shape, cdt, dev)
-        nb = int(np.prod(unit_shape)) * cdt.itemsize
-        for k, a in enumerate(local):
-            d = a if isinstance(a, _lib.DeviceArray) else _lib.DeviceArray.from_host(np.asarray(a), cdt, dev)
-            _lib._check(_lib.load().ssfm_device_copy(dev, _lib._VP(blk.ptr + k * nb), _lib._VP(d.ptr), nb, 2), "ssfm_device_copy")
-        return blk
+        return _stack_rows(local, cdt, dev, shape=(n_units,) + unit_shape)
     return gather_results(local, n_units, to_all=to_all, on_device=on_device)

@@ -74,7 +74,7 @@ def BER_analizer(mode: Literal["counter", "estimator"], *, device=None, **kargs)
         n = rx.size
         assert tx.size >= n, "Error: `Tx` and `Rx` must have the same length."
         errs = _lib._I64(0)
-        _lib._check(_lib.load().ssfm_device_count_diff(dev, _lib._VP(tx.ptr), _lib._VP(rx.ptr), n, _lib.C.byref(errs)), "ssfm_device_count_diff")
+        _lib.api.ssfm_device_count_diff(dev, tx, rx, n, _lib.C.byref(errs))
         return errs.value / n
     elif mode == "estimator":
         assert "eye_obj" in kargs.keys(), "`eye_obj` is a required argument for `mode='estimator'`."

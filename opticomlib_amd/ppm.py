@@ -93,7 +93,7 @@ def PPM_ENCODER(input, M: int, *, device=None) -> binary_sequence:
     dev = _device(device)
     bits = _on(bits, dev)
     out = _lib.DeviceArray((nsym * M,), np.uint8, dev)
-    _lib._check(_lib.load().ssfm_ppm_encode(dev, _lib._VP(bits.ptr), nsym, int(M), _lib._VP(out.ptr)), "ssfm_ppm_encode")
+    _lib.api.ssfm_ppm_encode(dev, bits, nsym, int(M), out)
     return _wrap(out, t0)
 
 
@@ -107,13 +107,12 @@ def PPM_DECODER(input, M: int, *, device=None) -> binary_sequence:
         return _wrap(np.empty(0, np.uint8), t0)
     dev = _device(device)
     slots = _on(slots, dev)
-    lib = _lib.load()
     n_bits = _lib._I64(0)
-    _lib._check(lib.ssfm_ppm_decode(dev, _lib._VP(slots.ptr), slots.size, int(M), None, 0, C.byref(n_bits)), "ssfm_ppm_decode")
+    _lib.api.ssfm_ppm_decode(dev, slots, slots.size, int(M), None, 0, C.byref(n_bits))
     if n_bits.value == 0:
         return _wrap(np.empty(0, np.uint8), t0)
     out = _lib.DeviceArray((n_bits.value,), np.uint8, dev)
-    _lib._check(lib.ssfm_ppm_decode(dev, _lib._VP(slots.ptr), slots.size, int(M), _lib._VP(out.ptr), n_bits.value, None), "ssfm_ppm_decode")
+    _lib.api.ssfm_ppm_decode(dev, slots, slots.size, int(M), out, n_bits.value, None)
     return _wrap(out, t0)
 
 
@@ -124,31 +123,28 @@ def _scratch(nbytes: int, dev: int) -> "_lib.DeviceArray":
 def _decide(x, noise, is_u8: bool, start: int, step: int, nsym: int, M: int, hard: bool, thr: float, want: str, rng: str, dev: int):
     """The per-symbol decision of ``nsym`` symbols of ``M`` slots read at ``x[start + q step]`` (+ ``noise``), then (hard) ``HDD``'s choice for
     the symbols without exactly one ON slot.  ``want``: 'bits' (the decoded ``k`` bits per symbol) or 'slots' (one-hot symbols)."""
-    lib = _lib.load()
     k = int(np.log2(M))
     out = _lib.DeviceArray((nsym * (k if want == "bits" else M),), np.uint8, dev)
-    bits, slots = (_lib._VP(out.ptr), None) if want == "bits" else (None, _lib._VP(out.ptr))
-    xp, np_ = _lib._VP(x.ptr), (None if noise is None else _lib._VP(noise.ptr))
+    bits, slots = (out, None) if want == "bits" else (None, out)
     counts = _scratch(4 * nsym, dev) if hard else None
-    _lib._check(lib.ssfm_ppm_decide(dev, xp, np_, int(is_u8), start, step, nsym, M, int(hard), float(thr), bits, slots,
-                                    _lib._VP(counts.ptr) if hard else None), "ssfm_ppm_decide")
+    _lib.api.ssfm_ppm_decide(dev, x, noise, int(is_u8), start, step, nsym, M, int(hard), float(thr), bits, slots, counts)
     if not hard:
         return out
-    resolve = lambda idx, draws, n_list, seed, stream: _lib._check(lib.ssfm_ppm_resolve(
-        dev, xp, np_, int(is_u8), start, step, nsym, M, float(thr), _lib._VP(counts.ptr), idx, draws, n_list, seed, stream, bits, slots), "ssfm_ppm_resolve")
+    resolve = lambda idx, draws, n_list, seed, stream: _lib.api.ssfm_ppm_resolve(
+        dev, x, noise, int(is_u8), start, step, nsym, M, float(thr), counts, idx, draws, n_list, seed, stream, bits, slots)
     if rng == "device":
         _DEVICE_RNG["stream"] += 1
         resolve(None, None, 0, _DEVICE_RNG["seed"] & (2 ** 64 - 1), _DEVICE_RNG["stream"])
         return out
     idx, cnt, nf = _scratch(4 * nsym, dev), _scratch(4 * nsym, dev), _lib._I64(0)
-    _lib._check(lib.ssfm_ppm_faulty(dev, _lib._VP(counts.ptr), nsym, _lib._VP(idx.ptr), _lib._VP(cnt.ptr), C.byref(nf)), "ssfm_ppm_faulty")
+    _lib.api.ssfm_ppm_faulty(dev, counts, nsym, idx, cnt, C.byref(nf))
     nf = int(nf.value)
     if nf:
         c = np.empty(nf, np.int32)
-        _lib._check(lib.ssfm_device_copy(dev, _lib._ptr(c), _lib._VP(cnt.ptr), c.nbytes, 1), "ssfm_device_copy")
+        _lib.api.ssfm_device_copy(dev, _lib._ptr(c), cnt, c.nbytes, _lib.COPY_D2H)
         draws = _hdd_draws(c, M)
         d = _lib.DeviceArray.from_host(draws.view(np.uint8), np.uint8, dev)
-        resolve(_lib._VP(idx.ptr), _lib._VP(d.ptr), nf, 0, 0)
+        resolve(idx, d, nf, 0, 0)
     return out
 
 
@@ -286,7 +282,7 @@ def BER_analizer(mode: Literal["counter", "estimator"], *, device=None, **kwargs
         if n == 0:
             return np.float64(np.nan)
         errs = _lib._I64(0)
-        _lib._check(_lib.load().ssfm_device_count_diff(dev, _lib._VP(tx.ptr), _lib._VP(rx.ptr), n, C.byref(errs)), "ssfm_device_count_diff")
+        _lib.api.ssfm_device_count_diff(dev, tx, rx, n, C.byref(errs))
         return errs.value / n
     elif mode.lower() == "estimator":
         eye_obj, M = kwargs.get("eye_obj", None), kwargs.get("M", None)

@@ -85,7 +85,6 @@ def _on_device(x, dev: int):
 
 def _welch_device(d, rows: int, n: int, ld: int, nperseg: int, out_f32: bool, dev: int) -> np.ndarray:
     """(rows, nperseg) fftshifted Welch estimate of the first ``n`` elements of every row of the device array ``d`` (rows ``ld`` apart)."""
-    lib = _lib.load()
     lay = _welch_layout(n, nperseg)
     code = _CODES[np.dtype(d.dtype)]
     itemsize = np.dtype(d.dtype).itemsize
@@ -95,8 +94,7 @@ def _welch_device(d, rows: int, n: int, ld: int, nperseg: int, out_f32: bool, de
     if lay["route"] in (1, 2):
         for r0 in range(0, rows, _MAX_GRID_ROWS):
             r1 = min(rows, r0 + _MAX_GRID_ROWS)
-            _lib._check(lib.ssfm_welch(dev, _lib._VP(d.ptr + r0 * ld * itemsize), code, r1 - r0, n, ld, nperseg, scale, int(out_f32),
-                                       _lib._VP(out.ctypes.data + r0 * nperseg * out.itemsize)), "ssfm_welch")
+            _lib.api.ssfm_welch(dev, d.ptr + r0 * ld * itemsize, code, r1 - r0, n, ld, nperseg, scale, int(out_f32), out.ctypes.data + r0 * nperseg * out.itemsize)
         return out
     from .devices import _ChirpZ
     _, hi = _lib.supported_log2n(_lib.C128, direct=True)
@@ -111,13 +109,10 @@ def _welch_device(d, rows: int, n: int, ld: int, nperseg: int, out_f32: bool, de
     with _ChirpZ(nperseg, chunk, dev) as eng:
         for first in range(0, total, chunk):
             count = min(chunk, total - first)
-            _lib._check(lib.ssfm_welch_frames(dev, _lib._VP(d.ptr), code, rows, n, ld, nperseg, first, count, chunk, _lib._VP(frames.ptr)),
-                        "ssfm_welch_frames")
+            _lib.api.ssfm_welch_frames(dev, d, code, rows, n, ld, nperseg, first, count, chunk, frames)
             eng.fourier(frames, False)
-            _lib._check(lib.ssfm_welch_accumulate(dev, _lib._VP(frames.ptr), nperseg, rows, nseg, first, count, _lib._VP(acc.ptr)),
-                        "ssfm_welch_accumulate")
-    _lib._check(lib.ssfm_welch_finish(dev, _lib._VP(acc.ptr), rows, nperseg, scale / nseg, int(out_f32), _lib._VP(out.ctypes.data)),
-                "ssfm_welch_finish")
+            _lib.api.ssfm_welch_accumulate(dev, frames, nperseg, rows, nseg, first, count, acc)
+    _lib.api.ssfm_welch_finish(dev, acc, rows, nperseg, scale / nseg, int(out_f32), out.ctypes.data)
     return out
 
 

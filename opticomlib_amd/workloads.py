@@ -72,6 +72,5 @@ def prbs_field_device(n: int, seed: int, n_pol: int = 2, sps: int = 16, power_w:
         pw = _lib.power_device(src, n_pol, n, True, dev)
         out = _lib.DeviceArray((n_pol, n), np.complex128, dev)
         for r in range(n_pol):
-            _lib._check(_lib.load().ssfm_device_scale_add(dev, _lib._VP(out.ptr + r * n * 16), _lib._VP(src + r * n * 16),
-                                                          float(np.sqrt(power_w / pw[r])), None, 2 * n), "ssfm_device_scale_add")
+            _lib.api.ssfm_device_scale_add(dev, out.ptr + r * n * 16, src + r * n * 16, float(np.sqrt(power_w / pw[r])), None, 2 * n)
     return out.astype(np.complex64)

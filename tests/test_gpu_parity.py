@@ -11,7 +11,9 @@ line to 3e-4 at 1000, proportional to the steps beyond) -- `TOL_100` / `TOL_1000
 tol(1000) and are only used for runs of at most 100 / of exactly 1000 steps.  Every comparison goes through
 `margins.within`, which writes the error it measured beside its bound (profiles/r06_parity_margins.txt).
 """
+import ctypes as C
 import os
+import re
 import warnings
 
 import numpy as np
@@ -2516,6 +2518,67 @@ def test_call_order_and_argument_errors():
         _lib.Plan(3000, 2, _lib.C64)
     with pytest.raises(oa.SsfmError, match="not available"):
         _lib.Plan(4096, 2, _lib.C64, device=99)
+    # every `int device` entry point: a device that is not there is SSFM_ERR_NO_DEVICE, checked before anything is touched
+    lib = _lib.load()
+    buf = _lib.DeviceArray((1 << 16,), np.complex128)
+    p = buf.ptr
+    sos, zi = np.array([[1.0, 0.0, 0.0, 1.0, 0.0, 0.0]]), np.zeros((1, 2))
+    tg, yset = np.zeros(64), np.zeros(4)
+    host = np.zeros(1 << 14)
+    ptr = _lib._ptr
+    i64, i32, u32, dbl = C.byref(C.c_int64()), C.byref(C.c_int()), C.byref(C.c_uint32()), C.byref(C.c_double())
+    fl, sz, vp = C.byref(C.c_float()), C.byref(C.c_size_t()), C.byref(C.c_void_p())
+    info = (C.c_int64 * 3)()
+    calls = {
+        "ssfm_plan_create": lambda: lib.ssfm_plan_create(vp, 99, 4096, 2, _lib.C64),
+        "ssfm_sosfiltfilt": lambda: lib.ssfm_sosfiltfilt(99, ptr(sos), ptr(zi), 1, p, p, 1024, 1, 0, 1),
+        "ssfm_sosfiltfilt_last": lambda: lib.ssfm_sosfiltfilt_last(99, fl, i32),
+        "ssfm_square_law": lambda: lib.ssfm_square_law(99, p, None, 1, 1024, 1.0, 1.0, p, None, 1),
+        "ssfm_square_law (host)": lambda: lib.ssfm_square_law(99, ptr(host), None, 1, 1024, 1.0, 1.0, ptr(host), None, 0),
+        "ssfm_device_alloc": lambda: lib.ssfm_device_alloc(99, 1024, vp),
+        "ssfm_device_free": lambda: lib.ssfm_device_free(99, p, 1024),
+        "ssfm_device_copy": lambda: lib.ssfm_device_copy(99, p, p, 1024, _lib.COPY_D2D),
+        "ssfm_device_convert": lambda: lib.ssfm_device_convert(99, p, _lib.C128, p, _lib.C64, 1024),
+        "ssfm_device_add": lambda: lib.ssfm_device_add(99, p, p, p, _lib.C128, 1024),
+        "ssfm_device_randn": lambda: lib.ssfm_device_randn(99, p, 1024, 1, 0, 0.0, 1.0),
+        "ssfm_device_sum3": lambda: lib.ssfm_device_sum3(99, p, p, None, None, 0.0, 1.0, 1024),
+        "ssfm_device_scale_add": lambda: lib.ssfm_device_scale_add(99, p, p, 1.0, None, 1024),
+        "ssfm_device_cumsum": lambda: lib.ssfm_device_cumsum(99, p, p, 1024),
+        "ssfm_mzm": lambda: lib.ssfm_mzm(99, p, None, p, None, 1, 1024, p, None, 0, 1.0, 0.0, 1.0, 0.0, 0),
+        "ssfm_laser": lambda: lib.ssfm_laser(99, p, 1024, 1.0, None, None, 0, 0.0, 1.0, 1.0),
+        "ssfm_device_axpb": lambda: lib.ssfm_device_axpb(99, p, p, 1.0, 0.0, 1024, 0),
+        "ssfm_device_shift": lambda: lib.ssfm_device_shift(99, p, p, 1024, 0, 1.0, 0.0),
+        "ssfm_device_reduce": lambda: lib.ssfm_device_reduce(99, _lib.REDUCE_MEAN, p, None, 1, 1024, 0, dbl),
+        "ssfm_prbs": lambda: lib.ssfm_prbs(99, p, 1024, 7, 1, u32),
+        "ssfm_device_mem_info": lambda: lib.ssfm_device_mem_info(99, sz, sz, sz),
+        "ssfm_device_chirp": lambda: lib.ssfm_device_chirp(99, p, 1024, 0),
+        "ssfm_device_sort_f64": lambda: lib.ssfm_device_sort_f64(99, p, 1024),
+        "ssfm_eye_prepare": lambda: lib.ssfm_eye_prepare(99, p, None, 0, 1024, 0, p),
+        "ssfm_eye_resample_stage": lambda: lib.ssfm_eye_resample_stage(99, 0, p, 1024, p, 1024),
+        "ssfm_eye_estimate": lambda: lib.ssfm_eye_estimate(99, p, 1024, ptr(tg), 32, ptr(yset), yset.size, ptr(host), 64, i64),
+        "ssfm_eye_levels": lambda: lib.ssfm_eye_levels(99, p, 1024, 32, 0, 16, 0.5, 500, ptr(host), 64),
+        "ssfm_device_sample": lambda: lib.ssfm_device_sample(99, p, None, 0, 2, 256, 0.5, None, p),
+        "ssfm_device_count_diff": lambda: lib.ssfm_device_count_diff(99, p, p, 1024, i64),
+        "ssfm_ppm_encode": lambda: lib.ssfm_ppm_encode(99, p, 256, 4, p),
+        "ssfm_ppm_decode": lambda: lib.ssfm_ppm_decode(99, p, 1024, 4, None, 0, i64),
+        "ssfm_ppm_decide": lambda: lib.ssfm_ppm_decide(99, p, None, 0, 0, 1, 256, 4, 1, 0.5, p, None, p),
+        "ssfm_ppm_faulty": lambda: lib.ssfm_ppm_faulty(99, p, 256, p, p, i64),
+        "ssfm_ppm_resolve": lambda: lib.ssfm_ppm_resolve(99, p, None, 0, 0, 1, 256, 4, 0.5, p, None, None, 0, 1, 0, p, None),
+        "ssfm_fbg_solve": lambda: lib.ssfm_fbg_solve(99, 1024, ptr(host), ptr(host), ptr(host), 0.0, 0, 1e-6, 1e-9, None, None, p, info),
+        "ssfm_fbg_delay": lambda: lib.ssfm_fbg_delay(99, p, p + (1 << 16), 1024, 1e-12, 0.0, 0),
+        "ssfm_pm": lambda: lib.ssfm_pm(99, p, None, p, None, 1, 1024, p, None, 0, 1.0),
+        "ssfm_shortest_int": lambda: lib.ssfm_shortest_int(99, p, 1024, 50.0, ptr(host)),
+        "ssfm_adc_quantize": lambda: lib.ssfm_adc_quantize(99, p, 1024, -1.0, 1.0, 16, 0, p),
+        "ssfm_welch": lambda: lib.ssfm_welch(99, p, _lib.C128, 1, 1024, 1024, 256, 1.0, 0, p),
+        "ssfm_welch_frames": lambda: lib.ssfm_welch_frames(99, p, _lib.C128, 1, 1024, 1024, 256, 0, 7, 8, p),
+        "ssfm_welch_accumulate": lambda: lib.ssfm_welch_accumulate(99, p, 256, 1, 7, 0, 7, p),
+        "ssfm_welch_finish": lambda: lib.ssfm_welch_finish(99, p, 1, 256, 1.0, 0, p),
+    }
+    hdr = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "ssfm_amd.h")).read()
+    names = set(re.findall(r"SSFM_API int (ssfm_\w+)\((?:ssfm_plan\*\* out, )?int device", hdr))
+    assert names == {k.split()[0] for k in calls}
+    for name, call in calls.items():
+        assert call() == 4, (name, lib.ssfm_last_error())
 
 
 def test_many_rows_equal_separate_runs():

@@ -35,6 +35,13 @@ def test_no_cpu_fallback_without_device():
     gv(sps=16, R=10e9)
     with pytest.raises(oa.SsfmError):
         oa.FIBER(optical_signal(np.ones(4096, complex)), length=1, h=1.0)
+    # every `int device` entry point reports a missing device as SSFM_ERR_NO_DEVICE (4), these two included
+    lib = _lib.load()
+    dst = np.zeros(64, np.complex128)                               # (never dereferenced: the device check comes first)
+    last = _lib.C.c_uint32(0)
+    assert lib.ssfm_prbs(0, _lib._ptr(dst), 64, 7, 1, _lib.C.byref(last)) == 4, lib.ssfm_last_error()
+    assert lib.ssfm_device_chirp(0, _lib._ptr(dst), 64, 0) == 4, lib.ssfm_last_error()
+    assert b"device 0 not available" in lib.ssfm_last_error()
 
 
 def test_product_never_imports_oracle():
