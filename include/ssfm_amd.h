@@ -51,6 +51,10 @@
  *   utils.py:2048-2079 (get_psd; also the          ssfm_welch (nperseg a power of two of 16 ... 8192, or < 16), and for every other nperseg
  *     signals' .psd(), typing.py:1850-1970:        ssfm_welch_frames / ssfm_welch_accumulate around ssfm_chirp_fourier, then ssfm_welch_finish
  *     scipy.signal.welch)
+ *   typing.py:1308-1419 (electrical_signal's       ssfm_signal_binary (+ - * > == with the signal / noise rules), ssfm_signal_unary (neg, conj, /, //,
+ *     operators), :1476-1486 (real, imag),         **, real, imag, abs), ssfm_signal_slice ([]), ssfm_signal_reduce (power, max |.|, sum),
+ *     :1599-1780 (conj, sum, abs, power,           ssfm_signal_phase (unwrap(angle(.))), ssfm_signal_pack / _split (filter: signal and noise as one
+ *     normalize, phase, filter)                    complex field through the DAC's convolution)
  *   (none: NumPy arrays are the reference's only   ssfm_device_alloc / _free / _copy / _convert / _add
  *     data format)                                 -- device-resident signals between calls
  *
@@ -564,6 +568,57 @@ SSFM_API int ssfm_welch_frames(int device, const void* x, int dtype, int64_t row
                                int64_t chunk, void* frames);
 SSFM_API int ssfm_welch_accumulate(int device, const void* frames, int64_t nperseg, int64_t rows, int64_t nseg, int64_t first, int64_t count, void* acc);
 SSFM_API int ssfm_welch_finish(int device, const void* acc, int64_t rows, int64_t nperseg, double factor, int out_f32, void* out);
+
+/* The algebra of electrical_signal (typing.py:1216-1780) on DEVICE arrays: float64 (is_complex = 0) or complex128 values, `rows` rows of `n`
+ * (rows = 1 today; the parameter is there for optical_signal's (2, N)).  `noise` / `out_noise` are nullable: an absent noise is the reference's
+ * NULL (typing.py:56-93: the identity of sums, absorbing in products).  Compiled without contraction: float64 results are NumPy's bits.
+ * Default stream; each call has finished its work when it returns.  No float atomics: two calls on the same input give the same bits.
+ * There is no device argument: a signal is computed where it lies, i.e. on the device that owns `signal` / `s1` / `re` / `src` (which becomes the
+ * calling thread's device); a pointer that is not device memory, or a second operand on another device, is SSFM_ERR_INVALID before any launch.
+ *
+ * ssfm_signal_binary: operand 1 is (s1, n1) of len1 values, operand 2 (s2, n2) of len2 values or, with s2 = NULL, the scalar re2 + j im2
+ * (complex2 says whether it is complex); len = n or 1 (one value for every sample).  The result is complex128 when either operand is, as
+ * numpy.result_type.  out_noise is needed exactly when n1 or n2 is given.
+ *   SSFM_SIGNAL_ADD   s1 + s2, n1 + n2                              (typing.py:1308-1315)
+ *   SSFM_SIGNAL_SUB   s1 + (-s2), n1 + (-n2)                        (typing.py:1327-1330)
+ *   SSFM_SIGNAL_RSUB  (-s1) + s2, (-n1) + n2                        (typing.py:1332-1335)
+ *   SSFM_SIGNAL_MUL   s1 s2, s1 n2 + n1 s2 + n1 n2 in that order    (typing.py:1337-1344)
+ *   SSFM_SIGNAL_GT    out_signal (uint8) = (s1 + n1) > (s2 + n2)    (typing.py:1378-1385; complex values in NumPy's lexicographic order)
+ *   SSFM_SIGNAL_EQ    out_signal (uint8) = (s1 + n1) == (s2 + n2)   (typing.py:1391-1398) */
+enum { SSFM_SIGNAL_ADD = 0, SSFM_SIGNAL_SUB = 1, SSFM_SIGNAL_RSUB = 2, SSFM_SIGNAL_MUL = 3, SSFM_SIGNAL_GT = 4, SSFM_SIGNAL_EQ = 5 };
+SSFM_API int ssfm_signal_binary(int op, int64_t rows, int64_t n, const void* s1, const void* n1, int64_t len1, int complex1, const void* s2,
+                                const void* n2, int64_t len2, int complex2, double re2, double im2, void* out_signal, void* out_noise);
+/* ssfm_signal_unary: p = p_re + j p_im (p_complex) is the divisor or the exponent.
+ *   SSFM_SIGNAL_NEG, _CONJ        of signal and noise                               (typing.py:1321-1325, :1599-1608)
+ *   SSFM_SIGNAL_DIV               signal / p, noise / p; complex128 out when the input or p is complex (NumPy's quotient)   (typing.py:1350-1359)
+ *   SSFM_SIGNAL_FLOORDIV          floor(signal / p), floor(noise / p); float64 only (typing.py:1361-1364)
+ *   SSFM_SIGNAL_POW2              signal^2, 2 signal noise + noise^2                (typing.py:1412-1414)
+ *   SSFM_SIGNAL_REAL, _IMAG       float64 parts of signal and noise                 (typing.py:1476-1486)
+ *   SSFM_SIGNAL_ABS_SIGNAL, _ABS_NOISE, _ABS_ALL   float64 |signal|, |noise|, |signal + noise| (the sum is never stored); no out_noise   (typing.py:1663-1691)
+ *   SSFM_SIGNAL_POW               (signal + noise) ** p_re, no out_noise: float64 by sqrt (0.5), the reciprocal (-1) or pow, as NumPy picks them;
+ *                                 complex128 for integer 0 < |p| < 100 by NumPy's products and for 0.5 (SSFM_ERR_UNSUPPORTED otherwise)   (typing.py:1415-1417) */
+enum { SSFM_SIGNAL_NEG = 0, SSFM_SIGNAL_CONJ = 1, SSFM_SIGNAL_DIV = 2, SSFM_SIGNAL_FLOORDIV = 3, SSFM_SIGNAL_POW2 = 4, SSFM_SIGNAL_REAL = 5, SSFM_SIGNAL_IMAG = 6,
+       SSFM_SIGNAL_ABS_SIGNAL = 7, SSFM_SIGNAL_ABS_NOISE = 8, SSFM_SIGNAL_ABS_ALL = 9, SSFM_SIGNAL_POW = 10 };
+SSFM_API int ssfm_signal_unary(int op, int64_t rows, int64_t n, const void* signal, const void* noise, int is_complex, double p_re, double p_im,
+                               int p_complex, void* out_signal, void* out_noise);
+/* ssfm_signal_slice: out[i] = in[start + i step], i < count, of signal and noise in one launch (typing.py:1366-1376); every index must lie in [0, n). */
+SSFM_API int ssfm_signal_slice(int64_t rows, int64_t n, const void* signal, const void* noise, int is_complex, int64_t start, int64_t step,
+                               int64_t count, void* out_signal, void* out_noise);
+/* ssfm_signal_reduce, results on the HOST:
+ *   SSFM_SIGNAL_POWER   out[0] = mean |signal + noise|^2, the sum formed in registers (one array: ssfm_device_reduce's SSFM_REDUCE_POWER)   (typing.py:1693-1720)
+ *   SSFM_SIGNAL_MAXABS  out[0] = max |signal| (a NaN stays, as in numpy.max); `noise` is not read    (typing.py:1741-1743)
+ *   SSFM_SIGNAL_SUM     out[0] + j out[1] = the sum of `signal`; `noise` is not read                 (typing.py:1610-1626) */
+enum { SSFM_SIGNAL_POWER = 0, SSFM_SIGNAL_MAXABS = 1, SSFM_SIGNAL_SUM = 2 };
+SSFM_API int ssfm_signal_reduce(int kind, int64_t rows, int64_t n, const void* signal, const void* noise, int is_complex, double* out);
+/* ssfm_signal_phase: out (DEVICE, n float64) = numpy.unwrap(numpy.angle(signal + noise)) (typing.py:1747-1756).  The wrap of every neighbouring pair
+ * is decided by NumPy's float64 expressions (its ddmod == -pi, dd > 0 case included) as an integer; the integers are scanned exactly
+ * (ssfm_device_cumsum) and multiplied by 2 pi afterwards, so the result does not depend on how the scan is split. */
+SSFM_API int ssfm_signal_phase(int64_t rows, int64_t n, const void* signal, const void* noise, int is_complex, double* out);
+/* filter (typing.py:1758-1780) with real signal, noise and taps: ssfm_signal_pack writes out (DEVICE, n complex128) = re + j im, which goes through
+ * ONE convolution on a plan (ssfm_load_padded, ssfm_apply_table); ssfm_signal_split reads n complex128 values at `src` (e.g. inside the plan's
+ * field) back into two float64 arrays (`im` nullable: the real part alone). */
+SSFM_API int ssfm_signal_pack(const double* re, const double* im, int64_t n, void* out);
+SSFM_API int ssfm_signal_split(const void* src, int64_t n, double* re, double* im);
 
 #ifdef __cplusplus
 }

@@ -106,6 +106,13 @@ SYMBOLS = {
     "ssfm_welch_frames": (_I, [_I, _VP, _I, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _VP]),
     "ssfm_welch_accumulate": (_I, [_I, _VP, _I64, _I64, _I64, _I64, _I64, _VP]),
     "ssfm_welch_finish": (_I, [_I, _VP, _I64, _I64, _D, _I, _VP]),
+    "ssfm_signal_binary": (_I, [_I, _I64, _I64, _VP, _VP, _I64, _I, _VP, _VP, _I64, _I, _D, _D, _VP, _VP]),
+    "ssfm_signal_unary": (_I, [_I, _I64, _I64, _VP, _VP, _I, _D, _D, _I, _VP, _VP]),
+    "ssfm_signal_slice": (_I, [_I64, _I64, _VP, _VP, _I, _I64, _I64, _I64, _VP, _VP]),
+    "ssfm_signal_reduce": (_I, [_I, _I64, _I64, _VP, _VP, _I, C.POINTER(_D)]),
+    "ssfm_signal_phase": (_I, [_I64, _I64, _VP, _VP, _I, _VP]),
+    "ssfm_signal_pack": (_I, [_VP, _VP, _I64, _VP]),
+    "ssfm_signal_split": (_I, [_VP, _I64, _VP, _VP]),
 }
 
 

@@ -1303,6 +1303,53 @@ def _upfir_device(bits, h, up: int, dev: int, spec=None) -> "_lib.DeviceArray":
     return out if cplx else _lib.real_device(out)
 
 
+def _filter_device(sig, noise, h):
+    """``scipy.signal.fftconvolve(x, h, mode='same')`` of a device-resident signal and its noise (``electrical_signal.filter``): the circular
+    convolution of :func:`_upfir_device` on a power-of-two complex128 plan, the input loaded from where it lies.  With real signal, noise and
+    taps the noise rides as the imaginary part of the signal's field: one convolution filters both and ``ssfm_signal_split`` parts them
+    again (the peak of that field is the larger of the two, so a noise below 1e-12 of the signal loses its digits).  Returns
+    ``(signal, noise or None)`` DeviceArrays."""
+    h = np.asarray(h)
+    if h.ndim != 1 or h.size < 1:
+        raise ValueError(f"filter: `h` must be a 1D array of at least one tap, got shape {h.shape}")
+    n, taps, dev = sig.size, h.size, sig.device
+    cplx_h, cplx_x = np.iscomplexobj(h), sig.dtype.kind == "c"
+    full = n + taps - 1
+    M = 1 << max(8, (full - 1).bit_length())
+    lo, hi = _lib.supported_log2n(_lib.C128, direct=True)
+    if M > (1 << hi):
+        raise ValueError(f"filter: {n} samples with {taps} taps exceed the device path (2^{hi} points)")
+    off = ((taps - 1) // 2) * 16                                # 'same': centred with respect to the full output
+    plan = get_plan(M, 1, _lib.C128, dev)
+    with plan.lock:
+        hd = _lib.DeviceArray.from_host(np.ascontiguousarray(h, dtype=np.complex128 if cplx_h else np.float64), None, dev)
+        plan.load_padded(hd)
+        plan.table_from_field(0)                                # slot 0 <- fft(h)
+        if not cplx_h and not cplx_x:
+            x = sig
+            if noise is not None:
+                x = _lib.DeviceArray((n,), np.complex128, dev)
+                _lib.api.ssfm_signal_pack(sig, noise, n, x)
+            plan.load_padded(x)
+            plan.apply_table(0)
+            plan.synchronize()
+            out_s = _lib.DeviceArray((n,), np.float64, dev)
+            out_n = None if noise is None else _lib.DeviceArray((n,), np.float64, dev)
+            _lib.api.ssfm_signal_split(plan.field_device_ptr + off, n, out_s, out_n)
+            return out_s, out_n
+        outs = []
+        for x in (sig, noise):
+            if x is None:
+                outs.append(None)
+                continue
+            plan.load_padded(x)
+            plan.apply_table(0)
+            out = _lib.DeviceArray((n,), np.complex128, dev)
+            plan.copy_from_field(off, out.ptr, n * 16)
+            outs.append(out)
+    return outs[0], outs[1]
+
+
 def DAC(input, pulse_shape: str = "nrz", coupling: str = "DC", Vpp: float = 1.0, offset: float = 0.0, h=None, BW: float = None,
         *, device=None, **kwargs) -> electrical_signal:
     """Digital-to-analog converter (reference ``devices.py:185-350``): a bit sequence becomes ``gv.sps`` samples

@@ -9,9 +9,12 @@
                        (``typing.py:2124-2196``).
 
 ``electrical_signal.psd()`` / ``optical_signal.psd()`` plot the Welch spectrum of :func:`opticomlib_amd.get_psd` (computed on the
-GPU; matplotlib is imported when the method is called).  Operators, the other plots, eye diagrams etc. are out of scope.
+GPU; matplotlib is imported when the method is called).  :class:`electrical_signal` has the reference's operators and methods, computed
+where the signal lies; ``optical_signal`` has a small host part of them.  The other plots, eye diagrams etc. are out of scope.
 """
 from __future__ import annotations
+
+import numbers
 
 import numpy as np
 
@@ -206,11 +209,30 @@ class binary_sequence:
 
 
 class electrical_signal:
-    """1-D electrical signal with optional noise (the slice ``LPF`` needs of reference
-    ``typing.py:1022-1165``)."""
+    """1-D electrical signal with optional noise and the algebra of the reference's class (``typing.py:1022-1780``).
+
+    ``+ - * / // **``, ``[]``, ``> < ==``, unary ``-``, ``abs``, ``power``, ``normalize``, ``phase``, ``conj``, ``sum``, ``filter``, ``w``,
+    ``f``, ``t``, ``fs``, ``sps``, ``dt``, ``real``, ``imag`` and the NumPy protocols ``__array__`` / ``__array_ufunc__`` carry the reference's
+    names, argument checks, error texts and signal / noise rules.
+
+    Residency: an operation on a signal that lies in GPU memory (``on_device``: what ``PD``, ``LPF``, ``ADC``, ``DAC`` and ``SAMPLER``
+    return) is computed there by the HIP kernels of ``csrc/signal_ops.hip`` and its result lies there too; a Python scalar is a kernel
+    argument, a host array or host signal as the other operand is uploaded once, two signals on different GPUs are a ``ValueError``.
+    Device arrays are float64 or complex128; any other device type raises ``TypeError``.  An operation on a host-only signal is NumPy on
+    the host, as in the reference, and loads no device.  ``power``, ``sum`` and an integer index of a noiseless signal return host scalars;
+    ``==`` returns a host bool array, ``>`` / ``<`` a ``binary_sequence`` (device-resident for device operands).  ``np.asarray(x)``,
+    iteration and a NumPy ufunc other than the three reflected operators and ``np.abs`` materialise the signal on the host.
+
+    On the device, ``filter`` with real signal, noise and taps carries the noise as the imaginary part of the signal's field through one
+    convolution: a noise below ``1e-12`` of the signal loses its digits on that path.  ``**`` of a complex128 device signal takes the
+    exponents NumPy computes by products (integers ``|p| < 100``) and ``0.5``; another exponent raises ``ValueError``.
+
+    Not provided: ``plot``, ``plot_eye``, ``print``, ``grid``, ``legend``, ``show``, ``sizeof``, the reference's ``__getattr__`` delegation
+    to ``ndarray`` and ``__array_function__``."""
 
     signal = _LazyArray()
     noise = _LazyArray()
+    __hash__ = None                  # (an `__eq__` that returns an array: unhashable, as the reference's class)
 
     @classmethod
     def from_device(cls, signal, noise=NULL):
@@ -249,6 +271,7 @@ class electrical_signal:
         self.noise = noi
         self.execution_time = 0.0
 
+    # -- metadata (no transfer)
     @property
     def size(self) -> int:
         return int(self._raw("signal").size)
@@ -257,17 +280,62 @@ class electrical_signal:
     def ndim(self) -> int:
         return self._raw("signal").ndim
 
+    @property
+    def shape(self):
+        return tuple(self._raw("signal").shape)
+
+    @property
+    def on_device(self) -> bool:
+        """True while ``signal`` lives in GPU memory only (no host copy has been asked for)."""
+        return _is_device(self._raw("signal"))
+
+    @property
+    def type(self):
+        return type(self)
+
+    @property
+    def fs(self):
+        return gv.fs
+
+    @property
+    def sps(self):
+        return gv.sps
+
+    @property
+    def dt(self):
+        return gv.dt
+
+    @property
+    def t(self):
+        return gv.t[:self.size]
+
     def __len__(self):
         return self.size
+
+    def __iter__(self):
+        return iter(self.__array__())
+
+    def __array__(self, dtype=None, copy=None):
+        arr = self.signal + self.noise
+        return arr if dtype is None else arr.astype(dtype)
+
+    def to_numpy(self) -> np.ndarray:
+        return np.asarray(self.signal + self.noise)
+
+    def w(self, shift: bool = False) -> np.ndarray:
+        """Angular frequency grid [rad/s], FFT order (reference ``typing.py:1628-1644``)."""
+        w = np.fft.fftfreq(self.size, gv.dt) * 2 * np.pi
+        return np.fft.fftshift(w, axes=-1) if shift else w
+
+    def f(self, shift: bool = False) -> np.ndarray:
+        """Frequency grid [Hz] (reference ``typing.py:1646-1660``)."""
+        return self.w(shift) / (2 * np.pi)
 
     def __call__(self, domain, shift: bool = False):
         """New object holding the FFT (``'w'`` / ``'f'``) or inverse FFT (``'t'``) of signal and noise along the last axis
         (reference ``typing.py:1421-1462``); ``shift`` applies fftshift / ifftshift.  Computed on the GPU."""
         from . import devices
         return devices._fourier(self, domain, shift)
-
-    def to_numpy(self) -> np.ndarray:
-        return np.asarray(self.signal + self.noise)
 
     def psd(self, fmt='-', mode='x', n=None, xlabel=None, ylabel=None, yscale='dbm', grid=False, hold=True, show=False, **kwargs):
         """Plot the power spectral density (reference ``typing.py:1850-1970``): Welch's estimate of the first ``n`` samples
@@ -277,7 +345,364 @@ class electrical_signal:
         return plot_psd(self, fmt, mode, n, xlabel, ylabel, yscale, grid, hold, show, **kwargs)
 
     def __repr__(self):
-        return f"electrical_signal(size={self.size}, dtype={self._raw('signal').dtype}, noise={'NULL' if self._raw('noise') is NULL else 'array'})"
+        where = " [device]" if self.on_device else ""
+        return f"electrical_signal(size={self.size}, dtype={self._raw('signal').dtype}, noise={'NULL' if self._raw('noise') is NULL else 'array'}){where}"
+
+    # -- device plumbing: the arrays where they lie, uploads of the other operand, launches
+    def _device_arrays(self):
+        """``(signal, noise or None)`` as float64 / complex128 DeviceArrays of one type on one GPU, for a device-resident signal."""
+        from . import _lib
+        s, n = self._raw("signal"), self._raw("noise")
+        if s.dtype not in _DEVICE_DTYPES:
+            raise TypeError(f"electrical_signal: the device algebra takes float64 and complex128, this signal lies on the GPU as {s.dtype}; "
+                            "there is no host fallback for a device-resident signal (convert it, or take .to_numpy())")
+        if n is NULL:
+            return s, None
+        if not _is_device(n):                                   # (a noise that was assigned on the host afterwards)
+            n = _lib.DeviceArray.from_host(np.ascontiguousarray(n, dtype=s.dtype), None, s.device)
+        elif n.dtype != s.dtype or n.device != s.device:
+            raise TypeError(f"electrical_signal: signal ({s.dtype}, GPU {s.device}) and noise ({n.dtype}, GPU {n.device}) differ")
+        return s, n
+
+    def _upload(self, dev):
+        """This host signal's arrays on GPU ``dev`` as float64 / complex128 (the widening ``np.result_type`` would apply anyway)."""
+        from . import _lib
+        s = np.asarray(self.signal)
+        dt = np.complex128 if s.dtype.kind == "c" else np.float64
+        up = lambda a: _lib.DeviceArray.from_host(np.ascontiguousarray(a, dtype=dt), None, dev)       # noqa: E731
+        return up(s), (None if self.noise is NULL else up(self.noise))
+
+    def _wrap(self, s, n=None):
+        return self.__class__.from_device(s, NULL if n is None else n)
+
+    def _shapes_error(self, other):
+        return ValueError(f"Can't operate '{self.__class__.__name__}'s with shapes {self.shape} and {other.shape}")
+
+    def _parse(self, other):
+        """The other operand as a signal of this class whose size is this one's or 1 (reference ``typing.py:1557-1573``)."""
+        if not isinstance(other, self.type):
+            other = self.__class__(other)
+        if self.size != other.size and min(self.size, other.size) != 1:
+            raise self._shapes_error(other)
+        return other
+
+    def _binary(self, op, other):
+        """``op``: 'add', 'sub', 'rsub', 'mul', 'gt' or 'eq' between this signal and ``other``, where the operands lie."""
+        other_dev = isinstance(other, electrical_signal) and other.on_device
+        if self.on_device or other_dev:
+            return self._binary_device(op, other)
+        o = self._parse(other)
+        s1, n1, s2, n2 = self.signal, self.noise, o.signal, o.noise
+        if op in ("gt", "eq"):
+            x, y = s1 + n1, s2 + n2
+            return binary_sequence(x > y) if op == "gt" else x == y
+        neg = lambda a: a if a is NULL else -a                                                       # noqa: E731
+        if op == "add":
+            return self.__class__(s1 + s2, n1 + n2)
+        if op == "sub":                                         # a + (-b), as the reference forms it
+            return self.__class__(s1 + (-s2), n1 + neg(n2))
+        if op == "rsub":                                        # (-a) + b
+            return self.__class__((-s1) + s2, neg(n1) + n2)
+        noi = NULL                                              # s1 n2 + n1 s2 + n1 n2; a product with NULL is NULL, a sum with it the other term
+        for a, b in ((s1, n2), (n1, s2), (n1, n2)):
+            if a is not NULL and b is not NULL:
+                noi = noi + a * b
+        return self.__class__(s1 * s2, noi)
+
+    def _binary_device(self, op, other):
+        from . import _lib
+        codes = {"add": 0, "sub": 1, "rsub": 2, "mul": 3, "gt": 4, "eq": 5}
+        scalar = None
+        if isinstance(other, (numbers.Number, np.number, np.bool_)):
+            scalar = complex(other) if isinstance(other, (complex, np.complexfloating)) else float(other)
+            size2, o = 1, None
+        else:
+            # (any electrical_signal is used where it lies, whatever its class: the constructor would read it to the host; the result is self's class)
+            o = other if isinstance(other, electrical_signal) else self.__class__(other)
+            size2 = o.size
+        n = max(self.size, size2)
+        if self.size != size2 and min(self.size, size2) != 1:
+            raise self._shapes_error(o)
+        devs = {x._raw("signal").device for x in (self, o) if x is not None and x.on_device}
+        if len(devs) > 1:
+            raise ValueError(f"Can't operate '{self.__class__.__name__}'s that lie on different GPUs {sorted(devs)}: move one of them first")
+        dev = devs.pop()
+        s1, n1 = self._device_arrays() if self.on_device else self._upload(dev)
+        s2 = n2 = None
+        if o is not None:
+            s2, n2 = o._device_arrays() if o.on_device else o._upload(dev)
+        c1 = s1.dtype.kind == "c"
+        c2 = isinstance(scalar, complex) if o is None else s2.dtype.kind == "c"
+        if op in ("gt", "eq"):
+            out = _lib.DeviceArray((n,), np.uint8, dev)
+            out_n = None
+        else:
+            # the reference adds the noises with NULL as the identity, so a lone noise of size 1 meets a signal of size n in the constructor
+            if op != "mul" and (n1 is None) != (n2 is None) and (n1 if n2 is None else n2).size != n:
+                raise ValueError(f"`signal` and `noise` must have the same shape, mismatch shapes {(n,)} and {(1,)}!")
+            dt = np.complex128 if (c1 or c2) else np.float64
+            out = _lib.DeviceArray((n,), dt, dev)
+            out_n = _lib.DeviceArray((n,), dt, dev) if (n1 is not None or n2 is not None) else None
+        z = complex(scalar) if scalar is not None else 0j
+        _lib.api.ssfm_signal_binary(codes[op], 1, n, s1, n1, s1.size, int(c1), s2, n2, size2, int(c2), z.real, z.imag, out, out_n)
+        if op == "gt":
+            return binary_sequence.from_device(out)
+        if op == "eq":
+            return out.to_host().astype(bool)
+        return self._wrap(out, out_n)
+
+    def _unary_device(self, op, p=0.0, *, real_out=False, single=False, complex_out=False):
+        """One launch of ``ssfm_signal_unary``; ``single``: one result array without noise."""
+        from . import _lib
+        s, n = self._device_arrays()
+        cplx = s.dtype.kind == "c"
+        dt = np.float64 if real_out else (np.complex128 if (cplx or complex_out) else np.float64)
+        out = _lib.DeviceArray(s.shape, dt, s.device)
+        out_n = None if (single or n is None) else _lib.DeviceArray(s.shape, dt, s.device)
+        z = complex(p)
+        _lib.api.ssfm_signal_unary(_UNARY[op], 1, s.size, s, n, int(cplx), z.real, z.imag, int(isinstance(p, (complex, np.complexfloating))), out, out_n)
+        return self._wrap(out, out_n)
+
+    # -- operators (reference typing.py:1308-1419)
+    def __add__(self, other):
+        return self._binary("add", other)
+
+    def __radd__(self, other):
+        return self._binary("add", other)
+
+    def __sub__(self, other):
+        return self._binary("sub", other)
+
+    def __rsub__(self, other):
+        return self._binary("rsub", other)
+
+    def __mul__(self, other):
+        return self._binary("mul", other)
+
+    def __rmul__(self, other):
+        return self._binary("mul", other)
+
+    def __neg__(self):
+        if self.on_device:
+            return self._unary_device("neg")
+        return self.__class__(-self.signal, NULL if self.noise is NULL else -self.noise)
+
+    def __truediv__(self, number):
+        if not isinstance(number, numbers.Complex):
+            raise TypeError(f"Can't divide electrical_signal by type {type(number)}")
+        if number == 0:
+            raise ZeroDivisionError("Can't divide electrical_signal by zero")
+        if self.on_device:
+            cplx = isinstance(number, (complex, np.complexfloating))
+            return self._unary_device("div", complex(number) if cplx else float(number), complex_out=cplx)
+        return self.__class__(self.signal / number, NULL if self.noise is NULL else self.noise / number)
+
+    def __floordiv__(self, other):
+        if self.on_device:
+            if not isinstance(other, numbers.Complex):
+                raise TypeError(f"Can't divide electrical_signal by type {type(other)}")
+            if other == 0:
+                raise ZeroDivisionError("Can't divide electrical_signal by zero")
+            if self._raw("signal").dtype.kind == "c" or isinstance(other, (complex, np.complexfloating)):
+                np.floor(np.zeros(1, np.complex128))            # NumPy's own TypeError: floor takes no complex values
+            return self._unary_device("floordiv", float(other))
+        x = self / other
+        return self.__class__(np.floor(x.signal), NULL if x.noise is NULL else np.floor(x.noise))
+
+    def __pow__(self, other):
+        """``** 0``: ones; ``** 1``: the signal; ``** 2``: ``signal**2`` with the noise ``2 signal noise + noise**2`` (``2.0`` takes this
+        branch too: the reference compares with ``==``); any other real exponent: ``(signal + noise) ** other`` without noise."""
+        if not isinstance(other, numbers.Real):
+            raise TypeError(f"Can't exponentiate electrical_signal by type {type(other)}")
+        if self.on_device:
+            s, n = self._device_arrays()
+            if other == 0:
+                from . import _lib
+                ones = _lib.zeros_device(s.shape, s.dtype, s.device)
+                return self._wrap(_lib.shift_device(ones, 1.0))
+            if other == 1:
+                return self._wrap(s, n)
+            if other == 2:
+                return self._unary_device("pow2")
+            if s.dtype.kind == "c" and other != 0.5 and not (float(other).is_integer() and abs(other) < 100):
+                raise ValueError(f"electrical_signal ** {other}: a complex128 signal on the GPU takes integer exponents below 100 and 0.5; "
+                                 "there is no host fallback for a device-resident signal")
+            return self._unary_device("pow", float(other), single=True)
+        if other == 0:
+            sig, noi = np.ones_like(self.signal), NULL
+        elif other == 1:
+            sig, noi = self.signal, self.noise
+        elif other == 2:
+            sig = self.signal ** 2
+            noi = NULL if self.noise is NULL else 2 * self.signal * self.noise + self.noise ** 2
+        else:
+            sig, noi = (self.signal + self.noise) ** other, NULL
+        return self.__class__(sig, noi)
+
+    def __getitem__(self, key):
+        """A slice: a new signal (an empty one is the constructor's ``ValueError``); an ``int``: the value itself when there is no noise, a
+        signal of size 1 otherwise (reference ``typing.py:1366-1376``)."""
+        if not isinstance(key, (slice, int)):
+            raise TypeError(f"Invalid argument type. {key} of type {type(key)}")
+        if not self.on_device:
+            if isinstance(key, int) and self.noise is NULL:
+                return self.signal[key]
+            return self.__class__(self.signal[key], NULL if self.noise is NULL else self.noise[key])
+        from . import _lib
+        s, n = self._device_arrays()
+        if isinstance(key, slice):
+            start, stop, step = key.indices(s.size)
+            count = len(range(start, stop, step))
+            if count < 1:
+                raise ValueError(f"Signal must be scalar or 1D array for electrical_signal, invalid shape {(0,)}")
+        else:
+            if not -s.size <= key < s.size:
+                raise IndexError(f"index {key} is out of bounds for axis 0 with size {s.size}")
+            start, step, count = key % s.size, 1, 1
+        out = _lib.DeviceArray((count,), s.dtype, s.device)
+        out_n = None if n is None else _lib.DeviceArray((count,), s.dtype, s.device)
+        _lib.api.ssfm_signal_slice(1, s.size, s, n, int(s.dtype.kind == "c"), start, step, count, out, out_n)
+        if isinstance(key, int) and n is None:
+            return out.to_host()[0]
+        return self._wrap(out, out_n)
+
+    def __gt__(self, other):
+        return self._binary("gt", other)
+
+    def __lt__(self, other):
+        return other - self > 0                                 # (the reference's form: through `-`, not a comparison of its own)
+
+    def __eq__(self, other):
+        return self._binary("eq", other)
+
+    def __array_ufunc__(self, ufunc, method, *inputs, **kwargs):
+        """``ndarray + x``, ``ndarray - x`` and ``ndarray * x`` go to the signal's own operators (the noise rules hold and no object array
+        appears); ``np.abs`` of a device-resident signal stays there; any other ufunc sees the materialised ``signal + noise`` and a 1-D
+        result comes back wrapped (reference ``typing.py:1240-1275``)."""
+        if method == "__call__" and not kwargs.get("out"):
+            if ufunc in (np.add, np.subtract, np.multiply) and len(inputs) == 2 and isinstance(inputs[1], electrical_signal):
+                lhs, rhs = inputs
+                if ufunc is np.add:
+                    return rhs.__add__(lhs)
+                if ufunc is np.subtract:
+                    return (-rhs).__add__(lhs)
+                return rhs.__mul__(lhs)
+            if ufunc is np.absolute and self.on_device and inputs[0] is self:
+                return self._unary_device("abs_all", real_out=True, single=True)
+        args = [a.__array__() if isinstance(a, self.__class__) else a for a in inputs]
+        result = getattr(ufunc, method)(*args, **kwargs)
+        if isinstance(result, np.ndarray) and result.ndim == 1:
+            return self.__class__(result)
+        return result
+
+    # -- methods (reference typing.py:1476-1486, :1599-1780)
+    @property
+    def real(self):
+        if self.on_device:
+            return self._unary_device("real", real_out=True)
+        return self.__class__(self.signal.real, NULL if self.noise is NULL else self.noise.real)
+
+    @property
+    def imag(self):
+        if self.on_device:
+            return self._unary_device("imag", real_out=True)
+        return self.__class__(self.signal.imag, NULL if self.noise is NULL else self.noise.imag)
+
+    def conj(self):
+        if self.on_device:
+            return self._unary_device("conj")
+        return self.__class__(self.signal.conj(), NULL if self.noise is NULL else self.noise.conj())
+
+    def _reduce_device(self, kind, s, n=None):
+        from . import _lib
+        import ctypes
+        out = (ctypes.c_double * 2)()
+        _lib.api.ssfm_signal_reduce(kind, 1, s.size, s, n, int(s.dtype.kind == "c"), out)
+        return out
+
+    def sum(self, axis=None):
+        """Sums of signal and noise as a signal of size 1 (host values: one small read each on the device)."""
+        if self.on_device:
+            s, n = self._device_arrays()
+            def val(a):
+                o = self._reduce_device(2, a)
+                return np.complex128(complex(o[0], o[1])) if a.dtype.kind == "c" else np.float64(o[0])
+            return self.__class__(val(s), NULL if n is None else val(n))
+        return self.__class__(self.signal.sum(axis=axis), NULL if self.noise is NULL else self.noise.sum(axis=axis))
+
+    def abs(self, of="all"):
+        """``|signal|``, ``|noise|`` (zeros of the real type without noise) or ``|signal + noise|`` as a new signal."""
+        if not isinstance(of, str):
+            raise TypeError('`of` must be a string.')
+        of = of.lower()
+        if of not in ("signal", "noise", "all"):
+            raise ValueError('`of` must be one of the following values ("signal", "noise", "all")')
+        if self.on_device:
+            if of == "noise" and self._raw("noise") is NULL:
+                from . import _lib
+                s = self._raw("signal")
+                return self._wrap(_lib.zeros_device(s.shape, np.float64, s.device))
+            return self._unary_device("abs_" + of, real_out=True, single=True)
+        if of == "signal":
+            return self.__class__(np.abs(self.signal))
+        if of == "noise":
+            return self.__class__(np.zeros_like(self.signal.real) if self.noise is NULL else np.abs(self.noise))
+        return np.abs(self)                                     # through __array_ufunc__, as the reference
+
+    def power(self, unit="W", of="all"):
+        """Mean ``|.|**2`` of the signal, the noise or both, in W or dBm (a host scalar)."""
+        if of.lower() not in ("signal", "noise", "all"):
+            raise ValueError('`of` must be one of the following values ("signal", "noise", "all")')
+        if self.on_device:
+            s, n = self._device_arrays()
+            of = of.lower()
+            if of == "noise" and n is None:
+                p = np.float64(0.0)
+            else:
+                p = np.float64(self._reduce_device(0, n if of == "noise" else s, n if of == "all" else None)[0])
+        else:
+            p = np.mean(np.asarray(self.abs(of).signal) ** 2, axis=-1)
+        unit = unit.lower()
+        if unit == "w":
+            return p
+        if unit == "dbm":
+            with np.errstate(divide="ignore"):
+                return 10 * np.log10(p) + 30
+        raise ValueError('`unit` must be one of the following values ("W", "dBm")')
+
+    def normalize(self, by="power"):
+        """The signal divided by the square root of its signal power, or by its largest ``|signal|``."""
+        if by == "power":
+            return self / self.power("W", "signal") ** 0.5
+        if by == "amplitude":
+            if self.on_device:
+                return self / np.float64(self._reduce_device(1, self._device_arrays()[0])[0])
+            return self / np.abs(self.signal).max()
+        raise ValueError('`by` must be one of the following values ("power", "amplitude")')
+
+    def phase(self):
+        """``unwrap(angle(signal + noise))`` as a signal without noise."""
+        if self.on_device:
+            from . import _lib
+            s, n = self._device_arrays()
+            out = _lib.DeviceArray(s.shape, np.float64, s.device)
+            _lib.api.ssfm_signal_phase(1, s.size, s, n, int(s.dtype.kind == "c"), out)
+            return self._wrap(out)
+        return self.__class__(np.unwrap(np.angle(self.__array__())))
+
+    def filter(self, h):
+        """``scipy.signal.fftconvolve(., h, mode='same')`` of signal and noise (reference ``typing.py:1758-1780``)."""
+        if self.on_device:
+            from . import devices
+            s, n = self._device_arrays()
+            return self._wrap(*devices._filter_device(s, n, h))
+        import scipy.signal as sg
+        return self.__class__(sg.fftconvolve(self.signal, h, mode="same"), NULL if self.noise is NULL else sg.fftconvolve(self.noise, h, mode="same"))
+
+
+_DEVICE_DTYPES = (np.dtype(np.float64), np.dtype(np.complex128))
+# enum of include/ssfm_amd.h (ssfm_signal_unary)
+_UNARY = {"neg": 0, "conj": 1, "div": 2, "floordiv": 3, "pow2": 4, "real": 5, "imag": 6, "abs_signal": 7, "abs_noise": 8, "abs_all": 9, "pow": 10}
 
 
 class optical_signal:

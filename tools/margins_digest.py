@@ -1,0 +1,45 @@
+#!/usr/bin/env python3
+"""Fold the margins a GPU test run recorded (tests/margins.py: SSFM_MARGINS_FILE) into one row per kind of comparison.
+
+    SSFM_MARGINS_FILE=raw.txt python -m pytest tests/test_signal_algebra_gpu.py -m gpu
+    python tools/margins_digest.py raw.txt profiles/signal_ops_margins.txt
+
+A kind is the record's `what` with the size (`n=...`), the tap count and the fixture's case name taken out; its row carries the record with the
+largest measured / bound of that kind, and how many records it stands for."""
+import collections
+import re
+import sys
+
+
+def kind(what):
+    what = re.sub(r"\b(n|taps)=\d+ ", "", what)
+    return re.sub(r"^(binary|reflected|scalar|pow|methods|filter|protocol)/\S+", lambda m: m.group(1) + " fixtures", what)
+
+
+def main(src, dst):
+    rows, total = collections.OrderedDict(), 0
+    for line in open(src):
+        if line.startswith("#") or not line.strip():
+            continue
+        test, rest = line.rstrip("\n").split(" | ", 1)
+        what, _steps, measured, bound, _ratio = rest.rsplit(" | ", 4)          # (`what` may hold a `|` of its own)
+        m, b = float(measured), float(bound)
+        r = m / b if b else 0.0
+        total += 1
+        k = kind(what.strip())
+        count = rows[k][4] + 1 if k in rows else 1
+        best = (m, b, r, test.split("::")[-1]) if k not in rows or r > rows[k][2] else rows[k][:4]
+        rows[k] = (*best, count)
+    with open(dst, "w") as f:
+        f.write(f"# {total} comparisons recorded by the GPU tests of the signal algebra on one MI355X, folded by tools/margins_digest.py: per kind of comparison,\n"
+                "# the record with the largest measured / bound.  [ulp]: max |d| / (2^-52 |want|), of the modulus for complex values; [rad]: absolute;\n"
+                "# [|d| / (...)]: elementwise against the stated product bound; otherwise max |d| / peak.  'numpy vs exact' rows are NumPy's own distance from\n"
+                "# the exact restatement of unwrap (their bound column is what the device is then allowed).  Comparisons held to NumPy's bits record nothing.\n"
+                "# kind | records | measured | bound | measured / bound | test of the worst record\n")
+        for k, (m, b, r, t, count) in rows.items():
+            f.write(f"{k} | {count} | {m:.3e} | {b:.3e} | {r:.3f} | {t}\n")
+    print(total, "records,", len(rows), "kinds ->", dst)
+
+
+if __name__ == "__main__":
+    main(sys.argv[1], sys.argv[2])
