@@ -562,7 +562,8 @@ SSFM_API int ssfm_adc_quantize(int device, const double* x, int64_t n, double vm
  *   ssfm_welch_frames      any nperseg: frames (DEVICE, chunk x nperseg complex128) <- the windowed segments first ... first + count - 1
  *                          (segment g is segment g % nseg of row g / nseg), zero from `count` up to `chunk`
  *   ssfm_welch_accumulate  acc (DEVICE, rows x nperseg float64) += |frames|^2 of the chunk's segments, per row in segment order
- *   ssfm_welch_finish      out = factor * acc, fftshifted (factor = 1 / (nseg sum(window)^2)) */
+ *   ssfm_welch_finish      out = factor * acc, fftshifted (factor = 1 / (nseg sum(window)^2)); rows <= 65535 (SSFM_ERR_INVALID beyond): a caller
+ *                          with more rows finishes them in blocks, `acc` and `out` advanced by the block's rows x nperseg elements */
 SSFM_API int ssfm_welch(int device, const void* x, int dtype, int64_t rows, int64_t n, int64_t ld, int64_t nperseg, double factor, int out_f32, void* out);
 SSFM_API int ssfm_welch_frames(int device, const void* x, int dtype, int64_t rows, int64_t n, int64_t ld, int64_t nperseg, int64_t first, int64_t count,
                                int64_t chunk, void* frames);

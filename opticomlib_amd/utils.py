@@ -19,7 +19,7 @@ from .typing import _is_device
 DIRECT_MAX = 15               # route 2: nperseg < 16, a direct DFT per segment
 POW2_MIN, POW2_MAX = 16, 8192  # route 1: one workgroup line transform per segment
 CHUNK_BYTES = 256 << 20       # route 3: chunk_rows x M x 16 B of the chirp-z plan stays at or below this
-_MAX_GRID_ROWS = 65535        # ssfm_welch: rows per call (grid.y)
+_MAX_GRID_ROWS = 65535        # ssfm_welch, ssfm_welch_finish: rows per call (grid.y)
 _MAX_PLAN_BATCH = 65535       # route 3: rows of a plan (ssfm_plan_create)
 
 
@@ -83,6 +83,13 @@ def _on_device(x, dev: int):
     return _lib.DeviceArray.from_host(np.ascontiguousarray(x), device=dev)
 
 
+def _check_chirp_length(nperseg: int) -> None:
+    """Route 3 runs on the chirp-z engine, whose line of M >= 2 nperseg - 1 points has a largest size: refuse a longer segment."""
+    _, hi = _lib.supported_log2n(_lib.C128, direct=True)
+    if 2 * nperseg - 1 > (1 << hi):
+        raise ValueError(f"the device transform takes 2 ... 2^{hi - 1} samples per row, got {nperseg} (there is no CPU fallback)")
+
+
 def _welch_device(d, rows: int, n: int, ld: int, nperseg: int, out_f32: bool, dev: int) -> np.ndarray:
     """(rows, nperseg) fftshifted Welch estimate of the first ``n`` elements of every row of the device array ``d`` (rows ``ld`` apart)."""
     lay = _welch_layout(n, nperseg)
@@ -97,9 +104,7 @@ def _welch_device(d, rows: int, n: int, ld: int, nperseg: int, out_f32: bool, de
             _lib.api.ssfm_welch(dev, d.ptr + r0 * ld * itemsize, code, r1 - r0, n, ld, nperseg, scale, int(out_f32), out.ctypes.data + r0 * nperseg * out.itemsize)
         return out
     from .devices import _ChirpZ
-    _, hi = _lib.supported_log2n(_lib.C128, direct=True)
-    if 2 * nperseg - 1 > (1 << hi):
-        raise ValueError(f"the device transform takes 2 ... 2^{hi - 1} samples per row, got {nperseg} (there is no CPU fallback)")
+    _check_chirp_length(nperseg)
     nseg = lay["nseg"]
     total = rows * nseg
     M = 1 << max(8, (2 * nperseg - 2).bit_length())             # the chirp-z plan's line (devices._ChirpZ)
@@ -112,7 +117,9 @@ def _welch_device(d, rows: int, n: int, ld: int, nperseg: int, out_f32: bool, de
             _lib.api.ssfm_welch_frames(dev, d, code, rows, n, ld, nperseg, first, count, chunk, frames)
             eng.fourier(frames, False)
             _lib.api.ssfm_welch_accumulate(dev, frames, nperseg, rows, nseg, first, count, acc)
-    _lib.api.ssfm_welch_finish(dev, acc, rows, nperseg, scale / nseg, int(out_f32), out.ctypes.data)
+    for r0 in range(0, rows, _MAX_GRID_ROWS):                      # ssfm_welch_finish takes at most 65535 rows, as ssfm_welch does
+        r1 = min(rows, r0 + _MAX_GRID_ROWS)
+        _lib.api.ssfm_welch_finish(dev, acc.ptr + r0 * nperseg * 8, r1 - r0, nperseg, scale / nseg, int(out_f32), out.ctypes.data + r0 * nperseg * out.itemsize)
     return out
 
 
@@ -141,6 +148,8 @@ def _welch(x, fs, nperseg, n=None, device=None):
     if not _is_device(x) and n != ld:
         x = np.asarray(x)[..., :n]
         ld = n
+    if _welch_layout(n, nperseg)["route"] == 3:
+        _check_chirp_length(nperseg)                              # before anything is uploaded or allocated
     d = _on_device(x, dev)
     psd = _welch_device(d, rows, n, ld, nperseg, out_f32, dev)
     return f, psd.reshape(lead + (nperseg,))

@@ -4,19 +4,26 @@
     SSFM_MARGINS_FILE=raw.txt python -m pytest tests/test_signal_algebra_gpu.py -m gpu
     python tools/margins_digest.py raw.txt profiles/signal_ops_margins.txt
 
-A kind is the record's `what` with the size (`n=...`), the tap count and the fixture's case name taken out; its row carries the record with the
-largest measured / bound of that kind, and how many records it stands for."""
+A kind is the record's `what` with the size (`n=...`), the tap count, the chunk size (`chunk=...`) and the fixture's case name taken out; its row carries the record with the
+largest measured / bound of that kind, and how many records it stands for.  A third argument names a file whose text replaces the header's
+description (it follows the record count; further lines start with `#`)."""
 import collections
 import re
 import sys
 
 
 def kind(what):
-    what = re.sub(r"\b(n|taps)=\d+ ", "", what)
+    what = re.sub(r"\b(n|taps|chunk)=\d+ ", "", what)
     return re.sub(r"^(binary|reflected|scalar|pow|methods|filter|protocol)/\S+", lambda m: m.group(1) + " fixtures", what)
 
 
-def main(src, dst):
+HEAD = ("comparisons recorded by the GPU tests of the signal algebra on one MI355X, folded by tools/margins_digest.py: per kind of comparison,\n"
+        "# the record with the largest measured / bound.  [ulp]: max |d| / (2^-52 |want|), of the modulus for complex values; [rad]: absolute;\n"
+        "# [|d| / (...)]: elementwise against the stated product bound; otherwise max |d| / peak.  'numpy vs exact' rows are NumPy's own distance from\n"
+        "# the exact restatement of unwrap (their bound column is what the device is then allowed).  Comparisons held to NumPy's bits record nothing.\n")
+
+
+def main(src, dst, head=HEAD):
     rows, total = collections.OrderedDict(), 0
     for line in open(src):
         if line.startswith("#") or not line.strip():
@@ -31,10 +38,7 @@ def main(src, dst):
         best = (m, b, r, test.split("::")[-1]) if k not in rows or r > rows[k][2] else rows[k][:4]
         rows[k] = (*best, count)
     with open(dst, "w") as f:
-        f.write(f"# {total} comparisons recorded by the GPU tests of the signal algebra on one MI355X, folded by tools/margins_digest.py: per kind of comparison,\n"
-                "# the record with the largest measured / bound.  [ulp]: max |d| / (2^-52 |want|), of the modulus for complex values; [rad]: absolute;\n"
-                "# [|d| / (...)]: elementwise against the stated product bound; otherwise max |d| / peak.  'numpy vs exact' rows are NumPy's own distance from\n"
-                "# the exact restatement of unwrap (their bound column is what the device is then allowed).  Comparisons held to NumPy's bits record nothing.\n"
+        f.write(f"# {total} " + head +
                 "# kind | records | measured | bound | measured / bound | test of the worst record\n")
         for k, (m, b, r, t, count) in rows.items():
             f.write(f"{k} | {count} | {m:.3e} | {b:.3e} | {r:.3f} | {t}\n")
@@ -42,4 +46,4 @@ def main(src, dst):
 
 
 if __name__ == "__main__":
-    main(sys.argv[1], sys.argv[2])
+    main(sys.argv[1], sys.argv[2], *([open(sys.argv[3]).read()] if len(sys.argv) > 3 else []))
