@@ -501,6 +501,29 @@ SSFM_API int ssfm_device_sample(int device, const double* x, const double* noise
 /* *out = number of i < n with a[i] != b[i] (uint8 arrays). */
 SSFM_API int ssfm_device_count_diff(int device, const unsigned char* a, const unsigned char* b, int64_t n, int64_t* out);
 
+/* ---- lab.SYNC and lab.GET_EYE_v2 (csrc/sync.hip), the data-aided receiver of lab.py:92-273: DEVICE pointers, float64 samples, uint8 slots (nonzero
+ * counts as 1).  ssfm_load_template runs on the plan's stream, as the plan's other loads; the other three take no device number, as the
+ * signal algebra below: they run where their input lies (the device that owns `x`, or `bits` for the split, becomes the calling thread's device; a
+ * pointer that is not device memory is SSFM_ERR_INVALID before any launch), on that device's default stream, and have finished when they return.  No float atomics: two calls on the same input give the same bits. ----
+ * ssfm_load_template: the field of a complex128 plan of plan_n points <- the slots held `sps` samples each, tx[m] = bits[m / sps] (m < nbits sps <= plan_n),
+ * written time-reversed modulo plan_n: field[(plan_n - m) mod plan_n] = tx[m], zero elsewhere.  ssfm_table_from_field then leaves conj(fft(tx)) in a slot,
+ * and ssfm_apply_table on a record loaded with ssfm_load_padded leaves corr[k] = sum_m rx[k + m] tx[m] at field index k (lab.py:146). */
+SSFM_API int ssfm_load_template(ssfm_plan* plan, int64_t plan_n, const unsigned char* bits, int64_t nbits, int sps);
+/* ssfm_sync_peak: of the n <= 2^22 values x[i stride] (stride 1: a float64 array; 2: the real parts of complex128 values, e.g. a plan's field),
+ * out (HOST, >= 4) = {np.max, np.argmax, np.mean, np.std}: a NaN is the maximum, the first of equal values wins; the std is two-pass (the squared
+ * deviations about the mean, which is held inside [min, max]), so equal values give exactly 0 (lab.py:148-151). */
+SSFM_API int ssfm_sync_peak(const double* x, int64_t stride, int64_t n, double* out, int64_t n_out);
+/* ssfm_eye_levels_known: ssfm_eye_levels with the level of a sample taken from the slot that was sent: x holds n = nslots sps samples, sample i
+ * belongs to bits[i / sps] (nslots values), the central samples are those with i mod sps in [k_lo, k_hi).  The same state block (HOST, >= 64):
+ * mu / sd / n of either level, the KDE's argmin over linspace(mu0, mu1, npts) (lab.py:252-264). */
+SSFM_API int ssfm_eye_levels_known(const double* x, int64_t n, int64_t sps, int64_t k_lo, int64_t k_hi, const unsigned char* bits, int npts,
+                                   double* out, int64_t n_out);
+/* ssfm_eye_split_known: ones <- the samples of the slots sent as 1, zeros <- those sent as 0, whole slots of sps samples in their order
+ * (x[ref == 1], x[ref == 0] of lab.py:232-235); nslots sps <= 2^21.  The state block (HOST, >= 64) returns the slots of either level in its
+ * n1 / n0 entries.  ones = zeros = NULL: the counts alone (x is not read); else each must have room for its count times sps samples. */
+SSFM_API int ssfm_eye_split_known(const double* x, int64_t nslots, int64_t sps, const unsigned char* bits, double* ones, double* zeros,
+                                  double* out, int64_t n_out);
+
 /* ---- the PPM receiver (csrc/ppm.hip): DEVICE pointers, uint8 bits / slots (0 or 1), float64 samples.  M is a power of two, 2 ... 2^16
  * (the encoder takes any M >= 2), k = floor(log2 M); nsym < 2^31.  Every call runs on the default stream of `device` and has finished its
  * work when it returns. ----

@@ -92,6 +92,10 @@ SYMBOLS = {
     "ssfm_eye_levels": (_I, [_I, _VP, _I64, _I64, _I64, _I64, _D, _I, _VP, _I64]),
     "ssfm_device_sample": (_I, [_I, _VP, _VP, _I64, _I64, _I64, _D, _VP, _VP]),
     "ssfm_device_count_diff": (_I, [_I, _VP, _VP, _I64, C.POINTER(_I64)]),
+    "ssfm_load_template": (_I, [_VP, _I64, _VP, _I64, _I]),
+    "ssfm_sync_peak": (_I, [_VP, _I64, _I64, _VP, _I64]),
+    "ssfm_eye_levels_known": (_I, [_VP, _I64, _I64, _I64, _I64, _VP, _I, _VP, _I64]),
+    "ssfm_eye_split_known": (_I, [_VP, _I64, _I64, _VP, _VP, _VP, _VP, _I64]),
     "ssfm_ppm_encode": (_I, [_I, _VP, _I64, _I, _VP]),
     "ssfm_ppm_decode": (_I, [_I, _VP, _I64, _I, _VP, _I64, C.POINTER(_I64)]),
     "ssfm_ppm_decide": (_I, [_I, _VP, _VP, _I, _I64, _I64, _I64, _I, _I, _D, _VP, _VP, _VP]),
@@ -742,9 +746,13 @@ class Plan:
     def apply_table(self, slot: int):
         api.ssfm_apply_table(self._h, int(slot))
 
-    def load_padded(self, src: "DeviceArray"):
-        """field <- the float64 / complex128 device array ``src``, zero-padded to the plan length (batch 1)."""
-        api.ssfm_load_padded(self._h, self.n, src, int(src.dtype.kind == "c"), src.size)
+    def load_padded(self, src: "DeviceArray", count: int = None):
+        """field <- the float64 / complex128 device array ``src`` (its first ``count`` values), zero-padded to the plan length (batch 1)."""
+        api.ssfm_load_padded(self._h, self.n, src, int(src.dtype.kind == "c"), src.size if count is None else int(count))
+
+    def load_template(self, bits: "DeviceArray", sps: int):
+        """field <- device-resident slots (uint8) held ``sps`` samples each, time-reversed modulo the plan length (``ssfm_load_template``)."""
+        api.ssfm_load_template(self._h, self.n, bits, bits.size, int(sps))
 
     def load_symbols(self, sym: "DeviceArray", up: int):
         """field <- the float64 amplitudes ``sym`` zero-stuffed to ``up`` samples per symbol (sample at ``up // 2``)."""

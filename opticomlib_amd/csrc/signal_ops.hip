@@ -401,15 +401,7 @@ int finish(const char* what) {
 
 // These entry points take no device number: a signal is computed where it lies, so the device is the one that owns the signal's memory (and a
 // pointer that is not device memory is refused before anything is launched).  It becomes the calling thread's device.
-int device_of(const void* p, int* device) {
-    hipPointerAttribute_t attr;
-    if (hipPointerGetAttributes(&attr, p) != hipSuccess || attr.type != hipMemoryTypeDevice) {
-        (void)hipGetLastError();
-        return fail(SSFM_ERR_INVALID, "ssfm_signal_*: %p is not device memory", p);
-    }
-    *device = attr.device;
-    return use_device(attr.device);
-}
+int device_of(const void* p, int* device) { return ssfm::device_of(p, "ssfm_signal_*", device); }
 bool same_device(const void* p, int device) {
     hipPointerAttribute_t attr;
     if (hipPointerGetAttributes(&attr, p) != hipSuccess) { (void)hipGetLastError(); return false; }

@@ -97,6 +97,18 @@ inline int use_device(int device) {
     return SSFM_OK;
 }
 
+// The entry points that take no device number (a signal is computed where it lies): the device is the one that owns the memory at `p`, which becomes
+// the calling thread's device; a pointer that is not device memory is refused before anything is launched.  `who` names the caller in the message.
+inline int device_of(const void* p, const char* who, int* device) {
+    hipPointerAttribute_t attr;
+    if (hipPointerGetAttributes(&attr, p) != hipSuccess || attr.type != hipMemoryTypeDevice) {
+        (void)hipGetLastError();
+        return fail(SSFM_ERR_INVALID, "%s: %p is not device memory", who, p);
+    }
+    *device = attr.device;
+    return use_device(attr.device);
+}
+
 // Workgroups of 256 threads for a grid-stride loop over n items: one per 256 items, at least one, at most `cap`.  The cap is the call site's own:
 // where per-block partials are folded (eye, FBG, PSD) a different grid changes the order of the sums.
 inline unsigned grid_for(long long n, long long cap) {

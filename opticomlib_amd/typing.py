@@ -922,18 +922,33 @@ class optical_signal:
         return f"optical_signal(n_pol={self.n_pol}, size={self.size}, dtype={self._raw('signal').dtype}, noise={'NULL' if self._raw('noise') is NULL else 'array'}){where}"
 
 
+class _KnownSlots(_LazyArray):
+    """``eye.ones`` / ``eye.zeros``: a lazy array that only the eye of ``lab.GET_EYE_v2`` has (an ``AttributeError`` on any other eye)."""
+
+    def __get__(self, obj, objtype=None):
+        if obj is not None and self.slot not in obj.__dict__:
+            raise AttributeError(f"'eye' object has no attribute '{self.slot[1:]}'")
+        return super().__get__(obj, objtype)
+
+
 class eye:
     """Eye-diagram parameters: what ``GET_EYE`` returns, with the reference's attribute names (``typing.py`` class ``eye``; no ``plot``).
 
     ``y`` (the possibly resampled, rolled signal) stays on the GPU until it is read; ``t``, ``y_25_75``, ``y_top`` and ``y_bot`` are
-    formed from it on first access (NaN outside their masks, as in the reference)."""
+    formed from it on first access (NaN outside their masks, as in the reference).  The eye of ``lab.GET_EYE_v2`` also has ``ones`` and
+    ``zeros`` (the samples of the slots sent as 1 / as 0, on the GPU until they are read) and their slot grids ``t1`` / ``t0``."""
 
     y = _LazyArray()
+    ones = _KnownSlots()
+    zeros = _KnownSlots()
 
     def __init__(self, **kw):
         y = kw.pop("y", None)
+        known = {k: kw.pop(k) for k in ("ones", "zeros") if k in kw}
         self.__dict__.update(kw)
         self.y = y
+        for k, v in known.items():
+            setattr(self, k, v)
         self._cache = {}
 
     def _tgrid(self):
@@ -952,6 +967,22 @@ class eye:
         if "t" not in self._cache:
             self._cache["t"] = np.kron(np.ones(self._nslots // 2), self._tgrid())
         return self._cache["t"]
+
+    def _slot_grid(self, name, count):
+        """``t0`` / ``t1``: the grid of one slot tiled over the slots of that level (``lab.GET_EYE_v2`` only)."""
+        if count not in self.__dict__:
+            raise AttributeError(f"'eye' object has no attribute '{name}'")
+        if name not in self._cache:
+            self._cache[name] = np.kron(np.ones(self.__dict__[count]), np.linspace(-0.5, 0.5, self.sps, endpoint=False))
+        return self._cache[name]
+
+    @property
+    def t0(self):
+        return self._slot_grid("t0", "_n0")
+
+    @property
+    def t1(self):
+        return self._slot_grid("t1", "_n1")
 
     @property
     def y_25_75(self):
