@@ -55,6 +55,9 @@
  *     operators), :1476-1486 (real, imag),         **, real, imag, abs), ssfm_signal_slice ([]), ssfm_signal_reduce (power, max |.|, sum),
  *     :1599-1780 (conj, sum, abs, power,           ssfm_signal_phase (unwrap(angle(.))), ssfm_signal_pack / _split (filter: signal and noise as one
  *     normalize, phase, filter)                    complex field through the DAC's convolution)
+ *   typing.py:402-1009 (binary_sequence's          ssfm_bits_binary (& | ^ !=), ssfm_bits_not (~, flip), ssfm_bits_concat (+), ssfm_bits_tile (* n),
+ *     operators, ones, zeros, hamming_distance)    ssfm_bits_slice ([]), ssfm_bits_count (ones, zeros, an integer index; hamming_distance of equal
+ *                                                  lengths is ssfm_device_count_diff)
  *   (none: NumPy arrays are the reference's only   ssfm_device_alloc / _free / _copy / _convert / _add
  *     data format)                                 -- device-resident signals between calls
  *
@@ -643,6 +646,29 @@ SSFM_API int ssfm_signal_phase(int64_t rows, int64_t n, const void* signal, cons
  * field) back into two float64 arrays (`im` nullable: the real part alone). */
 SSFM_API int ssfm_signal_pack(const double* re, const double* im, int64_t n, void* out);
 SSFM_API int ssfm_signal_split(const void* src, int64_t n, double* re, double* im);
+
+/* The algebra of binary_sequence (typing.py:402-1009) on DEVICE sequences: one uint8 per bit.  A nonzero byte counts as 1 (as ssfm_ppm_* and
+ * ssfm_load_template read bits); every entry point writes exactly 0 or 1, so a result is a valid sequence whatever the input bytes were.
+ * Integers only.  As ssfm_signal_*: no device argument -- the work runs on the device that owns the first pointer (`a` / `src`; `out` for
+ * ssfm_bits_concat), which becomes the calling thread's device; a pointer that is not device memory, or one on another device, is
+ * SSFM_ERR_INVALID before any launch.  Default stream; each call has finished its work when it returns.  A length of 0 launches nothing and
+ * returns SSFM_OK (the pointers are not looked at).  `out` must not overlap an operand; neither operand nor result needs any alignment.
+ *
+ * ssfm_bits_binary: out[i] = a[i] OP b[i], i < n; len_a and len_b are n or 1 (the one bit for every index).  `!=` is SSFM_BITS_XOR. */
+enum { SSFM_BITS_AND = 0, SSFM_BITS_OR = 1, SSFM_BITS_XOR = 2 };
+SSFM_API int ssfm_bits_binary(int op, const unsigned char* a, int64_t len_a, const unsigned char* b, int64_t len_b, int64_t n, unsigned char* out);
+/* ssfm_bits_not: out[i] = !a[i], i < n (typing.py:763-766). */
+SSFM_API int ssfm_bits_not(const unsigned char* a, int64_t n, unsigned char* out);
+/* ssfm_bits_slice: out[i] = src[start + i step], i < count, of a sequence of n bits (typing.py:694-710); step may be negative, never 0; every index
+ * read must lie in [0, n).  step = 1 is a copy at an offset (16 bytes per lane), any other step a gather. */
+SSFM_API int ssfm_bits_slice(const unsigned char* src, int64_t n, int64_t start, int64_t step, int64_t count, unsigned char* out);
+/* ssfm_bits_tile: out (n reps bits) = the n bits of src, reps times (numpy.tile; typing.py:750-753). */
+SSFM_API int ssfm_bits_tile(const unsigned char* src, int64_t n, int64_t reps, unsigned char* out);
+/* ssfm_bits_concat: out (len_a + len_b bits) = a, then b (numpy.concatenate; typing.py:729-745).  Either length may be 0. */
+SSFM_API int ssfm_bits_concat(const unsigned char* a, int64_t len_a, const unsigned char* b, int64_t len_b, unsigned char* out);
+/* ssfm_bits_count: *ones (HOST) = the number of nonzero bytes among the n at a (typing.py:796-808).  Integer sums and one integer atomic per
+ * workgroup: exact, and the same number on every call. */
+SSFM_API int ssfm_bits_count(const unsigned char* a, int64_t n, int64_t* ones);
 
 #ifdef __cplusplus
 }

@@ -117,6 +117,12 @@ SYMBOLS = {
     "ssfm_signal_phase": (_I, [_I64, _I64, _VP, _VP, _I, _VP]),
     "ssfm_signal_pack": (_I, [_VP, _VP, _I64, _VP]),
     "ssfm_signal_split": (_I, [_VP, _I64, _VP, _VP]),
+    "ssfm_bits_binary": (_I, [_I, _VP, _I64, _VP, _I64, _I64, _VP]),
+    "ssfm_bits_not": (_I, [_VP, _I64, _VP]),
+    "ssfm_bits_slice": (_I, [_VP, _I64, _I64, _I64, _I64, _VP]),
+    "ssfm_bits_tile": (_I, [_VP, _I64, _I64, _VP]),
+    "ssfm_bits_concat": (_I, [_VP, _I64, _VP, _I64, _VP]),
+    "ssfm_bits_count": (_I, [_VP, _I64, C.POINTER(_I64)]),
 }
 
 
@@ -329,6 +335,8 @@ class DeviceArray:
         self.device = int(device)
         self.nbytes = int(np.prod(self.shape)) * self.dtype.itemsize
         self.ptr = 0
+        if self.nbytes == 0:                   # an empty array (an empty slice of a bit sequence) owns no memory; from_host, to_host, copy and astype
+            return                             # skip their calls for it, and an entry point handed its NULL pointer with a length above 0 refuses it
         p = _VP()
         api.ssfm_device_alloc(self.device, self.nbytes, C.byref(p))
         self.ptr = int(p.value)
@@ -369,19 +377,24 @@ class DeviceArray:
     def from_host(cls, a: np.ndarray, dtype=None, device: int = 0) -> "DeviceArray":
         a = np.ascontiguousarray(a, dtype=dtype)
         d = cls(a.shape, a.dtype, device)
+        if d.nbytes == 0:
+            return d
         api.ssfm_device_copy(d.device, d, _ptr(a), d.nbytes, COPY_H2D)
         TRANSFERS["h2d"] += 1
         return d
 
     def to_host(self) -> np.ndarray:
         out = host_empty(self.shape, self.dtype)
+        if self.nbytes == 0:
+            return out
         api.ssfm_device_copy(self.device, _ptr(out), self, self.nbytes, COPY_D2H)
         TRANSFERS["d2h"] += 1
         return out
 
     def copy(self) -> "DeviceArray":
         d = DeviceArray(self.shape, self.dtype, self.device)
-        api.ssfm_device_copy(self.device, d, self, self.nbytes, COPY_D2D)
+        if self.nbytes:
+            api.ssfm_device_copy(self.device, d, self, self.nbytes, COPY_D2D)
         return d
 
     def astype(self, dtype) -> "DeviceArray":
@@ -393,7 +406,8 @@ class DeviceArray:
         if self.dtype not in codes or dtype not in codes or codes[dtype] == 2:
             raise TypeError(f"DeviceArray.astype: {self.dtype} -> {dtype} is not supported")
         d = DeviceArray(self.shape, dtype, self.device)
-        api.ssfm_device_convert(self.device, self, codes[self.dtype], d, codes[dtype], self.size)
+        if self.size:
+            api.ssfm_device_convert(self.device, self, codes[self.dtype], d, codes[dtype], self.size)
         return d
 
     def __add__(self, other: "DeviceArray") -> "DeviceArray":
@@ -487,6 +501,57 @@ def prbs_device(order: int, length: int, seed: int, device: int = 0):
     last = C.c_uint32(0)
     api.ssfm_prbs(int(device), out, int(length), int(order), C.c_uint32(int(seed)), C.byref(last))
     return out, int(last.value)
+
+
+# -- the algebra of binary_sequence on uint8 device arrays (csrc/bits.hip): a nonzero byte is a 1, every result holds 0 / 1
+BITS_AND, BITS_OR, BITS_XOR = 0, 1, 2
+
+
+def bits_binary_device(op: int, a: DeviceArray, b: DeviceArray) -> DeviceArray:
+    """``a OP b`` bit by bit; the sizes are equal or one of them is 1."""
+    out = DeviceArray((max(a.size, b.size),), np.uint8, a.device)
+    api.ssfm_bits_binary(int(op), a, a.size, b, b.size, out.size, out)
+    return out
+
+
+def bits_not_device(a: DeviceArray) -> DeviceArray:
+    out = DeviceArray((a.size,), np.uint8, a.device)
+    api.ssfm_bits_not(a, a.size, out)
+    return out
+
+
+def bits_slice_device(a: DeviceArray, start: int, step: int, count: int) -> DeviceArray:
+    """``a[start + i step]``, ``i < count`` (every index inside the sequence)."""
+    out = DeviceArray((int(count),), np.uint8, a.device)
+    api.ssfm_bits_slice(a, a.size, int(start), int(step), int(count), out)
+    return out
+
+
+def bits_tile_device(a: DeviceArray, reps: int) -> DeviceArray:
+    out = DeviceArray((a.size * int(reps),), np.uint8, a.device)
+    api.ssfm_bits_tile(a, a.size, int(reps), out)
+    return out
+
+
+def bits_concat_device(a: DeviceArray, b: DeviceArray) -> DeviceArray:
+    out = DeviceArray((a.size + b.size,), np.uint8, a.device)
+    api.ssfm_bits_concat(a, a.size, b, b.size, out)
+    return out
+
+
+def bits_count_device(a: DeviceArray, start: int = 0, count: int = None) -> int:
+    """The number of ones among ``count`` bits from ``start`` on (all of them by default): one integer comes back, not the sequence."""
+    count = a.size - start if count is None else int(count)
+    ones = _I64(0)
+    api.ssfm_bits_count(C.c_void_p(a.ptr + int(start)) if count else None, count, C.byref(ones))
+    return int(ones.value)
+
+
+def count_diff_device(a: DeviceArray, b: DeviceArray) -> int:
+    """The number of positions at which two uint8 device arrays of one size differ (``ssfm_device_count_diff``)."""
+    diff = _I64(0)
+    api.ssfm_device_count_diff(a.device, a, b, a.size, C.byref(diff))
+    return int(diff.value)
 
 
 def real_device(a: DeviceArray) -> DeviceArray:

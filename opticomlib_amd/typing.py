@@ -135,9 +135,25 @@ class _LazyArray:
 
 
 class binary_sequence:
-    """Bit sequence container: the slice of reference ``typing.py:402-1020`` that ``PRBS`` returns and a DAC
-    consumes -- ``.data`` (uint8 0/1), ``.size``, ``len()``, ``.to_numpy()``, comparison with array-likes.
-    ``PRBS`` leaves its bits in GPU memory (``from_device``); ``.data`` downloads them on first access."""
+    """Bit sequence (uint8 0 / 1) with the algebra of the reference's class (``typing.py:402-1009``): ``~``, ``&``, ``|``, ``^``, ``!=`` (a
+    ``binary_sequence`` mask of the differences), ``+`` (concatenation, either order), ``*`` (an ``int`` above 1 tiles, anything else is ``&``),
+    ``[]``, ``flip``, ``hamming_distance``, ``dac``, ``prbs``, ``ones``, ``zeros``, ``size``, ``sizeof``, ``print``, ``to_numpy``.  The other
+    operand may be a sequence, a string (``'1010'``), a list, an array or a scalar: it goes through ``binary_sequence(other)``, so a value other
+    than 0 / 1 is the constructor's ``ValueError``.  The lengths are equal or one of them is 1 (NumPy's broadcast); anything else is a ``ValueError``.
+    ``ndarray + a`` and ``ndarray * a`` come to ``a``'s own operators through ``__array_ufunc__``.
+
+    Residency: ``PRBS``, ``x > thr``, ``SAMPLER`` and the receivers leave their bits in GPU memory (``from_device``).  An operation on such a
+    sequence is computed there by the HIP kernels of ``csrc/bits.hip`` and its result lies there too; a host operand is uploaded once, two
+    sequences on different GPUs are a ``ValueError``.  ``ones``, ``zeros``, ``hamming_distance`` and an integer index bring one integer back and
+    leave the sequence where it is; a slice (any step, empty results, bounds clipped as Python clips them) stays on the GPU; an index of another
+    kind (a mask, an index array) materialises on the host.  ``dac(h)`` uploads nothing but ``h``.  An operation between host-only sequences is
+    NumPy on the host, as in the reference, and loads no device.  ``.data`` downloads the bits on first access and the object is a host sequence
+    from then on.
+
+    ``==`` returns a host bool array (callers write ``(a == b).all()``), not the reference's mask; ``!=`` returns the mask.
+
+    Not provided: ``plot``, the reference's ``__getattr__`` delegation to ``ndarray`` and ``__array_function__``.  A NumPy ufunc other than the
+    two reflected operators sees the materialised bits and returns NumPy's own result."""
 
     data = _LazyArray()
 
@@ -169,6 +185,7 @@ class binary_sequence:
         self.data = d.astype(np.uint8)
         self.execution_time = 0.0
 
+    # -- metadata (no transfer)
     @property
     def size(self) -> int:
         return int(self._raw().size)
@@ -178,34 +195,216 @@ class binary_sequence:
         return binary_sequence
 
     @property
+    def on_device(self) -> bool:
+        """True while the bits live in GPU memory only (no host copy has been asked for)."""
+        return _is_device(self._raw())
+
+    @property
+    def sizeof(self) -> int:
+        """Bytes the bits occupy, on the host or on the GPU: one per bit."""
+        return self.size * np.dtype(np.uint8).itemsize
+
+    def __len__(self):
+        return self.size
+
+    # -- one integer back from the GPU: the sequence stays where it is
+    @property
     def ones(self) -> int:
-        return int(self.data.sum())
+        if self.on_device:
+            from . import _lib
+            return _lib.bits_count_device(self._raw())
+        return int(np.count_nonzero(self.data))
 
     @property
     def zeros(self) -> int:
         return self.size - self.ones
 
-    def __len__(self):
-        return self.size
+    def _host(self) -> np.ndarray:
+        """The bits as a host array; a device sequence is read, not converted."""
+        raw = self._raw()
+        return raw.to_host() if _is_device(raw) else raw
 
-    def __getitem__(self, key):
-        r = self.data[key]
-        return binary_sequence(r) if isinstance(r, np.ndarray) else int(r)
-
-    def __eq__(self, other):
-        other = other.data if isinstance(other, binary_sequence) else np.asarray(other)
-        return self.data == other
+    def __iter__(self):
+        return iter(self._host().tolist())
 
     def __array__(self, dtype=None, copy=None):
         return self.data if dtype is None else self.data.astype(dtype)
 
-    def to_numpy(self) -> np.ndarray:
-        return self.data
+    def to_numpy(self, dtype=None) -> np.ndarray:
+        return self.data if dtype is None else np.array(self.data, dtype=dtype)
 
     def __repr__(self):
         if _is_device(self._raw()):
             return f"binary_sequence(size={self.size}, on GPU {self._raw().device})"
         return f"binary_sequence({np.array2string(self.data, threshold=20)})"
+
+    def __str__(self, title=None):
+        title = 3 * "*" + f"    {self.__class__.__name__ if title is None else title}    " + 3 * "*"
+        sub = len(title) * "-"
+        where = f"on GPU {self._raw().device}" if self.on_device else np.array2string(self.data, threshold=100)
+        return (f"\n{sub}\n{title}\n{sub}\n\tdata  :  {where} (shape: {(self.size,)})\n\tones  :  {self.ones}\n\tzeros :  {self.zeros}\n\t"
+                f"size  :  {self.sizeof} bytes\n\ttime  :  {self.execution_time:.3g} s\n")
+
+    def print(self, msg=None):
+        """Print the sequence's parameters under the title ``msg``; returns ``self``."""
+        print(self.__str__(msg))
+        return self
+
+    # -- operands: where they lie, and the one upload of a host operand
+    def _pair(self, other):
+        """``(other as a sequence, the GPU the operation runs on or None)``; the lengths are equal or one of them is 1."""
+        o = other if isinstance(other, binary_sequence) else binary_sequence(other)
+        devs = {x._raw().device for x in (self, o) if x.on_device}
+        if len(devs) > 1:
+            raise ValueError(f"Can't operate binary_sequences that lie on different GPUs {sorted(devs)}: move one of them first")
+        return o, (devs.pop() if devs else None)
+
+    def _check_lengths(self, o):
+        if self.size != o.size and 1 not in (self.size, o.size):
+            raise ValueError(f"operands could not be broadcast together with shapes ({self.size},) ({o.size},)")
+
+    def _on(self, dev):
+        """The bits as a uint8 DeviceArray on GPU ``dev``."""
+        if self.on_device:
+            return self._raw()
+        from . import _lib
+        return _lib.DeviceArray.from_host(self.data, np.uint8, dev)
+
+    def _logic(self, op, other):
+        """``op``: 'and', 'or' or 'xor' between this sequence and ``other``, where the operands lie."""
+        o, dev = self._pair(other)
+        self._check_lengths(o)
+        if dev is None:
+            a, b = self.data, o.data
+            return binary_sequence(a & b if op == "and" else (a | b if op == "or" else a ^ b))
+        from . import _lib
+        if 0 in (self.size, o.size):                            # (0,) against (0,) or (1,) is (0,), as NumPy broadcasts
+            return binary_sequence.from_device(_lib.DeviceArray((0,), np.uint8, dev))
+        code = {"and": _lib.BITS_AND, "or": _lib.BITS_OR, "xor": _lib.BITS_XOR}[op]
+        return binary_sequence.from_device(_lib.bits_binary_device(code, self._on(dev), o._on(dev)))
+
+    def _concat(self, other, reflected):
+        o, dev = self._pair(other)
+        first, second = (o, self) if reflected else (self, o)
+        if dev is None:
+            return binary_sequence(np.concatenate((first.data, second.data)))
+        from . import _lib
+        return binary_sequence.from_device(_lib.bits_concat_device(first._on(dev), second._on(dev)))
+
+    # -- operators (reference typing.py:694-793)
+    def __invert__(self):
+        if self.on_device:
+            from . import _lib
+            return binary_sequence.from_device(_lib.bits_not_device(self._raw()))
+        return binary_sequence(~self.data.astype(bool))
+
+    def __and__(self, other):
+        return self._logic("and", other)
+
+    __rand__ = __and__
+
+    def __or__(self, other):
+        return self._logic("or", other)
+
+    __ror__ = __or__
+
+    def __xor__(self, other):
+        return self._logic("xor", other)
+
+    __rxor__ = __xor__
+
+    def __ne__(self, other):
+        """The mask of the positions that differ, as a ``binary_sequence`` (``hamming_distance`` is its sum).  ``==`` is not its mirror image
+        here: it keeps returning a host bool array."""
+        return self._logic("xor", other)
+
+    def __eq__(self, other):
+        """A host bool array (``(a == b).all()``); a device sequence is downloaded for it."""
+        other = other.data if isinstance(other, binary_sequence) else np.asarray(other)
+        return self.data == other
+
+    def __add__(self, other):
+        return self._concat(other, False)
+
+    def __radd__(self, other):
+        return self._concat(other, True)
+
+    def __mul__(self, other):
+        """An ``int`` above 1 repeats the sequence that many times; anything else (``0``, ``1``, ``True``, a sequence, an array) is ``&``
+        with ``binary_sequence(other)``, so ``* 2.0`` and ``* -1`` are the constructor's ``ValueError`` (reference ``typing.py:747-761``)."""
+        if isinstance(other, int) and other > 1:
+            if self.on_device:
+                from . import _lib
+                return binary_sequence.from_device(_lib.bits_tile_device(self._raw(), other))
+            return binary_sequence(np.tile(self.data, other))
+        return self._logic("and", other)
+
+    __rmul__ = __mul__
+
+    def __getitem__(self, key):
+        """An ``int``: the bit as a Python ``int``; a slice: a new sequence (on the GPU for a device sequence); any other index NumPy takes:
+        the host array's answer."""
+        raw = self._raw()
+        if _is_device(raw) and isinstance(key, (int, np.integer, slice)) and not isinstance(key, (bool, np.bool_)):
+            from . import _lib
+            if isinstance(key, slice):
+                start, stop, step = key.indices(raw.size)
+                return binary_sequence.from_device(_lib.bits_slice_device(raw, start, step, len(range(start, stop, step))))
+            if not -raw.size <= key < raw.size:
+                raise IndexError(f"index {key} is out of bounds for axis 0 with size {raw.size}")
+            return _lib.bits_count_device(raw, int(key) % raw.size, 1)
+        r = self.data[key]
+        return binary_sequence(r) if isinstance(r, np.ndarray) else int(r)
+
+    def __array_ufunc__(self, ufunc, method, *inputs, **kwargs):
+        """``ndarray + a`` is ``a.__radd__(ndarray)`` and ``ndarray * a`` is ``a.__mul__(ndarray)`` (reference ``typing.py:606-614``); any
+        other ufunc sees the materialised bits and its result comes back as NumPy made it."""
+        if method == "__call__" and not kwargs.get("out") and len(inputs) == 2 and isinstance(inputs[1], binary_sequence):
+            if ufunc is np.add:
+                return inputs[1].__radd__(inputs[0])
+            if ufunc is np.multiply:
+                return inputs[1].__mul__(inputs[0])
+        args = [a._host() if isinstance(a, binary_sequence) else a for a in inputs]
+        return getattr(ufunc, method)(*args, **kwargs)
+
+    # -- methods (reference typing.py:832-984)
+    @staticmethod
+    def prbs(order: int, len: int = None, seed: int = None, return_seed: bool = False):
+        """Pseudo-random binary sequence: :func:`opticomlib_amd.devices.PRBS` (generated on the GPU, where it stays)."""
+        from .devices import PRBS
+        return PRBS(order, len, seed, return_seed)
+
+    def flip(self):
+        """``~self``."""
+        return ~self
+
+    def hamming_distance(self, other) -> int:
+        """The number of positions at which the two sequences differ (lengths equal, or one of them 1), as a Python ``int``."""
+        o, dev = self._pair(other)
+        self._check_lengths(o)
+        if dev is None:
+            return int(np.count_nonzero(self.data != o.data))
+        if self.size != o.size:                                 # one bit against n: the ones, or the zeros, of the longer sequence
+            one, many = (self, o) if self.size == 1 else (o, self)
+            return many.zeros if one[0] else many.ones
+        if self.size == 0:
+            return 0
+        from . import _lib
+        return _lib.count_diff_device(self._on(dev), o._on(dev))
+
+    def dac(self, h):
+        """``electrical_signal(upfir(bits, h, up=gv.sps))``: the bits held at offset ``sps // 2`` of ``gv.sps`` samples each, convolved with the
+        impulse response ``h`` (``mode='same'``).  On the GPU for a device sequence (nothing but ``h`` is uploaded)."""
+        if self.on_device:
+            from . import devices
+            raw = self._raw()
+            if raw.size == 0:                                   # (what the constructor says to the host path's empty convolution)
+                raise ValueError(f"Signal must be scalar or 1D array for electrical_signal, invalid shape {(0,)}")
+            return electrical_signal.from_device(devices._upfir_device(raw, h, gv.sps, raw.device))
+        import scipy.signal as sg
+        xu = np.zeros(self.size * gv.sps)
+        xu[gv.sps // 2::gv.sps] = self.data
+        return electrical_signal(sg.fftconvolve(xu, h, mode="same"))
 
 
 class electrical_signal:
