@@ -424,7 +424,10 @@ class DeviceArray:
 
 def randn_device(shape, std: float, seed: int, stream: int, dtype=np.float64, device: int = 0) -> DeviceArray:
     """``std * N(0, 1)`` from the library's Philox4x32-10 generator (``ssfm_device_randn``).  For a complex dtype
-    real and imaginary parts are independent, each of standard deviation ``std``."""
+    real and imaginary parts are independent, each of standard deviation ``std``.  The kernel writes float64 values, so only float64
+    and complex128 are taken: any other dtype raises ``TypeError`` before a buffer is allocated (it would be written past its end)."""
+    if np.dtype(dtype) not in (np.dtype(np.float64), np.dtype(np.complex128)):
+        raise TypeError(f"randn_device writes float64 values: dtype must be float64 or complex128, not {np.dtype(dtype)}")
     out = DeviceArray(shape, dtype, device)
     count = out.size * (2 if out.dtype.kind == "c" else 1)
     api.ssfm_device_randn(out.device, out, count, int(seed) & (2 ** 64 - 1), int(stream) & (2 ** 64 - 1), 0.0, float(std))

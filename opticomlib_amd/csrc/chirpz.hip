@@ -587,7 +587,9 @@ extern "C" int ssfm_load_pulse(ssfm_plan* plan, int64_t plan_n, int kind, int64_
 
 // ---------------------------------------------------------------------------------- the chirp itself
 // c_m = exp(-i pi m^2 / n): the phase is reduced exactly in integers (m^2 mod 2n) and taken with sincospi, so
-// the chirp carries no argument-rounding error at all.  k_chirp: out[m] = c_m or conj(c_m), m < n.  k_chirp_kernel:
+// the argument never grows with m.  What remains is the one rounding of the quotient r / n in [0, 2): up to 2^-53 of
+// the argument, pi 2^-53 of the value (measured over n = 2^21 + 1: 3.3 x 2^-53, sincospi's own error included).
+// k_chirp: out[m] = c_m or conj(c_m), m < n.  k_chirp_kernel:
 // the convolution kernel of Bluestein's identity in the plan's field (row 0, length M): v[m] = v[M - m] = conj(c_m)
 // (which = 0: forward transform) or c_m (which = 1: inverse), zero elsewhere; ssfm_table_from_field turns it into
 // the resident transfer function of a slot -- no host transform, no upload.

@@ -270,7 +270,8 @@ extern "C" int ssfm_device_mem_info(int device, size_t* free_bytes, size_t* tota
 // the host mirror reproduces those draws on the host when asked for seed-for-seed parity.  For Monte-Carlo runs
 // that only need the statistics, this is the documented device generator: Philox4x32-10 (Salmon et al., SC'11)
 // with key = the 64-bit seed and counter = (pair index, stream); one call yields 128 random bits = two 53-bit
-// uniforms u1, u2 in (0, 1) = one Box-Muller pair  sqrt(-2 ln u1) * (cos, sin)(2 pi u2).  Element 2p and 2p+1 of
+// uniforms u1, u2 in (0, 1] = one Box-Muller pair  sqrt(-2 ln u1) * (cos, sin)(2 pi u2)  (the largest 53-bit integer
+// + 0.5 rounds up to 2^53: u = 1 exactly, which only makes r = 0 or the angle a whole turn).  Element 2p and 2p+1 of
 // the output come from pair p, so a buffer's content depends only on (seed, stream), not on the launch shape.
 namespace {
 
