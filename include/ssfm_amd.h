@@ -55,6 +55,9 @@
  *     operators), :1476-1486 (real, imag),         **, real, imag, abs), ssfm_signal_slice ([]), ssfm_signal_reduce (power, max |.|, sum),
  *     :1599-1780 (conj, sum, abs, power,           ssfm_signal_phase (unwrap(angle(.))), ssfm_signal_pack / _split (filter: signal and noise as one
  *     normalize, phase, filter)                    complex field through the DAC's convolution)
+ *   typing.py:1308-1419 and :2261-2305             ssfm_field_binary (+ - * == of (N,) and (2, N) fields that broadcast), ssfm_field_unary (the pointwise
+ *     (optical_signal: the inherited operators     operations; complex64: neg, conj, /), ssfm_field_slice (column slices, a row, a row's slice, an element),
+ *     and its own __getitem__)                     ssfm_field_reduce (power, max |.|, sum of every row in one launch)
  *   typing.py:402-1009 (binary_sequence's          ssfm_bits_binary (& | ^ !=), ssfm_bits_not (~, flip), ssfm_bits_concat (+), ssfm_bits_tile (* n),
  *     operators, ones, zeros, hamming_distance)    ssfm_bits_slice ([]), ssfm_bits_count (ones, zeros, an integer index; hamming_distance of equal
  *                                                  lengths is ssfm_device_count_diff)
@@ -646,6 +649,32 @@ SSFM_API int ssfm_signal_phase(int64_t rows, int64_t n, const void* signal, cons
  * field) back into two float64 arrays (`im` nullable: the real part alone). */
 SSFM_API int ssfm_signal_pack(const double* re, const double* im, int64_t n, void* out);
 SSFM_API int ssfm_signal_split(const void* src, int64_t n, double* re, double* im);
+
+/* The same algebra for optical_signal (typing.py:1308-1419 inherited, :2261-2305 its own __getitem__) on DEVICE fields: C-contiguous (rows, n)
+ * arrays with rows = 1 or 2 (row 1 starts n values after row 0), of `dtype` SSFM_F64_REAL (float64), SSFM_C128 or SSFM_C64.  Every array of a call
+ * has that one type (ssfm_device_convert widens an operand first: exact) and starts on a 16-byte boundary.  complex64 is computed in single
+ * precision; the file is compiled without contraction, so + - neg conj [] are NumPy's bits in every type.  Conventions as ssfm_signal_*: no device
+ * argument (the device that owns `s1` / `signal`), host memory or a second device is SSFM_ERR_INVALID before any launch, default stream, finished
+ * on return, the same bits on every call.
+ *
+ * ssfm_field_binary: the result is (rows, n); operand k is (rows_k, len_k) with rows_k in {1, rows} and len_k in {1, n} -- one row serves both
+ * rows, one value a whole row (NumPy's broadcast of (N,), (2, N), (2, 1) and (1,)) -- or, with s2 = NULL, the scalar re2 + j im2.  At least one
+ * operand has `rows` rows and one has n columns.  op: SSFM_SIGNAL_ADD, _SUB, _RSUB, _MUL with the signal / noise rules of ssfm_signal_binary, or
+ * SSFM_SIGNAL_EQ (out_signal: rows x n uint8).  out_noise is needed exactly when n1 or n2 is given (not for _EQ); a noise broadcasts as its signal. */
+SSFM_API int ssfm_field_binary(int op, int dtype, int64_t rows, int64_t n, const void* s1, const void* n1, int64_t rows1, int64_t len1, const void* s2,
+                               const void* n2, int64_t rows2, int64_t len2, double re2, double im2, void* out_signal, void* out_noise);
+/* ssfm_field_unary: the operations of ssfm_signal_unary on every value of the field.  SSFM_F64_REAL and SSFM_C128: all of them (the rows of a
+ * contiguous field are one run of rows x n values).  SSFM_C64: SSFM_SIGNAL_NEG, _CONJ and _DIV (NumPy's complex64 quotient), in single precision;
+ * any other op is SSFM_ERR_UNSUPPORTED -- the caller widens the field, computes in double precision and rounds once. */
+SSFM_API int ssfm_field_unary(int op, int dtype, int64_t rows, int64_t n, const void* signal, const void* noise, double p_re, double p_im, int p_complex,
+                              void* out_signal, void* out_noise);
+/* ssfm_field_slice: out (nrows, count) = in[row0 + r][start + i step] of signal and noise in one launch (typing.py:2261-2305: a column slice of all
+ * rows, one row, one row's slice, one element); step may be negative, never 0; every row and column read must lie inside the field. */
+SSFM_API int ssfm_field_slice(int dtype, int64_t rows, int64_t n, const void* signal, const void* noise, int64_t row0, int64_t nrows, int64_t start, int64_t step,
+                              int64_t count, void* out_signal, void* out_noise);
+/* ssfm_field_reduce (float64 / complex128; a complex64 field is widened first), results on the HOST, two per row in one launch: out[2 r] and
+ * out[2 r + 1] are what ssfm_signal_reduce's out[0] and out[1] are for row r (SSFM_SIGNAL_POWER, _MAXABS, _SUM). */
+SSFM_API int ssfm_field_reduce(int kind, int64_t rows, int64_t n, const void* signal, const void* noise, int is_complex, double* out);
 
 /* The algebra of binary_sequence (typing.py:402-1009) on DEVICE sequences: one uint8 per bit.  A nonzero byte counts as 1 (as ssfm_ppm_* and
  * ssfm_load_template read bits); every entry point writes exactly 0 or 1, so a result is a valid sequence whatever the input bytes were.

@@ -117,6 +117,10 @@ SYMBOLS = {
     "ssfm_signal_phase": (_I, [_I64, _I64, _VP, _VP, _I, _VP]),
     "ssfm_signal_pack": (_I, [_VP, _VP, _I64, _VP]),
     "ssfm_signal_split": (_I, [_VP, _I64, _VP, _VP]),
+    "ssfm_field_binary": (_I, [_I, _I, _I64, _I64, _VP, _VP, _I64, _I64, _VP, _VP, _I64, _I64, _D, _D, _VP, _VP]),
+    "ssfm_field_unary": (_I, [_I, _I, _I64, _I64, _VP, _VP, _D, _D, _I, _VP, _VP]),
+    "ssfm_field_slice": (_I, [_I, _I64, _I64, _VP, _VP, _I64, _I64, _I64, _I64, _I64, _VP, _VP]),
+    "ssfm_field_reduce": (_I, [_I, _I64, _I64, _VP, _VP, _I, C.POINTER(_D)]),
     "ssfm_bits_binary": (_I, [_I, _VP, _I64, _VP, _I64, _I64, _VP]),
     "ssfm_bits_not": (_I, [_VP, _I64, _VP]),
     "ssfm_bits_slice": (_I, [_VP, _I64, _I64, _I64, _I64, _VP]),

@@ -1,6 +1,8 @@
 // signal_ops.hip -- the algebra of electrical_signal (reference typing.py:1216-1780) on device-resident signals: the operators between two signals
 // or a signal and a scalar with the reference's signal / noise rules in one pass, the unary and scalar operations, comparison, slicing, the
 // reductions behind power / normalize / sum, unwrap(angle(.)) and the two pointwise ends of filter().  float64 and complex128, (rows, n) with rows = 1.
+// The ssfm_field_* entry points at the end are the same algebra for optical_signal (typing.py:2103-2320): rows = 1 or 2, operands that broadcast
+// along either axis, and complex64 beside the two double-precision types.
 //
 // All of them are bandwidth-bound streaming kernels: 16 bytes per lane and access (a complex128 value, or two float64 values), a grid of at most
 // 256 CUs x 8 workgroups with a grid-stride loop, wavefront shuffles and four LDS words per workgroup for the reductions.  The whole file is
@@ -22,23 +24,30 @@ constexpr long long kGridCap = 2048;        // 256 CUs x 8 workgroups
 
 struct cd { double re, im; };               // one complex128 value
 struct r2 { double x, y; };                 // two neighbouring float64 values: the 16-byte unit of the real kernels
+struct cf { float re, im; };                // one complex64 value (the field kernels)
 
 __device__ __forceinline__ cd operator+(cd a, cd b) { return {a.re + b.re, a.im + b.im}; }
 __device__ __forceinline__ cd operator-(cd a) { return {-a.re, -a.im}; }
 __device__ __forceinline__ cd operator*(cd a, cd b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
+__device__ __forceinline__ cf operator+(cf a, cf b) { return {a.re + b.re, a.im + b.im}; }
+__device__ __forceinline__ cf operator-(cf a) { return {-a.re, -a.im}; }
+__device__ __forceinline__ cf operator*(cf a, cf b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
 __device__ __forceinline__ r2 operator+(r2 a, r2 b) { return {a.x + b.x, a.y + b.y}; }
 __device__ __forceinline__ r2 operator-(r2 a) { return {-a.x, -a.y}; }
 __device__ __forceinline__ r2 operator*(r2 a, r2 b) { return {a.x * b.x, a.y * b.y}; }
 
-// NumPy's complex quotient (Smith's method, the loop behind complex128 / complex128)
-__device__ __forceinline__ cd cdiv(cd a, cd b) {
-    const double br = fabs(b.re), bi = fabs(b.im);
+// NumPy's complex quotient (Smith's method, the loop behind complex128 / complex128 and complex64 / complex64), in the precision of C
+__device__ __forceinline__ double absr(double v) { return fabs(v); }
+__device__ __forceinline__ float absr(float v) { return fabsf(v); }
+template <typename C> __device__ __forceinline__ C cdiv(C a, C b) {
+    using R = decltype(a.re);
+    const R br = absr(b.re), bi = absr(b.im);
     if (br >= bi) {
-        if (br == 0.0 && bi == 0.0) return {a.re / br, a.im / br};
-        const double rat = b.im / b.re, scl = 1.0 / (b.re + b.im * rat);
+        if (br == R(0) && bi == R(0)) return {a.re / br, a.im / br};
+        const R rat = b.im / b.re, scl = R(1) / (b.re + b.im * rat);
         return {(a.re + a.im * rat) * scl, (a.im - a.re * rat) * scl};
     }
-    const double rat = b.re / b.im, scl = 1.0 / (b.im + b.re * rat);
+    const R rat = b.re / b.im, scl = R(1) / (b.im + b.re * rat);
     return {(a.re * rat + a.im) * scl, (a.im * rat - a.re) * scl};
 }
 
@@ -85,6 +94,7 @@ __device__ __forceinline__ bool eq(double a, double b) { return a == b; }
 // NumPy orders complex numbers by real part, then imaginary part
 __device__ __forceinline__ bool gt(cd a, cd b) { return (a.re > b.re && !isnan(a.im) && !isnan(b.im)) || (a.re == b.re && a.im > b.im); }
 __device__ __forceinline__ bool eq(cd a, cd b) { return a.re == b.re && a.im == b.im; }
+__device__ __forceinline__ bool eq(cf a, cf b) { return a.re == b.re && a.im == b.im; }
 
 // ---------------------------------------------------------------------------------------------- binary operations
 // typing.py:1308-1348 (+, -, *), :1378-1398 (>, ==).  `h1` / `h2`: the operand has noise.  A sum with an absent noise is the other term and a
@@ -308,8 +318,10 @@ __global__ __launch_bounds__(256) void k_signal_slice(const T* __restrict__ s, c
 // device_mem.hip).  The grid depends on n alone and the host folds the partials in order, so a result is the same bits every time.
 __device__ __forceinline__ double fold_max(double acc, double v) { return (v > acc || isnan(v)) ? v : acc; }        // a NaN stays, as in numpy.max
 
-__global__ __launch_bounds__(256) void k_signal_reduce(int kind, int cplx, const double* __restrict__ s, const double* __restrict__ nz, long long n,
-                                                       double* __restrict__ partial) {
+// One row: `s` (and `nz`) of n values.  A float64 row that starts off 16 bytes (row 1 of a (2, n) field with odd n) gives its first value to
+// the lane that also takes the odd last one, so that every pair is read from an aligned address.
+__device__ __forceinline__ void reduce_row(int kind, int cplx, const double* __restrict__ s, const double* __restrict__ nz, long long n,
+                                           double* __restrict__ partial) {
     double a0 = 0.0, a1 = 0.0;
     const long long first = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
     auto take = [&](double re, double im) {
@@ -324,13 +336,17 @@ __global__ __launch_bounds__(256) void k_signal_reduce(int kind, int cplx, const
             take(v.re, v.im);
         }
     } else {
-        for (long long i = first; i < (n >> 1); i += stride) {
-            r2 v = load<r2, false>(s, i, n);
-            if (nz) v = v + load<r2, false>(nz, i, n);
+        const long long head = (reinterpret_cast<uintptr_t>(s) & 15) ? 1 : 0;
+        for (long long i = first; i < ((n - head) >> 1); i += stride) {
+            r2 v = load<r2, false>(s + head, i, 2);
+            if (nz) v = v + load<r2, false>(nz + head, i, 2);
             take(v.x, 0.0);
             take(v.y, 0.0);
         }
-        if ((n & 1) && first == 0) take(nz ? s[n - 1] + nz[n - 1] : s[n - 1], 0.0);
+        if (first == 0) {
+            if (head) take(nz ? s[0] + nz[0] : s[0], 0.0);
+            if ((n - head) & 1) take(nz ? s[n - 1] + nz[n - 1] : s[n - 1], 0.0);
+        }
     }
     const bool is_max = kind == SSFM_SIGNAL_MAXABS;
     for (int o = 32; o > 0; o >>= 1) {
@@ -345,6 +361,16 @@ __global__ __launch_bounds__(256) void k_signal_reduce(int kind, int cplx, const
         partial[2 * blockIdx.x] = is_max ? fold_max(fold_max(w[0], w[1]), fold_max(w[2], w[3])) : w[0] + w[1] + w[2] + w[3];
         partial[2 * blockIdx.x + 1] = w[4] + w[5] + w[6] + w[7];
     }
+}
+__global__ __launch_bounds__(256) void k_signal_reduce(int kind, int cplx, const double* __restrict__ s, const double* __restrict__ nz, long long n,
+                                                       double* __restrict__ partial) {
+    reduce_row(kind, cplx, s, nz, n, partial);
+}
+// blockIdx.y: the row of a (rows, n) field; its partials follow those of the rows before it
+__global__ __launch_bounds__(256) void k_field_reduce(int kind, int cplx, const double* __restrict__ s, const double* __restrict__ nz, long long n,
+                                                      double* __restrict__ partial) {
+    const long long off = (long long)blockIdx.y * n * (cplx ? 2 : 1);
+    reduce_row(kind, cplx, s + off, nz ? nz + off : nullptr, n, partial + 2ll * blockIdx.y * gridDim.x);
 }
 
 // ---------------------------------------------------------------------------------------------- phase
@@ -392,6 +418,141 @@ __global__ __launch_bounds__(256) void k_signal_split(const double2* __restrict_
     }
 }
 
+// ---------------------------------------------------------------------------------------------- optical fields
+// (rows, n) arrays, rows = 1 or 2, C-contiguous: row 1 starts n values after row 0 (typing.py:2103-2320).  T is double, cd or cf.  An operand
+// has its own (rows, len) with rows in {1, the result's} and len in {1, n}: a single row serves both rows, a single value a whole row.
+// cd: one value per lane and pass.  double and cf: two (16 bytes).  For odd n row 1 of those starts 8 bytes off a 16-byte boundary: the row's
+// first value is peeled (the first lane takes it with the odd last one), so that the pairs of the result, and of every operand of the
+// result's shape, lie on 16-byte boundaries; an operand of another shape whose pair does not is read as two values.  The choice depends on
+// the row alone, never on the lane.
+struct FieldOperand {
+    const void* s;
+    const void* n;
+    long long rows, len;
+    double re, im;
+};
+template <typename T> struct alignas(16) two { T a, b; };
+
+template <typename T> __device__ __forceinline__ T scalar_as(double re, double im) {
+    if constexpr (sizeof(T) == sizeof(double) && !__is_same(T, cf)) return re;
+    else if constexpr (__is_same(T, cf)) return {(float)re, (float)im};
+    else return {re, im};
+}
+__device__ __forceinline__ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+// values c, c + 1 of a row of `len` values
+template <typename T> __device__ __forceinline__ void fetch2(const T* row, long long c, long long len, T& x, T& y) {
+    if (len == 1) { x = y = row[0]; return; }
+    const T* q = row + c;
+    if (aligned16(q)) {
+        const two<T> v = *reinterpret_cast<const two<T>*>(q);
+        x = v.a; y = v.b;
+    } else {
+        x = q[0]; y = q[1];
+    }
+}
+template <typename T> __device__ __forceinline__ void put2(T* row, long long c, T x, T y) {
+    T* q = row + c;
+    if (aligned16(q)) *reinterpret_cast<two<T>*>(q) = two<T>{x, y};
+    else { q[0] = x; q[1] = y; }
+}
+
+// W values (1 or 2) from column c on of one row
+template <typename T, int W>
+__device__ __forceinline__ void field_binary_at(int op, long long c, const T* s1, const T* n1, long long len1, const T* s2, const T* n2, long long len2, T scalar,
+                                                T* os, T* on, unsigned char* ob) {
+    const bool h1 = n1 != nullptr, h2 = n2 != nullptr;
+    T a[2], an[2], b[2], bn[2];
+    const T zero = scalar_as<T>(0.0, 0.0);
+    an[0] = an[1] = bn[0] = bn[1] = zero;
+    b[0] = b[1] = scalar;
+    if constexpr (W == 2) {
+        fetch2<T>(s1, c, len1, a[0], a[1]);
+        if (h1) fetch2<T>(n1, c, len1, an[0], an[1]);
+        if (s2) fetch2<T>(s2, c, len2, b[0], b[1]);
+        if (h2) fetch2<T>(n2, c, len2, bn[0], bn[1]);
+    } else {
+        a[0] = s1[len1 == 1 ? 0 : c];
+        if (h1) an[0] = n1[len1 == 1 ? 0 : c];
+        if (s2) b[0] = s2[len2 == 1 ? 0 : c];
+        if (h2) bn[0] = n2[len2 == 1 ? 0 : c];
+    }
+    if (op == SSFM_SIGNAL_EQ) {
+#pragma unroll
+        for (int k = 0; k < W; ++k) ob[c + k] = eq(h1 ? a[k] + an[k] : a[k], h2 ? b[k] + bn[k] : b[k]);
+        return;
+    }
+    T so[2], no[2];
+#pragma unroll
+    for (int k = 0; k < W; ++k) binary_one<T>(op, a[k], an[k], h1, b[k], bn[k], h2, so[k], no[k]);
+    if constexpr (W == 2) {
+        put2<T>(os, c, so[0], so[1]);
+        if (on) put2<T>(on, c, no[0], no[1]);
+    } else {
+        os[c] = so[0];
+        if (on) on[c] = no[0];
+    }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_field_binary(int op, long long n, FieldOperand a, FieldOperand b, T* __restrict__ out_s, T* __restrict__ out_n,
+                                                      unsigned char* __restrict__ out_b) {
+    const long long r = blockIdx.y, first = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+    const long long o1 = (a.rows == 1 ? 0 : r) * a.len, o2 = (b.rows == 1 ? 0 : r) * b.len;
+    const T* s1 = (const T*)a.s + o1;
+    const T* n1 = a.n ? (const T*)a.n + o1 : nullptr;
+    const T* s2 = b.s ? (const T*)b.s + o2 : nullptr;
+    const T* n2 = b.n ? (const T*)b.n + o2 : nullptr;
+    T* os = out_s ? out_s + r * n : nullptr;
+    T* on = out_n ? out_n + r * n : nullptr;
+    unsigned char* ob = out_b ? out_b + r * n : nullptr;
+    const T scalar = scalar_as<T>(b.re, b.im);
+    if constexpr (sizeof(T) == 16) {
+        for (long long c = first; c < n; c += stride) field_binary_at<T, 1>(op, c, s1, n1, a.len, s2, n2, b.len, scalar, os, on, ob);
+    } else {
+        const long long head = (r * n) & 1, pairs = (n - head) >> 1;
+        for (long long i = first; i < pairs; i += stride) field_binary_at<T, 2>(op, head + 2 * i, s1, n1, a.len, s2, n2, b.len, scalar, os, on, ob);
+        if (first == 0) {
+            if (head) field_binary_at<T, 1>(op, 0, s1, n1, a.len, s2, n2, b.len, scalar, os, on, ob);
+            if ((n - head) & 1) field_binary_at<T, 1>(op, n - 1, s1, n1, a.len, s2, n2, b.len, scalar, os, on, ob);
+        }
+    }
+}
+
+// complex64, `count` values in a row (a whole contiguous field): -x, conj(x), x / p in single precision
+__global__ __launch_bounds__(256) void k_field_unary_cf(int op, long long count, const cf* __restrict__ s, const cf* __restrict__ nz, cf p, cf* __restrict__ out_s,
+                                                        cf* __restrict__ out_n) {
+    const long long first = (long long)blockIdx.x * blockDim.x + threadIdx.x, stride = (long long)gridDim.x * blockDim.x;
+    auto one = [&](cf v) -> cf {
+        if (op == SSFM_SIGNAL_NEG) return -v;
+        if (op == SSFM_SIGNAL_CONJ) return {v.re, -v.im};
+        return cdiv(v, p);
+    };
+    for (long long i = first; i < (count >> 1); i += stride) {
+        cf x, y;
+        fetch2<cf>(s, 2 * i, count, x, y);
+        put2<cf>(out_s, 2 * i, one(x), one(y));
+        if (nz) {
+            fetch2<cf>(nz, 2 * i, count, x, y);
+            put2<cf>(out_n, 2 * i, one(x), one(y));
+        }
+    }
+    if ((count & 1) && first == 0) {
+        out_s[count - 1] = one(s[count - 1]);
+        if (nz) out_n[count - 1] = one(nz[count - 1]);
+    }
+}
+
+// out[r][i] = in[row0 + r][start + i step] of signal and noise (typing.py:2261-2305); T: a value of 8 or of 16 bytes
+template <typename T>
+__global__ __launch_bounds__(256) void k_field_slice(const T* __restrict__ s, const T* __restrict__ nz, long long n, long long row0, long long start, long long step,
+                                                     long long count, T* __restrict__ out_s, T* __restrict__ out_n) {
+    const long long src = (row0 + blockIdx.y) * n + start, dst = (long long)blockIdx.y * count;
+    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (long long)gridDim.x * blockDim.x) {
+        out_s[dst + i] = s[src + i * step];
+        if (nz) out_n[dst + i] = nz[src + i * step];
+    }
+}
+
 int finish(const char* what) {
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -409,6 +570,20 @@ bool same_device(const void* p, int device) {
 }
 
 bool operand_ok(const void* s, const void* nz, int64_t len, int64_t n) { return s ? (len == n || len == 1) : nz == nullptr; }
+
+// the per-workgroup partials of one row, folded in order on the host
+void fold_partials(int kind, const double* host, int blocks, int64_t n, double* out) {
+    double a0 = 0.0, a1 = 0.0;
+    for (int i = 0; i < blocks; ++i) {
+        const double v = host[2 * i];
+        if (kind == SSFM_SIGNAL_MAXABS) a0 = (v > a0 || v != v) ? v : a0;
+        else a0 += v;
+        a1 += host[2 * i + 1];
+    }
+    if (kind == SSFM_SIGNAL_POWER) a0 /= (double)n;
+    out[0] = a0;
+    if (kind == SSFM_SIGNAL_SUM) out[1] = a1;
+}
 
 }  // namespace
 
@@ -514,16 +689,7 @@ extern "C" int ssfm_signal_reduce(int kind, int64_t rows, int64_t n, const void*
     hipError_t e = hipMemcpy(host, partial, sizeof(double) * 2 * blocks, hipMemcpyDeviceToHost);
     (void)ssfm_device_free(device, partial, sizeof(double) * 2 * kBlocks);
     if (e != hipSuccess) return fail(SSFM_ERR_HIP, "ssfm_signal_reduce: %s", hipGetErrorString(e));
-    double a0 = 0.0, a1 = 0.0;
-    for (int i = 0; i < blocks; ++i) {
-        const double v = host[2 * i];
-        if (kind == SSFM_SIGNAL_MAXABS) a0 = (v > a0 || v != v) ? v : a0;
-        else a0 += v;
-        a1 += host[2 * i + 1];
-    }
-    if (kind == SSFM_SIGNAL_POWER) a0 /= (double)n;
-    out[0] = a0;
-    if (kind == SSFM_SIGNAL_SUM) out[1] = a1;
+    fold_partials(kind, host, blocks, n, out);
     return SSFM_OK;
 }
 
@@ -558,4 +724,113 @@ extern "C" int ssfm_signal_split(const void* src, int64_t n, double* re, double*
     if (int rc = device_of(src, &device)) return rc;
     hipLaunchKernelGGL(k_signal_split, dim3(grid_for(n, kGridCap)), dim3(256), 0, 0, (const double2*)src, (long long)n, re, im);
     return finish("ssfm_signal_split");
+}
+
+// ---------------------------------------------------------------------------------------------- optical fields: entry points
+namespace {
+bool field_dtype_ok(int dtype) { return dtype == SSFM_C64 || dtype == SSFM_C128 || dtype == SSFM_F64_REAL; }
+// an operand's shape against the result's: rows 1 or the result's, len 1 or n; a scalar (s == nullptr) has no noise
+bool field_operand_ok(const void* s, const void* nz, int64_t rows_k, int64_t len_k, int64_t rows, int64_t n) {
+    return s ? ((rows_k == 1 || rows_k == rows) && (len_k == 1 || len_k == n)) : nz == nullptr;
+}
+bool base_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+}  // namespace
+
+extern "C" int ssfm_field_binary(int op, int dtype, int64_t rows, int64_t n, const void* s1, const void* n1, int64_t rows1, int64_t len1, const void* s2,
+                                 const void* n2, int64_t rows2, int64_t len2, double re2, double im2, void* out_signal, void* out_noise) {
+    const bool op_ok = op == SSFM_SIGNAL_ADD || op == SSFM_SIGNAL_SUB || op == SSFM_SIGNAL_RSUB || op == SSFM_SIGNAL_MUL || op == SSFM_SIGNAL_EQ;
+    if (!s2) rows2 = len2 = 1;
+    if (!op_ok || !field_dtype_ok(dtype) || (rows != 1 && rows != 2) || n < 1 || !s1 || !out_signal || !field_operand_ok(s1, n1, rows1, len1, rows, n) ||
+        !field_operand_ok(s2, n2, rows2, len2, rows, n) || (rows1 != rows && rows2 != rows) || (len1 != n && len2 != n))
+        return fail(SSFM_ERR_INVALID, "ssfm_field_binary: op=%d dtype=%d result (%lld, %lld), operands (%lld, %lld) and (%lld, %lld): rows 1 or 2, each operand "
+                    "1 or the result's along either axis", op, dtype, (long long)rows, (long long)n, (long long)rows1, (long long)len1, (long long)rows2, (long long)len2);
+    const bool compare = op == SSFM_SIGNAL_EQ;
+    if (!compare && ((n1 || n2) != (out_noise != nullptr))) return fail(SSFM_ERR_INVALID, "ssfm_field_binary: out_noise is needed exactly when an operand has noise");
+    if (!base_aligned(s1) || !base_aligned(n1) || !base_aligned(s2) || !base_aligned(n2) || !base_aligned(out_signal) || !base_aligned(out_noise))
+        return fail(SSFM_ERR_INVALID, "ssfm_field_binary: an array does not start on a 16-byte boundary");
+    int device = 0;
+    if (int rc = ssfm::device_of(s1, "ssfm_field_*", &device)) return rc;
+    for (const void* p : {n1, s2, n2, (const void*)out_signal, (const void*)out_noise})
+        if (p && !same_device(p, device)) return fail(SSFM_ERR_INVALID, "ssfm_field_binary: the operands lie on different devices");
+    const FieldOperand a = {s1, n1, (long long)rows1, (long long)len1, 0.0, 0.0};
+    const FieldOperand b = {s2, n2, (long long)rows2, (long long)len2, re2, im2};
+    void* os = compare ? nullptr : out_signal;
+    void* on = compare ? nullptr : out_noise;
+    unsigned char* ob = compare ? (unsigned char*)out_signal : nullptr;
+    const dim3 grid(grid_for(dtype == SSFM_C128 ? n : (n + 1) / 2, kGridCap), (unsigned)rows);
+    if (dtype == SSFM_C128) hipLaunchKernelGGL(k_field_binary<cd>, grid, dim3(256), 0, 0, op, (long long)n, a, b, (cd*)os, (cd*)on, ob);
+    else if (dtype == SSFM_C64) hipLaunchKernelGGL(k_field_binary<cf>, grid, dim3(256), 0, 0, op, (long long)n, a, b, (cf*)os, (cf*)on, ob);
+    else hipLaunchKernelGGL(k_field_binary<double>, grid, dim3(256), 0, 0, op, (long long)n, a, b, (double*)os, (double*)on, ob);
+    return finish("ssfm_field_binary");
+}
+
+extern "C" int ssfm_field_unary(int op, int dtype, int64_t rows, int64_t n, const void* signal, const void* noise, double p_re, double p_im, int p_complex,
+                                void* out_signal, void* out_noise) {
+    if (!field_dtype_ok(dtype) || (rows != 1 && rows != 2) || n < 1 || !signal || !out_signal)
+        return fail(SSFM_ERR_INVALID, "ssfm_field_unary: op=%d dtype=%d rows=%lld n=%lld (rows 1 or 2)", op, dtype, (long long)rows, (long long)n);
+    // a pointwise operation does not see the rows of a contiguous field: the double-precision types are ssfm_signal_unary's, on rows * n values
+    if (dtype != SSFM_C64) return ssfm_signal_unary(op, 1, rows * n, signal, noise, dtype == SSFM_C128, p_re, p_im, p_complex, out_signal, out_noise);
+    if (op != SSFM_SIGNAL_NEG && op != SSFM_SIGNAL_CONJ && op != SSFM_SIGNAL_DIV)
+        return fail(SSFM_ERR_UNSUPPORTED, "ssfm_field_unary: op=%d of complex64 values (neg, conj and the quotient only: widen the field for the others)", op);
+    if ((noise != nullptr) != (out_noise != nullptr)) return fail(SSFM_ERR_INVALID, "ssfm_field_unary: op=%d takes out_noise exactly with noise", op);
+    const cf p = {(float)p_re, p_complex ? (float)p_im : 0.0f};
+    if (op == SSFM_SIGNAL_DIV && p.re == 0.0f && p.im == 0.0f) return fail(SSFM_ERR_INVALID, "ssfm_field_unary: division by zero");
+    if (!base_aligned(signal) || !base_aligned(noise) || !base_aligned(out_signal) || !base_aligned(out_noise))
+        return fail(SSFM_ERR_INVALID, "ssfm_field_unary: an array does not start on a 16-byte boundary");
+    int device = 0;
+    if (int rc = ssfm::device_of(signal, "ssfm_field_*", &device)) return rc;
+    for (const void* p : {noise, (const void*)out_signal, (const void*)out_noise})
+        if (p && !same_device(p, device)) return fail(SSFM_ERR_INVALID, "ssfm_field_unary: signal, noise and results lie on different devices, or in host memory");
+    const long long count = rows * n;
+    hipLaunchKernelGGL(k_field_unary_cf, dim3(grid_for((count + 1) / 2, kGridCap)), dim3(256), 0, 0, op, count, (const cf*)signal, (const cf*)noise, p, (cf*)out_signal,
+                       (cf*)out_noise);
+    return finish("ssfm_field_unary");
+}
+
+extern "C" int ssfm_field_slice(int dtype, int64_t rows, int64_t n, const void* signal, const void* noise, int64_t row0, int64_t nrows, int64_t start, int64_t step,
+                                int64_t count, void* out_signal, void* out_noise) {
+    // every row and column read lies inside the field: checked here, so that no key reaches the kernel that would read outside the arrays
+    // (count and step are bounded by n before the last index is formed, so that no argument makes it overflow)
+    // (one value: any step; more: a step of at most n either way)
+    const bool span_ok = n >= 1 && n <= (int64_t(1) << 31) && count >= 1 && count <= n && step != 0 && (count == 1 || (step >= -n && step <= n)) && start >= 0 && start < n;
+    const int64_t last = !span_ok ? -1 : (count == 1 ? start : start + (count - 1) * step);
+    if (!field_dtype_ok(dtype) || (rows != 1 && rows != 2) || !span_ok || !signal || !out_signal || row0 < 0 || row0 > 1 || nrows < 1 || nrows > 2 || row0 + nrows > rows ||
+        last < 0 || last >= n || (noise != nullptr) != (out_noise != nullptr))
+        return fail(SSFM_ERR_INVALID, "ssfm_field_slice: dtype=%d rows=%lld n=%lld row0=%lld nrows=%lld start=%lld step=%lld count=%lld", dtype, (long long)rows,
+                    (long long)n, (long long)row0, (long long)nrows, (long long)start, (long long)step, (long long)count);
+    int device = 0;
+    if (int rc = ssfm::device_of(signal, "ssfm_field_*", &device)) return rc;
+    for (const void* p : {noise, (const void*)out_signal, (const void*)out_noise})
+        if (p && !same_device(p, device)) return fail(SSFM_ERR_INVALID, "ssfm_field_slice: signal, noise and results lie on different devices, or in host memory");
+    const dim3 grid(grid_for(count, kGridCap), (unsigned)nrows);
+    if (dtype == SSFM_C128)
+        hipLaunchKernelGGL(k_field_slice<double2>, grid, dim3(256), 0, 0, (const double2*)signal, (const double2*)noise, (long long)n, (long long)row0, (long long)start,
+                           (long long)step, (long long)count, (double2*)out_signal, (double2*)out_noise);
+    else        // 8 bytes: a float64 or a complex64 value
+        hipLaunchKernelGGL(k_field_slice<double>, grid, dim3(256), 0, 0, (const double*)signal, (const double*)noise, (long long)n, (long long)row0, (long long)start,
+                           (long long)step, (long long)count, (double*)out_signal, (double*)out_noise);
+    return finish("ssfm_field_slice");
+}
+
+extern "C" int ssfm_field_reduce(int kind, int64_t rows, int64_t n, const void* signal, const void* noise, int is_complex, double* out) {
+    if ((rows != 1 && rows != 2) || n < 1 || !signal || !out || kind < SSFM_SIGNAL_POWER || kind > SSFM_SIGNAL_SUM)
+        return fail(SSFM_ERR_INVALID, "ssfm_field_reduce: kind=%d rows=%lld n=%lld (rows 1 or 2)", kind, (long long)rows, (long long)n);
+    if (!base_aligned(signal) || !base_aligned(noise)) return fail(SSFM_ERR_INVALID, "ssfm_field_reduce: an array does not start on a 16-byte boundary");
+    int device = 0;
+    if (int rc = ssfm::device_of(signal, "ssfm_field_*", &device)) return rc;
+    if (noise && !same_device(noise, device)) return fail(SSFM_ERR_INVALID, "ssfm_field_reduce: signal and noise lie on different devices");
+    constexpr int kBlocks = 1024;
+    const int blocks = (int)grid_for(is_complex ? n : (n + 1) / 2, kBlocks);
+    double* partial = nullptr;
+    if (int rc = ssfm_device_alloc(device, sizeof(double) * 4 * kBlocks, (void**)&partial)) return rc;
+    hipLaunchKernelGGL(k_field_reduce, dim3(blocks, (unsigned)rows), dim3(256), 0, 0, kind, is_complex, (const double*)signal, (const double*)noise, (long long)n, partial);
+    static thread_local double host[4 * kBlocks];
+    hipError_t e = hipMemcpy(host, partial, sizeof(double) * 2 * blocks * rows, hipMemcpyDeviceToHost);
+    (void)ssfm_device_free(device, partial, sizeof(double) * 4 * kBlocks);
+    if (e != hipSuccess) return fail(SSFM_ERR_HIP, "ssfm_field_reduce: %s", hipGetErrorString(e));
+    for (int64_t r = 0; r < rows; ++r) {
+        out[2 * r + 1] = 0.0;
+        fold_partials(kind, host + 2 * blocks * r, blocks, n, out + 2 * r);
+    }
+    return SSFM_OK;
 }

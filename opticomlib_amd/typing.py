@@ -10,7 +10,7 @@
 
 ``electrical_signal.psd()`` / ``optical_signal.psd()`` plot the Welch spectrum of :func:`opticomlib_amd.get_psd` (computed on the
 GPU; matplotlib is imported when the method is called).  :class:`electrical_signal` has the reference's operators and methods, computed
-where the signal lies; ``optical_signal`` has a small host part of them.  The other plots, eye diagrams etc. are out of scope.
+where the signal lies, and so has :class:`optical_signal`.  The other plots, eye diagrams etc. are out of scope.
 """
 from __future__ import annotations
 
@@ -595,22 +595,10 @@ class electrical_signal:
         if op in ("gt", "eq"):
             x, y = s1 + n1, s2 + n2
             return binary_sequence(x > y) if op == "gt" else x == y
-        neg = lambda a: a if a is NULL else -a                                                       # noqa: E731
-        if op == "add":
-            return self.__class__(s1 + s2, n1 + n2)
-        if op == "sub":                                         # a + (-b), as the reference forms it
-            return self.__class__(s1 + (-s2), n1 + neg(n2))
-        if op == "rsub":                                        # (-a) + b
-            return self.__class__((-s1) + s2, neg(n1) + n2)
-        noi = NULL                                              # s1 n2 + n1 s2 + n1 n2; a product with NULL is NULL, a sum with it the other term
-        for a, b in ((s1, n2), (n1, s2), (n1, n2)):
-            if a is not NULL and b is not NULL:
-                noi = noi + a * b
-        return self.__class__(s1 * s2, noi)
+        return _host_binary(self.__class__, op, s1, n1, s2, n2)
 
     def _binary_device(self, op, other):
         from . import _lib
-        codes = {"add": 0, "sub": 1, "rsub": 2, "mul": 3, "gt": 4, "eq": 5}
         scalar = None
         if isinstance(other, (numbers.Number, np.number, np.bool_)):
             scalar = complex(other) if isinstance(other, (complex, np.complexfloating)) else float(other)
@@ -643,7 +631,7 @@ class electrical_signal:
             out = _lib.DeviceArray((n,), dt, dev)
             out_n = _lib.DeviceArray((n,), dt, dev) if (n1 is not None or n2 is not None) else None
         z = complex(scalar) if scalar is not None else 0j
-        _lib.api.ssfm_signal_binary(codes[op], 1, n, s1, n1, s1.size, int(c1), s2, n2, size2, int(c2), z.real, z.imag, out, out_n)
+        _lib.api.ssfm_signal_binary(_BINARY[op], 1, n, s1, n1, s1.size, int(c1), s2, n2, size2, int(c2), z.real, z.imag, out, out_n)
         if op == "gt":
             return binary_sequence.from_device(out)
         if op == "eq":
@@ -684,29 +672,22 @@ class electrical_signal:
     def __neg__(self):
         if self.on_device:
             return self._unary_device("neg")
-        return self.__class__(-self.signal, NULL if self.noise is NULL else -self.noise)
+        return _host_map(self.__class__, lambda a: -a, self)
 
     def __truediv__(self, number):
-        if not isinstance(number, numbers.Complex):
-            raise TypeError(f"Can't divide electrical_signal by type {type(number)}")
-        if number == 0:
-            raise ZeroDivisionError("Can't divide electrical_signal by zero")
+        _check_divisor(number)
         if self.on_device:
             cplx = isinstance(number, (complex, np.complexfloating))
             return self._unary_device("div", complex(number) if cplx else float(number), complex_out=cplx)
-        return self.__class__(self.signal / number, NULL if self.noise is NULL else self.noise / number)
+        return _host_map(self.__class__, lambda a: a / number, self)
 
     def __floordiv__(self, other):
         if self.on_device:
-            if not isinstance(other, numbers.Complex):
-                raise TypeError(f"Can't divide electrical_signal by type {type(other)}")
-            if other == 0:
-                raise ZeroDivisionError("Can't divide electrical_signal by zero")
+            _check_divisor(other)
             if self._raw("signal").dtype.kind == "c" or isinstance(other, (complex, np.complexfloating)):
                 np.floor(np.zeros(1, np.complex128))            # NumPy's own TypeError: floor takes no complex values
             return self._unary_device("floordiv", float(other))
-        x = self / other
-        return self.__class__(np.floor(x.signal), NULL if x.noise is NULL else np.floor(x.noise))
+        return _host_map(self.__class__, np.floor, self / other)
 
     def __pow__(self, other):
         """``** 0``: ones; ``** 1``: the signal; ``** 2``: ``signal**2`` with the noise ``2 signal noise + noise**2`` (``2.0`` takes this
@@ -727,16 +708,7 @@ class electrical_signal:
                 raise ValueError(f"electrical_signal ** {other}: a complex128 signal on the GPU takes integer exponents below 100 and 0.5; "
                                  "there is no host fallback for a device-resident signal")
             return self._unary_device("pow", float(other), single=True)
-        if other == 0:
-            sig, noi = np.ones_like(self.signal), NULL
-        elif other == 1:
-            sig, noi = self.signal, self.noise
-        elif other == 2:
-            sig = self.signal ** 2
-            noi = NULL if self.noise is NULL else 2 * self.signal * self.noise + self.noise ** 2
-        else:
-            sig, noi = (self.signal + self.noise) ** other, NULL
-        return self.__class__(sig, noi)
+        return _host_pow(self.__class__, self, other)
 
     def __getitem__(self, key):
         """A slice: a new signal (an empty one is the constructor's ``ValueError``); an ``int``: the value itself when there is no noise, a
@@ -779,13 +751,9 @@ class electrical_signal:
         appears); ``np.abs`` of a device-resident signal stays there; any other ufunc sees the materialised ``signal + noise`` and a 1-D
         result comes back wrapped (reference ``typing.py:1240-1275``)."""
         if method == "__call__" and not kwargs.get("out"):
-            if ufunc in (np.add, np.subtract, np.multiply) and len(inputs) == 2 and isinstance(inputs[1], electrical_signal):
-                lhs, rhs = inputs
-                if ufunc is np.add:
-                    return rhs.__add__(lhs)
-                if ufunc is np.subtract:
-                    return (-rhs).__add__(lhs)
-                return rhs.__mul__(lhs)
+            r = _reflected_ufunc(electrical_signal, ufunc, inputs)
+            if r is not NotImplemented:
+                return r
             if ufunc is np.absolute and self.on_device and inputs[0] is self:
                 return self._unary_device("abs_all", real_out=True, single=True)
         args = [a.__array__() if isinstance(a, self.__class__) else a for a in inputs]
@@ -799,18 +767,18 @@ class electrical_signal:
     def real(self):
         if self.on_device:
             return self._unary_device("real", real_out=True)
-        return self.__class__(self.signal.real, NULL if self.noise is NULL else self.noise.real)
+        return _host_map(self.__class__, lambda a: a.real, self)
 
     @property
     def imag(self):
         if self.on_device:
             return self._unary_device("imag", real_out=True)
-        return self.__class__(self.signal.imag, NULL if self.noise is NULL else self.noise.imag)
+        return _host_map(self.__class__, lambda a: a.imag, self)
 
     def conj(self):
         if self.on_device:
             return self._unary_device("conj")
-        return self.__class__(self.signal.conj(), NULL if self.noise is NULL else self.noise.conj())
+        return _host_map(self.__class__, lambda a: a.conj(), self)
 
     def _reduce_device(self, kind, s, n=None):
         from . import _lib
@@ -827,7 +795,7 @@ class electrical_signal:
                 o = self._reduce_device(2, a)
                 return np.complex128(complex(o[0], o[1])) if a.dtype.kind == "c" else np.float64(o[0])
             return self.__class__(val(s), NULL if n is None else val(n))
-        return self.__class__(self.signal.sum(axis=axis), NULL if self.noise is NULL else self.noise.sum(axis=axis))
+        return _host_map(self.__class__, lambda a: a.sum(axis=axis), self)
 
     def abs(self, of="all"):
         """``|signal|``, ``|noise|`` (zeros of the real type without noise) or ``|signal + noise|`` as a new signal."""
@@ -896,17 +864,123 @@ class electrical_signal:
             s, n = self._device_arrays()
             return self._wrap(*devices._filter_device(s, n, h))
         import scipy.signal as sg
-        return self.__class__(sg.fftconvolve(self.signal, h, mode="same"), NULL if self.noise is NULL else sg.fftconvolve(self.noise, h, mode="same"))
+        return _host_map(self.__class__, lambda a: sg.fftconvolve(a, h, mode="same"), self)
 
 
 _DEVICE_DTYPES = (np.dtype(np.float64), np.dtype(np.complex128))
-# enum of include/ssfm_amd.h (ssfm_signal_unary)
+# enums of include/ssfm_amd.h (ssfm_signal_binary / ssfm_field_binary, ssfm_signal_unary / ssfm_field_unary)
+_BINARY = {"add": 0, "sub": 1, "rsub": 2, "mul": 3, "gt": 4, "eq": 5}
 _UNARY = {"neg": 0, "conj": 1, "div": 2, "floordiv": 3, "pow2": 4, "real": 5, "imag": 6, "abs_signal": 7, "abs_noise": 8, "abs_all": 9, "pow": 10}
+# ssfm_field_*: the code of a device field's type (enum ssfm_precision and SSFM_F64_REAL of include/ssfm_amd.h)
+_FIELD_CODES = {np.dtype(np.complex64): 0, np.dtype(np.complex128): 1, np.dtype(np.float64): 2}
+
+
+# -- the host algebra that electrical_signal and optical_signal share: NumPy on materialised arrays, NULL for an absent noise
+def _host_binary(make, op, s1, n1, s2, n2):
+    """'add', 'sub', 'rsub' or 'mul' of (s1, n1) and (s2, n2) with the reference's signal / noise rules (``typing.py:1308-1348``);
+    ``make(signal, noise)`` builds the result."""
+    neg = lambda a: a if a is NULL else -a                                                           # noqa: E731
+    if op == "add":
+        return make(s1 + s2, n1 + n2)
+    if op == "sub":                                             # a + (-b), as the reference forms it
+        return make(s1 + (-s2), n1 + neg(n2))
+    if op == "rsub":                                            # (-a) + b
+        return make((-s1) + s2, neg(n1) + n2)
+    noi = NULL                                                  # s1 n2 + n1 s2 + n1 n2; a product with NULL is NULL, a sum with it the other term
+    for a, b in ((s1, n2), (n1, s2), (n1, n2)):
+        if a is not NULL and b is not NULL:
+            noi = noi + a * b
+    return make(s1 * s2, noi)
+
+
+def _host_map(make, f, x):
+    """``make(f(signal), f(noise))``, an absent noise staying absent: neg, conj, real, imag, the quotient, sum, filter."""
+    return make(f(x.signal), NULL if x.noise is NULL else f(x.noise))
+
+
+def _host_pow(make, x, other):
+    """``** 0``: ones; ``** 1``: the signal; ``** 2``: ``signal**2`` with the noise ``2 signal noise + noise**2``; any other exponent:
+    ``(signal + noise) ** other`` without noise (reference ``typing.py:1400-1419``)."""
+    if other == 0:
+        return make(np.ones_like(x.signal), NULL)
+    if other == 1:
+        return make(x.signal, x.noise)
+    if other == 2:
+        return make(x.signal ** 2, NULL if x.noise is NULL else 2 * x.signal * x.noise + x.noise ** 2)
+    return make((x.signal + x.noise) ** other, NULL)
+
+
+def _check_divisor(number):
+    """The reference's checks of ``/`` and ``//`` (``typing.py:1350-1357``; its texts name ``electrical_signal`` for both classes)."""
+    if not isinstance(number, numbers.Complex):
+        raise TypeError(f"Can't divide electrical_signal by type {type(number)}")
+    if number == 0:
+        raise ZeroDivisionError("Can't divide electrical_signal by zero")
+
+
+def _reflected_ufunc(cls, ufunc, inputs):
+    """``ndarray + x``, ``ndarray - x`` and ``ndarray * x`` as the operators of ``x`` (reference ``typing.py:1243-1255``), or NotImplemented."""
+    if ufunc in (np.add, np.subtract, np.multiply) and len(inputs) == 2 and isinstance(inputs[1], cls):
+        lhs, rhs = inputs
+        if ufunc is np.add:
+            return rhs.__add__(lhs)
+        if ufunc is np.subtract:
+            return (-rhs).__add__(lhs)
+        return rhs.__mul__(lhs)
+    return NotImplemented
+
+
+def _field_total(x, dev):
+    """``signal + noise`` of a field or an electrical signal, in its own type, as one array on GPU ``dev`` (the signal itself without noise)."""
+    from . import _lib
+    if not x.on_device:
+        return np.asarray(x.signal + x.noise)                 # (uploaded once, as the operation's type, by the caller)
+    s, n = x._device_arrays()
+    if n is None:
+        return s
+    out = _lib.DeviceArray(s.shape, s.dtype, s.device)
+    rows, cols = (s.shape[0] if s.ndim == 2 else 1), s.shape[-1]
+    _lib.api.ssfm_field_binary(_BINARY["add"], _FIELD_CODES[s.dtype], rows, cols, s, None, rows, cols, n, None, rows, cols, 0.0, 0.0, out, None)
+    return out
+
+
 
 
 class optical_signal:
-    """Optical field container: ``signal`` (and optional ``noise``) of shape ``(N,)`` for one
-    polarisation or ``(2, N)`` for two."""
+    """Optical field: ``signal`` (and optional ``noise``) of shape ``(N,)`` for one polarisation or ``(2, N)`` for two, with the algebra the
+    reference's class inherits from ``electrical_signal`` (``typing.py:1308-1419``) and its own indexing (``typing.py:2261-2305``).
+
+    ``+ - * / // **`` and the reflected forms, unary ``-``, ``==``, ``[]`` with a slice, an integer or ``x[pol, samples]``, ``conj``, ``real``,
+    ``imag``, ``sum``, ``power``, ``normalize``, ``filter``, ``w``, ``f``, ``t``, ``fs``, ``sps``, ``dt``, ``type``, ``ndim``, ``__array__``,
+    ``__iter__`` and ``__array_ufunc__`` carry the reference's names, argument checks, error texts (they say ``electrical_signal`` where the
+    reference's do) and signal / noise rules.  Operands broadcast as NumPy's: a ``(2, N)`` field with an ``(N,)`` field, an
+    ``electrical_signal`` (its signal and noise stay apart and serve both polarisations), a ``(2, 1)`` or ``(1,)`` value, an array or a
+    scalar.  The result's ``n_pol`` follows its shape.  ``>`` and ``<`` raise the reference's ``NotImplementedError``.
+
+    Residency, as ``electrical_signal``'s: an operation with a device-resident operand (``on_device``: what ``FIBER``, ``DBP``, ``DM``,
+    ``BPF``, ``EDFA``, ``MZM``, ``LASER``, ``PM`` and ``FBG`` return) runs on that GPU, by the ``ssfm_field_*`` kernels of
+    ``csrc/signal_ops.hip``, and its result lies there too.  A Python scalar is a kernel argument; a host array or host signal as the other
+    operand is uploaded once; operands on two GPUs are a ``ValueError``; there is no silent copy to the host: a case the device path does
+    not take raises.  Device fields are float64, complex128 or complex64; another device type is a ``TypeError``.  Host-only operands are
+    NumPy on the host and load no device.
+
+    Types on the device follow NumPy >= 2's ``result_type`` of the arrays the reference forms (a Python ``2.5`` is a float64 array there,
+    so ``complex64 * 2.5`` is complex128; ``complex64 / 2.5`` stays complex64).  ``+ - *``, ``-x``, ``conj``, ``[]`` and the quotient by a
+    scalar of complex64 operands are computed in single precision; a complex64 operand that meets a wider one is widened first (exact).
+    ``**``, ``power``, ``sum``, ``normalize`` and ``filter`` of a complex64 field are computed in double precision from the widened values
+    and rounded once.  ``power`` (a NumPy scalar, or a ``(2,)`` array), ``sum`` (a host field of size 1) and an element ``x[i]`` of a
+    noiseless field bring numbers back, ``==`` a host bool array; ``np.asarray(x)``, iteration and a NumPy ufunc other than the three
+    reflected operators and ``np.abs`` materialise the field on the host.
+
+    ``abs(of)`` and ``phase()`` are reads, like ``.signal``: they return host NumPy arrays (the reference returns signal objects there).
+    The device-resident magnitude is ``np.abs(x)``.
+
+    Left to raise on the GPU: ``real``, ``imag`` and ``np.abs`` of a complex64 field (float32 in NumPy, a type the device arrays do not
+    hold): ``TypeError``; ``**`` of a complex field with an exponent other than an integer ``|p| < 100`` or ``0.5``: ``ValueError``;
+    ``filter`` of a two-polarisation field: SciPy's ``ValueError``, as on the host; a polarisation key other than an integer or ``:`` and
+    a samples key other than an integer or a slice: ``TypeError``.
+
+    Not provided: ``plot``, ``print``, ``sizeof``, the reference's ``__getattr__`` delegation to ``ndarray`` and ``__array_function__``."""
 
     signal = _LazyArray()
     noise = _LazyArray()
@@ -1036,10 +1110,43 @@ class optical_signal:
         w = np.fft.fftfreq(self.size, gv.dt) * 2 * np.pi
         return np.fft.fftshift(w, axes=-1) if shift else w
 
-    # -- the little signal algebra a link script uses around the devices (reference typing.py:1308-1344, :1599-1608,
-    #    :1663-1720); host arithmetic on materialised arrays
+    # -- metadata and protocols (reference typing.py:1216-1229, :1488-1522): no transfer but for __array__ / __iter__
+    __hash__ = None                  # (an `__eq__` that returns an array: unhashable, as the reference's class)
+
+    @property
+    def ndim(self) -> int:
+        return self._raw("signal").ndim
+
+    @property
+    def type(self):
+        return type(self)
+
+    @property
+    def fs(self):
+        return gv.fs
+
+    @property
+    def sps(self):
+        return gv.sps
+
+    @property
+    def t(self):
+        return gv.t[:self.size]
+
+    def f(self, shift: bool = False) -> np.ndarray:
+        """Frequency grid [Hz] (reference ``typing.py:1646-1660``)."""
+        return self.w(shift) / (2 * np.pi)
+
+    def __iter__(self):
+        return iter(self.__array__())
+
+    def __array__(self, dtype=None, copy=None):
+        arr = self.signal + self.noise
+        return arr if dtype is None else arr.astype(dtype)
+
+    # -- reads: NumPy arrays on the host, like `.signal` (the reference returns signal objects here; the device-resident |x| is np.abs(x))
     def abs(self, of: str = "all") -> np.ndarray:
-        """``|signal|``, ``|noise|`` (zeros without noise) or ``|signal + noise|``."""
+        """``|signal|``, ``|noise|`` (zeros without noise) or ``|signal + noise|`` as a host array: a read, like ``.signal``."""
         of = of.lower()
         if of == "signal":
             return np.abs(self.signal)
@@ -1049,50 +1156,190 @@ class optical_signal:
             return np.abs(self.to_numpy())
         raise ValueError('`of` must be one of the following values ("signal", "noise", "all")')
 
-    def power(self, unit: str = "W", of: str = "all"):
-        """Mean power per polarisation of the signal, the noise or both, in W or dBm."""
-        p = np.mean(self.abs(of) ** 2, axis=-1)
-        unit = unit.lower()
-        if unit == "w":
-            return p
-        if unit == "dbm":
-            return 10 * np.log10(p) + 30
-        raise ValueError('`unit` must be one of the following values ("W", "dBm")')
-
     def phase(self) -> np.ndarray:
+        """``unwrap(angle(signal + noise))`` as a host array: a read, like ``.signal``."""
         return np.unwrap(np.angle(self.to_numpy()))
 
-    def conj(self):
-        return optical_signal(np.conj(self.signal), NULL if self.noise is NULL else np.conj(self.noise), n_pol=self.n_pol)
+    def power(self, unit: str = "W", of: str = "all"):
+        """Mean power per polarisation of the signal, the noise or both, in W or dBm: a NumPy scalar, or a ``(2,)`` array.  Reduced on the
+        GPU for a device-resident field (every row in one launch; a complex64 field is widened and the result rounded once to float32)."""
+        single = False
+        if self.on_device:
+            if of.lower() not in ("signal", "noise", "all"):
+                raise ValueError('`of` must be one of the following values ("signal", "noise", "all")')
+            s, n = self._device_arrays()
+            single = s.dtype == np.complex64                    # float64 up to the end, then rounded once to NumPy's float32
+            of = of.lower()
+            if of == "noise" and n is None:
+                p = np.zeros(s.shape[:-1])[()]
+            else:
+                p = self._reduce_device(0, n if of == "noise" else s, n if of == "all" else None)[:, 0]
+                p = p if s.ndim == 2 else p[0]
+        else:
+            p = np.mean(self.abs(of) ** 2, axis=-1)
+        unit = unit.lower()
+        if unit == "w":
+            return p.astype(np.float32) if single else p
+        if unit == "dbm":
+            p = 10 * np.log10(p) + 30
+            return p.astype(np.float32) if single else p
+        raise ValueError('`unit` must be one of the following values ("W", "dBm")')
 
-    def _other(self, other):
-        return (other.signal, other.noise) if isinstance(other, (optical_signal, electrical_signal)) else (np.asarray(other), NULL)
+    # -- device plumbing: the arrays where they lie, the one upload of a host operand, launches
+    def _device_arrays(self):
+        """``(signal, noise or None)`` as DeviceArrays of one type (float64, complex128 or complex64) on one GPU, for a device-resident field."""
+        from . import _lib
+        s, n = self._raw("signal"), self._raw("noise")
+        if s.dtype not in _FIELD_CODES:
+            raise TypeError(f"optical_signal: the device algebra takes float64, complex128 and complex64, this field lies on the GPU as {s.dtype}; "
+                            "there is no host fallback for a device-resident field (convert it, or take .to_numpy())")
+        if n is NULL:
+            return s, None
+        if not _is_device(n):                                   # (a noise that was assigned on the host afterwards)
+            n = _lib.DeviceArray.from_host(np.ascontiguousarray(n, dtype=s.dtype), None, s.device)
+        elif n.dtype != s.dtype or n.device != s.device:
+            raise TypeError(f"optical_signal: signal ({s.dtype}, GPU {s.device}) and noise ({n.dtype}, GPU {n.device}) differ")
+        return s, n
 
-    def _device_pair(self, other):
-        """Both operands entirely in the memory of one GPU, same shape and complex type: the sum can stay there."""
-        if not isinstance(other, optical_signal):
-            return False
-        a, b = self._raw("signal"), other._raw("signal")
-        if not (_is_device(a) and _is_device(b)) or tuple(a.shape) != tuple(b.shape) or a.dtype != b.dtype or a.dtype.kind != "c" or a.device != b.device:
-            return False
-        return all(x is NULL or (_is_device(x) and x.dtype == a.dtype and x.device == a.device) for x in (self._raw("noise"), other._raw("noise")))
+    @staticmethod
+    def _wrap(s, n=None):
+        """A device result as a field; ``n_pol`` follows the shape, as in ``self.__class__(sig, noi)`` of the reference."""
+        return optical_signal.from_device(s, NULL if n is None else n)
 
+    @staticmethod
+    def _as(a, dt, dev):
+        """Array ``a`` (device or host, or None) on GPU ``dev`` as type ``dt``: widened on the device (exact), or uploaded once as ``dt``."""
+        from . import _lib
+        if a is None:
+            return None
+        if _is_device(a):
+            return a if a.dtype == dt else a.astype(dt)
+        return _lib.DeviceArray.from_host(np.ascontiguousarray(a, dtype=dt), None, dev)
+
+    def _shapes_error(self, shape):
+        return ValueError(f"Can't operate 'optical_signal's with shapes {self.shape} and {tuple(shape)}")
+
+    def _parse(self, other):
+        """The other operand as a field whose size is this one's or 1 (reference ``typing.py:1557-1573``); an ``electrical_signal`` keeps its
+        signal and noise apart and broadcasts over the polarisations."""
+        if isinstance(other, electrical_signal):
+            other = optical_signal(other.signal, other.noise)
+        elif not isinstance(other, optical_signal):
+            other = optical_signal(other)
+        if self.size != other.size and min(self.size, other.size) != 1:
+            raise self._shapes_error(other.shape)
+        return other
+
+    def _binary(self, op, other):
+        """``op``: 'add', 'sub', 'rsub', 'mul' or 'eq' between this field and ``other``, where the operands lie."""
+        if self.on_device or (isinstance(other, (optical_signal, electrical_signal)) and other.on_device):
+            return self._binary_device(op, other)
+        o = self._parse(other)
+        s1, n1, s2, n2 = self.signal, self.noise, o.signal, o.noise
+        if op == "eq":
+            return (s1 + n1) == (s2 + n2)
+        return _host_binary(optical_signal, op, s1, n1, s2, n2)
+
+    def _binary_device(self, op, other):
+        """One launch of ``ssfm_field_binary`` on the GPU that holds a device-resident operand.  The result's type is NumPy's
+        ``result_type`` of the arrays the reference would form (a scalar is ``np.array(scalar)``: a Python float is float64 there);
+        an operand of a narrower type is widened first, which is exact."""
+        from . import _lib
+        scalar = None
+        if isinstance(other, (numbers.Number, np.number, np.bool_)):
+            scalar, o = complex(other), None
+            shape2, dt2 = (1,), np.asarray(other).dtype
+        else:
+            if isinstance(other, (optical_signal, electrical_signal)):
+                o = other
+            else:
+                o = optical_signal(other)                       # a host array: the constructor's shape rules and errors
+            shape2, dt2 = tuple(o._raw("signal").shape), o._raw("signal").dtype
+        if self.size != shape2[-1] and min(self.size, shape2[-1]) != 1:
+            raise self._shapes_error(shape2)
+        devs = {x._raw("signal").device for x in (self, o) if x is not None and x.on_device}
+        if len(devs) > 1:
+            raise ValueError(f"Can't operate 'optical_signal's that lie on different GPUs {sorted(devs)}: move one of them first")
+        dev = devs.pop()
+        for x in (self, o):
+            if x is not None and x.on_device:
+                x._device_arrays()                              # (the TypeError of a device type the kernels do not take)
+        shape = np.broadcast_shapes(self.shape, shape2)
+        dt = np.result_type(self._raw("signal").dtype, dt2)
+        if dt not in _FIELD_CODES:
+            raise TypeError(f"optical_signal: the device algebra takes float64, complex128 and complex64, not the {dt} this operation gives")
+        part = lambda x: [None if a is NULL else a for a in (x._raw("signal"), x._raw("noise"))]     # noqa: E731
+        (s1, n1), (s2, n2) = part(self), ((None, None) if o is None else part(o))
+        if op == "eq":                                          # signal + noise of each operand in its own type first, as NumPy forms it
+            s1, n1 = _field_total(self, dev), None
+            if o is not None:
+                s2, n2 = _field_total(o, dev), None
+        elif op != "mul" and (n1 is None) != (n2 is None):
+            # the reference adds the noises with NULL as the identity: a lone noise meets the signal's shape in the constructor
+            nshape = tuple((n1 if n2 is None else n2).shape)
+            if nshape != shape:
+                raise ValueError(f"`signal` and `noise` must have the same shape, mismatch shapes {shape} and {nshape}!")
+        s1, n1, s2, n2 = (self._as(a, dt, dev) for a in (s1, n1, s2, n2))
+        rows, n = (shape[0] if len(shape) == 2 else 1), shape[-1]
+        dims = lambda sh: ((sh[0] if len(sh) == 2 else 1), sh[-1])                                   # noqa: E731
+        if op == "eq":
+            out, out_n = _lib.DeviceArray(shape, np.uint8, dev), None
+        else:
+            out = _lib.DeviceArray(shape, dt, dev)
+            out_n = _lib.DeviceArray(shape, dt, dev) if (n1 is not None or n2 is not None) else None
+        z = scalar if scalar is not None else 0j
+        _lib.api.ssfm_field_binary(_BINARY[op], _FIELD_CODES[dt], rows, n, s1, n1, *dims(self.shape), s2, n2, *dims(shape2), z.real, z.imag, out, out_n)
+        if op == "eq":
+            return out.to_host().astype(bool)
+        return self._wrap(out, out_n)
+
+    def _unary_device(self, op, p=0.0, *, out_dtype=None, single=False, wide=False, back=False):
+        """One launch of ``ssfm_field_unary``.  ``single``: one result array without noise; ``wide``: a complex64 field is widened
+        (exact) and computed in double precision; ``back``: the result of that is rounded once to complex64."""
+        from . import _lib
+        s, n = self._device_arrays()
+        narrow = back and wide and s.dtype == np.complex64
+        if wide and s.dtype == np.complex64:
+            s, n = s.astype(np.complex128), (None if n is None else n.astype(np.complex128))
+        dt = s.dtype if out_dtype is None else np.dtype(out_dtype)
+        out = _lib.DeviceArray(s.shape, dt, s.device)
+        out_n = None if (single or n is None) else _lib.DeviceArray(s.shape, dt, s.device)
+        z = complex(p)
+        rows, cols = (s.shape[0] if s.ndim == 2 else 1), s.shape[-1]
+        _lib.api.ssfm_field_unary(_UNARY[op], _FIELD_CODES[s.dtype], rows, cols, s, n, z.real, z.imag, int(isinstance(p, (complex, np.complexfloating))), out, out_n)
+        if narrow and dt == np.complex128:
+            out, out_n = out.astype(np.complex64), (None if out_n is None else out_n.astype(np.complex64))
+        return self._wrap(out, out_n)
+
+    def _no_float32(self, what):
+        """``real``, ``imag`` and ``np.abs`` of a complex64 field are float32 arrays in NumPy, a type the device arrays do not have."""
+        if self._raw("signal").dtype == np.complex64:
+            raise TypeError(f"optical_signal: {what} of a complex64 field on the GPU would be float32, which the device arrays do not hold; "
+                            "widen the field first (x * np.complex128(1)) or take .to_numpy()")
+
+    def _reduce_device(self, kind, s, n=None):
+        """``ssfm_field_reduce`` of every row in one launch: a ``(rows, 2)`` float64 array (a complex64 field is widened first)."""
+        from . import _lib
+        import ctypes
+        if s.dtype == np.complex64:
+            s, n = s.astype(np.complex128), (None if n is None else n.astype(np.complex128))
+        rows = s.shape[0] if s.ndim == 2 else 1
+        out = (ctypes.c_double * (2 * rows))()
+        _lib.api.ssfm_field_reduce(kind, rows, s.shape[-1], s, n, int(s.dtype.kind == "c"), out)
+        return np.array(out[:], dtype=np.float64).reshape(rows, 2)
+
+    # -- operators (reference typing.py:1308-1419)
     def __add__(self, other):
-        if self._device_pair(other):                          # e.g. two WDM channels coming out of their modulators
-            n1, n2 = self._raw("noise"), other._raw("noise")
-            noise = n2 if n1 is NULL else (n1 if n2 is NULL else n1 + n2)
-            return optical_signal.from_device(self._raw("signal") + other._raw("signal"), noise, n_pol=self.n_pol)
-        s, n = self._other(other)
-        return optical_signal(self.signal + s, self.noise + n, n_pol=self.n_pol)
+        return self._binary("add", other)
 
-    __radd__ = __add__
-
-    def __neg__(self):
-        return optical_signal(-self.signal, NULL if self.noise is NULL else -self.noise, n_pol=self.n_pol)
+    def __radd__(self, other):
+        return self._binary("add", other)
 
     def __sub__(self, other):
-        s, n = self._other(other)
-        return optical_signal(self.signal - s, self.noise - n if n is not NULL else self.noise, n_pol=self.n_pol)
+        return self._binary("sub", other)
+
+    def __rsub__(self, other):
+        return self._binary("rsub", other)
 
     def __mul__(self, other):
         """``(s1 + n1)(s2 + n2)``: the signal is ``s1 s2``, everything that contains a noise factor is noise."""
@@ -1102,19 +1349,257 @@ class optical_signal:
             from . import _lib                                 # a real gain / loss factor on a device-resident signal
             return optical_signal.from_device(_lib.scale_add_device(raw_s, float(other)),
                                               NULL if raw_n is NULL else _lib.scale_add_device(raw_n, float(other)), n_pol=self.n_pol)
-        s, n = self._other(other)
-        sig = self.signal * s
-        noi = NULL
-        for term in ((self.signal * n) if n is not NULL else NULL, (self.noise * s) if self.noise is not NULL else NULL,
-                     (self.noise * n) if (self.noise is not NULL and n is not NULL) else NULL):
-            noi = noi + term
-        return optical_signal(sig, noi, n_pol=self.n_pol)
+        return self._binary("mul", other)
 
-    __rmul__ = __mul__
+    def __rmul__(self, other):
+        return self.__mul__(other)
+
+    def __neg__(self):
+        if self.on_device:
+            return self._unary_device("neg")
+        return _host_map(optical_signal, lambda a: -a, self)
+
+    def __truediv__(self, number):
+        _check_divisor(number)
+        if self.on_device:
+            s, _ = self._device_arrays()
+            dt = np.result_type(s.dtype, number)                # NumPy >= 2: a Python scalar does not widen a complex64 field, a float64 scalar does
+            cplx = isinstance(number, (complex, np.complexfloating))
+            return self._unary_device("div", complex(number) if cplx else float(number), out_dtype=dt, wide=dt != np.complex64)
+        return _host_map(optical_signal, lambda a: a / number, self)
+
+    def __floordiv__(self, other):
+        if self.on_device:
+            _check_divisor(other)
+            if self._device_arrays()[0].dtype.kind == "c" or isinstance(other, (complex, np.complexfloating)):
+                np.floor(np.zeros(1, np.complex128))            # NumPy's own TypeError: floor takes no complex values
+            return self._unary_device("floordiv", float(other))
+        return _host_map(optical_signal, np.floor, self / other)
+
+    def __pow__(self, other):
+        """``** 0``: ones; ``** 1``: the field; ``** 2``: ``signal**2`` with the noise ``2 signal noise + noise**2``; any other real exponent:
+        ``(signal + noise) ** other`` without noise (on the GPU: the exponents ``electrical_signal`` takes there)."""
+        if not isinstance(other, numbers.Real):
+            raise TypeError(f"Can't exponentiate electrical_signal by type {type(other)}")
+        if self.on_device:
+            s, n = self._device_arrays()
+            if other == 0:
+                from . import _lib
+                ones = _lib.shift_device(_lib.zeros_device(s.shape, np.complex128 if s.dtype.kind == "c" else np.float64, s.device), 1.0)
+                return self._wrap(ones if ones.dtype == s.dtype or s.dtype.kind != "c" else ones.astype(s.dtype))
+            if other == 1:
+                return self._wrap(s, n)
+            if other == 2:
+                return self._unary_device("pow2", wide=True, back=True)
+            if s.dtype.kind == "c" and other != 0.5 and not (float(other).is_integer() and abs(other) < 100):
+                raise ValueError(f"optical_signal ** {other}: a complex field on the GPU takes integer exponents below 100 and 0.5; "
+                                 "there is no host fallback for a device-resident field")
+            return self._unary_device("pow", float(other), single=True, wide=True, back=True)
+        return _host_pow(optical_signal, self, other)
+
+    def __eq__(self, other):
+        """A host bool array (``(a == b).all()``); computed on the GPU for device operands, then read."""
+        return self._binary("eq", other)
+
+    def __gt__(self, other):
+        raise NotImplementedError('The > operator is not implemented for optical_signal objects.')
+
+    def __lt__(self, other):
+        raise NotImplementedError('The < operator is not implemented for optical_signal objects.')
 
     def __getitem__(self, key):
-        return optical_signal(self.signal[..., key] if self.n_pol == 2 else self.signal[key],
-                              NULL if self.noise is NULL else (self.noise[..., key] if self.n_pol == 2 else self.noise[key]), n_pol=self.n_pol)
+        """The reference's indexing (``typing.py:2261-2305``): a slice cuts the samples of every polarisation; an integer is a sample of a
+        one-polarisation field (the value itself without noise) or a polarisation of a two-polarisation field; ``x[pol, samples]`` takes
+        both.  On the GPU a polarisation is an integer or ``:`` and the samples an integer or a slice; other keys raise ``TypeError``."""
+        if self.on_device:
+            return self._getitem_device(key)
+        sig_, noi_, two = self.signal, self.noise, self.n_pol == 2
+        if isinstance(key, tuple):
+            if len(key) != 2:
+                raise IndexError('Too many indices for optical_signal object.')
+            pol_idx, time_idx = key
+            if not two and pol_idx not in [0, -1, slice(None)]:
+                raise IndexError('Optical signal has only one polarization (index 0).')
+            sig = sig_[pol_idx, time_idx] if two else sig_[time_idx]
+            if noi_ is not NULL:
+                noi = noi_[pol_idx, time_idx] if two else noi_[time_idx]
+            elif isinstance(time_idx, int):
+                return sig[time_idx]
+            else:
+                noi = NULL
+            return optical_signal(sig, noi, n_pol=1 if sig.ndim != 2 else self.n_pol)
+        if isinstance(key, slice):
+            cut = (lambda a: a[:, key]) if two else (lambda a: a[key])
+            return optical_signal(cut(sig_), NULL if noi_ is NULL else cut(noi_), n_pol=self.n_pol)
+        if not two:
+            sig = sig_[key]
+            if noi_ is NULL:
+                return sig
+            noi = noi_[key]
+        else:
+            sig = sig_[key, :]
+            noi = NULL if noi_ is NULL else noi_[key, :]
+        return optical_signal(sig, noi, n_pol=1 if sig.ndim != 2 else self.n_pol)
+
+    def _getitem_device(self, key):
+        from . import _lib
+        s, n = self._device_arrays()
+        two, size = self.n_pol == 2 and s.ndim == 2, s.shape[-1]
+        bad_shape = lambda sh: ValueError(f"Signal must be a scalar, 1D or 2D array for optical_signal, invalid shape {sh}")     # noqa: E731
+        is_int = lambda k: isinstance(k, (int, np.integer)) and not isinstance(k, (bool, np.bool_))                            # noqa: E731
+
+        def probe(k):
+            """NumPy's own exception for a key it does not take (asked of an array of this shape that holds no data)."""
+            np.broadcast_to(np.zeros(1, np.uint8), s.shape)[k]
+
+        def column(k):
+            """(start, step, count, is a single sample) of the samples' key."""
+            if isinstance(k, slice):
+                start, stop, step = k.indices(size)
+                return start, step, len(range(start, stop, step)), False
+            if not is_int(k):
+                probe((slice(None), k) if two else k)
+                raise TypeError(f"optical_signal on the GPU takes an integer or a slice for the samples, not {k!r} of type {type(k)}; "
+                                "there is no host fallback for a device-resident field")
+            if not -size <= k < size:
+                raise IndexError(f"index {k} is out of bounds for axis {1 if two else 0} with size {size}")
+            return int(k) % size, 1, 1, True
+
+        def row(k):
+            if not is_int(k):
+                probe(k)
+                raise TypeError(f"optical_signal on the GPU takes an integer or ':' for the polarisation, not {k!r} of type {type(k)}; "
+                                "there is no host fallback for a device-resident field")
+            if not -2 <= k < 2:
+                raise IndexError(f"index {k} is out of bounds for axis 0 with size 2")
+            return int(k) % 2
+
+        def cut(row0, nrows, start, step, count, shape):
+            out = _lib.DeviceArray(shape, s.dtype, s.device)
+            out_n = None if n is None else _lib.DeviceArray(shape, s.dtype, s.device)
+            _lib.api.ssfm_field_slice(_FIELD_CODES[s.dtype], 2 if s.ndim == 2 else 1, size, s, n, row0, nrows, start, step, count, out, out_n)
+            return out, out_n
+
+        if isinstance(key, tuple):
+            if len(key) != 2:
+                raise IndexError('Too many indices for optical_signal object.')
+            pol_idx, time_idx = key
+            if not two and pol_idx not in [0, -1, slice(None)]:
+                raise IndexError('Optical signal has only one polarization (index 0).')
+            all_rows = not two or (isinstance(pol_idx, slice) and pol_idx == slice(None))
+            r0 = 0 if all_rows else row(pol_idx)
+            start, step, count, one = column(time_idx)
+            nrows = 2 if (two and all_rows) else 1
+            if n is None and isinstance(time_idx, int):         # the reference indexes its result once more by the sample's key
+                if nrows == 1:
+                    raise IndexError("invalid index to scalar variable.")
+                if not -2 <= time_idx < 2:
+                    raise IndexError(f"index {time_idx} is out of bounds for axis 0 with size 2")
+                return cut(time_idx % 2, 1, start, 1, 1, (1,))[0].to_host()[0]
+            if count < 1:
+                raise bad_shape((2, 0) if nrows == 2 else (0,))
+            shape = ((2,) if nrows == 2 else (1,)) if one else ((2, count) if nrows == 2 else (count,))
+            return self._wrap(*cut(r0, nrows, start, step, count, shape))
+        if isinstance(key, slice):
+            start, step, count, _ = column(key)
+            if count < 1:
+                raise bad_shape((2, 0) if two else (0,))
+            return self._wrap(*cut(0, 2 if two else 1, start, step, count, (2, count) if two else (count,)))
+        if not two:
+            start, _, _, _ = column(key)
+            out, out_n = cut(0, 1, start, 1, 1, (1,))
+            return out.to_host()[0] if n is None else self._wrap(out, out_n)
+        return self._wrap(*cut(row(key), 1, 0, 1, size, (size,)))
+
+    def __array_ufunc__(self, ufunc, method, *inputs, **kwargs):
+        """``ndarray + x``, ``ndarray - x`` and ``ndarray * x`` go to the field's own operators; ``np.abs`` of a device-resident field stays
+        there as a field; any other ufunc sees the materialised ``signal + noise`` and a 1-D or 2-D result comes back wrapped (reference
+        ``typing.py:1240-1275``)."""
+        if method == "__call__" and not kwargs.get("out"):
+            r = _reflected_ufunc(optical_signal, ufunc, inputs)
+            if r is not NotImplemented:
+                return r
+            if ufunc is np.absolute and self.on_device and inputs[0] is self:
+                self._device_arrays()
+                self._no_float32("np.abs")
+                return self._unary_device("abs_all", out_dtype=np.float64, single=True)
+        args = [a.__array__() if isinstance(a, optical_signal) else a for a in inputs]
+        result = getattr(ufunc, method)(*args, **kwargs)
+        if isinstance(result, np.ndarray) and result.ndim in (1, 2):
+            return optical_signal(result)
+        return result
+
+    # -- methods (reference typing.py:1476-1486, :1599-1780)
+    @property
+    def real(self):
+        if self.on_device:
+            self._device_arrays()
+            self._no_float32("real")
+            return self._unary_device("real", out_dtype=np.float64)
+        return _host_map(optical_signal, lambda a: a.real, self)
+
+    @property
+    def imag(self):
+        if self.on_device:
+            self._device_arrays()
+            self._no_float32("imag")
+            return self._unary_device("imag", out_dtype=np.float64)
+        return _host_map(optical_signal, lambda a: a.imag, self)
+
+    def conj(self):
+        if self.on_device:
+            return self._unary_device("conj")
+        return _host_map(optical_signal, np.conj, self)
+
+    def sum(self, axis=None):
+        """Sums of signal and noise over the whole field as a field of size 1 (host values; on the device every row is summed in one
+        launch and the rows are added on the host).  ``axis`` is the host path's, as NumPy's."""
+        if self.on_device:
+            s, n = self._device_arrays()
+
+            def val(a):
+                o = self._reduce_device(2, a).sum(axis=0)
+                return a.dtype.type(complex(o[0], o[1])) if a.dtype.kind == "c" else np.float64(o[0])
+            return optical_signal(val(s), NULL if n is None else val(n))
+        return _host_map(optical_signal, lambda a: a.sum(axis=axis), self)
+
+    def normalize(self, by="power"):
+        """The field divided by the square root of its signal power (one polarisation: the quotient is by a scalar), or by its largest
+        ``|signal|`` over both polarisations."""
+        if by not in ("power", "amplitude"):
+            raise ValueError('`by` must be one of the following values ("power", "amplitude")')
+        if not self.on_device:
+            return self / (self.power("W", "signal") ** 0.5 if by == "power" else np.abs(self.signal).max())
+        s = self._device_arrays()[0]
+        if by == "power":
+            d = self._reduce_device(0, s)[:, 0] ** 0.5
+            d = d if s.ndim == 2 else d[0]
+        else:
+            amp = self._reduce_device(1, s)[:, 0]
+            d = amp[np.isnan(amp)][0] if np.isnan(amp).any() else amp.max()
+        if s.dtype != np.complex64 or np.ndim(d) or d == 0:     # (two powers: the quotient's TypeError, as the (2,) array of power() gives it)
+            return self / (d.astype(np.float32) if s.dtype == np.complex64 else d)
+        return self._unary_device("div", float(d), wide=True, back=True)      # float64 up to the end, then rounded once to complex64
+
+    def filter(self, h):
+        """``scipy.signal.fftconvolve(., h, mode='same')`` of signal and noise (reference ``typing.py:1758-1780``): one polarisation,
+        as SciPy's own ``ValueError`` says of a ``(2, N)`` field with 1-D taps.  On the GPU in complex128; a complex64 field is widened
+        and the result rounded once."""
+        if self.on_device:
+            from . import devices
+            s, n = self._device_arrays()
+            h = np.asarray(h)
+            if s.ndim != h.ndim:
+                raise ValueError("in1 and in2 should have the same dimensionality")
+            single = s.dtype == np.complex64
+            if single:
+                s, n = s.astype(np.complex128), (None if n is None else n.astype(np.complex128))
+            out, out_n = devices._filter_device(s, n, h)
+            if single and np.result_type(np.complex64, h.dtype) == np.complex64:
+                out, out_n = out.astype(np.complex64), (None if out_n is None else out_n.astype(np.complex64))
+            return self._wrap(out, out_n)
+        import scipy.signal as sg
+        return _host_map(optical_signal, lambda a: sg.fftconvolve(a, h, mode="same"), self)
 
     def __repr__(self):
         where = " [device]" if self.on_device else ""

@@ -13,8 +13,8 @@ import sys
 
 
 def kind(what):
-    what = re.sub(r"\b(n|taps|chunk)=\d+ ", "", what)
-    return re.sub(r"^(binary|reflected|scalar|pow|methods|filter|protocol)/\S+", lambda m: m.group(1) + " fixtures", what)
+    what = re.sub(r"\b(n|taps|chunk|rows)=\d+ ", "", what)
+    return re.sub(r"^(binary|reflected|scalar|pow|methods|filter|protocol)(_\w+)?/\S+", lambda m: m.group(1) + " fixtures", what)
 
 
 HEAD = ("comparisons recorded by the GPU tests of the signal algebra on one MI355X, folded by tools/margins_digest.py: per kind of comparison,\n"
