@@ -61,6 +61,9 @@
  *   typing.py:402-1009 (binary_sequence's          ssfm_bits_binary (& | ^ !=), ssfm_bits_not (~, flip), ssfm_bits_concat (+), ssfm_bits_tile (* n),
  *     operators, ones, zeros, hamming_distance)    ssfm_bits_slice ([]), ssfm_bits_count (ones, zeros, an integer index; hamming_distance of equal
  *                                                  lengths is ssfm_device_count_diff)
+ *   utils.py:1593-1787 (eyediagram; also           ssfm_eye_density_range (minimum, maximum, non-finite flag of the plotted points), ssfm_eye_density
+ *     electrical_signal.plot_eye,                  (np.histogram2d counts, scipy.ndimage.gaussian_filter, the plotted points' colours)
+ *     typing.py:1971-2041)
  *   (none: NumPy arrays are the reference's only   ssfm_device_alloc / _free / _copy / _convert / _add
  *     data format)                                 -- device-resident signals between calls
  *
@@ -698,6 +701,26 @@ SSFM_API int ssfm_bits_concat(const unsigned char* a, int64_t len_a, const unsig
 /* ssfm_bits_count: *ones (HOST) = the number of nonzero bytes among the n at a (typing.py:796-808).  Integer sums and one integer atomic per
  * workgroup: exact, and the same number on every call. */
 SSFM_API int ssfm_bits_count(const unsigned char* a, int64_t n, int64_t* ones);
+
+/* The density grid of an eye diagram (utils.py:1593-1787, eyediagram) of a real float64 record of n samples in DEVICE memory, `noise` (nullable, DEVICE,
+ * n samples) added to it sample by sample.  sps / 2 samples are cut from both ends; a trace is P = 2 sps points; T = min(available, n_traces) traces
+ * are drawn (n_traces < 0: all); point j < T P is sample sps / 2 + j at phase j mod P.  n <= 2^31 (uint32 counters).  As ssfm_signal_*: no device
+ * argument (the device that owns `y`), a pointer that is not device memory or a record that leaves no trace is SSFM_ERR_INVALID before any launch,
+ * default stream, finished on return.  Counts are integers, minima and maxima exact, float sums in a fixed order: the same bits on every call.
+ *   ssfm_eye_density_range  out (HOST, 3) = minimum and maximum of the plotted points (NaN ignored, infinities included) and flags: 1 a NaN, 2 an
+ *                           infinity was seen.  The caller forms numpy.linspace edges from them on the host.
+ *   ssfm_eye_density        counts (HOST, bins x bins uint32, [ix][iy]) = np.histogram2d of the points: the bin of y among `yedges` (HOST, bins + 1)
+ *                           is searchsorted(side='right') - 1 with the last edge in the last bin, decided by comparisons with the edges; the
+ *                           column of phase p is xbin[p] (HOST, P entries, non-decreasing).  grid (HOST, bins x bins float64) =
+ *                           scipy.ndimage.gaussian_filter(counts) with mode='reflect': weights (HOST, radius + 1 values, the centre's first;
+ *                           NULL: no blur) applied along axis 0, then axis 1, in SciPy's order of terms.  1 <= bins <= 4096.
+ *                           With xidx (HOST, P entries; nullable) also, per plotted point: points = its value, iy = clip(int((v - min_y) /
+ *                           (max_y - min_y) (bins - 1)), 0, bins - 1) (0 when max_y == min_y), colors = grid[xidx[p]][iy] normalised to
+ *                           (c - c_min) / (c_max - c_min) over the points, zeros when c_max == c_min (HOST, T P values each). */
+SSFM_API int ssfm_eye_density_range(const double* y, const double* noise, int64_t n, int64_t sps, int64_t n_traces, double* out);
+SSFM_API int ssfm_eye_density(const double* y, const double* noise, int64_t n, int64_t sps, int64_t n_traces, int64_t bins, const double* yedges,
+                              const int32_t* xbin, const double* weights, int64_t radius, uint32_t* counts, double* grid, const int32_t* xidx,
+                              double min_y, double max_y, double* points, int32_t* iy, double* colors);
 
 #ifdef __cplusplus
 }

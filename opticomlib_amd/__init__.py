@@ -9,8 +9,8 @@ The arithmetic runs in hand-written HIP kernels (``csrc/``) behind the C ABI dec
 from .typing import NULL, binary_sequence, electrical_signal, eye, gv, optical_signal
 from .devices import ADC, BPF, DAC, DBP, DM, EDFA, FBG, FIBER, GET_EYE, LASER, LPF, MZM, PD, PM, PRBS, SAMPLER, device_rng_seed
 from . import lab, ook, ppm
-from .utils import get_psd
+from .utils import eye_density, eyediagram, get_psd
 from ._lib import C64, C128, Plan, SsfmError, device_count
 
-__all__ = ["NULL", "gv", "optical_signal", "electrical_signal", "FIBER", "DBP", "DM", "LPF", "BPF", "PD", "EDFA", "PRBS", "DAC", "LASER", "MZM", "PM", "FBG", "ADC", "GET_EYE", "SAMPLER", "ook", "ppm", "lab", "get_psd", "eye", "binary_sequence", "device_rng_seed", "Plan", "SsfmError", "device_count", "C64", "C128"]
+__all__ = ["NULL", "gv", "optical_signal", "electrical_signal", "FIBER", "DBP", "DM", "LPF", "BPF", "PD", "EDFA", "PRBS", "DAC", "LASER", "MZM", "PM", "FBG", "ADC", "GET_EYE", "SAMPLER", "ook", "ppm", "lab", "get_psd", "eye_density", "eyediagram", "eye", "binary_sequence", "device_rng_seed", "Plan", "SsfmError", "device_count", "C64", "C128"]
 __version__ = "0.1.0"

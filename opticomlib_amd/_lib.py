@@ -127,6 +127,8 @@ SYMBOLS = {
     "ssfm_bits_tile": (_I, [_VP, _I64, _I64, _VP]),
     "ssfm_bits_concat": (_I, [_VP, _I64, _VP, _I64, _VP]),
     "ssfm_bits_count": (_I, [_VP, _I64, C.POINTER(_I64)]),
+    "ssfm_eye_density_range": (_I, [_VP, _VP, _I64, _I64, _I64, C.POINTER(_D)]),
+    "ssfm_eye_density": (_I, [_VP, _VP, _I64, _I64, _I64, _I64, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _D, _D, _VP, _VP, _VP]),
 }
 
 

@@ -426,7 +426,7 @@ class electrical_signal:
     convolution: a noise below ``1e-12`` of the signal loses its digits on that path.  ``**`` of a complex128 device signal takes the
     exponents NumPy computes by products (integers ``|p| < 100``) and ``0.5``; another exponent raises ``ValueError``.
 
-    Not provided: ``plot``, ``plot_eye``, ``print``, ``grid``, ``legend``, ``show``, ``sizeof``, the reference's ``__getattr__`` delegation
+    Not provided: ``plot``, ``print``, ``grid``, ``legend``, ``show``, ``sizeof``, the reference's ``__getattr__`` delegation
     to ``ndarray`` and ``__array_function__``."""
 
     signal = _LazyArray()
@@ -542,6 +542,17 @@ class electrical_signal:
         ``yscale``: ``'dbm'`` or ``'linear'`` (mW); ``mode``: ``'x'``, ``'y'`` or ``'both'`` polarisations.  Returns ``self``."""
         from .utils import plot_psd
         return plot_psd(self, fmt, mode, n, xlabel, ylabel, yscale, grid, hold, show, **kwargs)
+
+    MAX_EYE_TRACES = 4096
+
+    def plot_eye(self, n_traces=None, cmap='jet', N_grid_bins=200, grid_sigma=5, style='dot', ax=None, **plot_kw):
+        """Plot the eye diagram of signal + noise with ``gv.sps`` samples per symbol (reference ``typing.py:1971-2041``): at most
+        ``min(n_traces, 4096)`` traces, the density computed where the signal lies (``utils.eyediagram`` has the styles and ``plot_kw``).
+        Returns ``self``."""
+        from .utils import eyediagram
+        n_traces = self.MAX_EYE_TRACES if n_traces is None else min(n_traces, self.MAX_EYE_TRACES)
+        eyediagram(self, gv.sps, n_traces, cmap, N_grid_bins, grid_sigma, style, ax, **plot_kw)
+        return self
 
     def __repr__(self):
         where = " [device]" if self.on_device else ""

@@ -5,6 +5,10 @@ The reference wraps ``scipy.signal.welch``; here the same estimate -- periodic H
 ``nfft = nperseg``, no detrend, ``scaling='spectrum'``, two-sided, mean over the segments -- runs in the HIP kernels of
 ``csrc/psd.hip`` on the field where it lies (a device-resident signal is read in place, only the result comes back).
 All arithmetic is float64.  There is no host fallback.
+
+Also the eye diagram (reference ``utils.py:1593-1787``): :func:`eye_density` computes the picture's data -- ``np.histogram2d`` of the traces'
+points, ``scipy.ndimage.gaussian_filter`` of the counts, the plotted points' colours -- where the record lies (``csrc/eye_density.hip`` for a
+record in GPU memory, NumPy / SciPy for a host record), and :func:`eyediagram` draws it.
 """
 from __future__ import annotations
 
@@ -303,4 +307,247 @@ def plot_psd(obj, fmt='-', mode='x', n=None, xlabel=None, ylabel=None, yscale='d
     return obj
 
 
-__all__ = ["get_psd"]
+# ----------------------------------------------------------------------------- the eye diagram's density (csrc/eye_density.hip)
+EYE_CHUNK_POINTS = 32768      # csrc/eye_density.hip kChunkPoints: a workgroup of the counting kernel takes max(1, 32768 // (2 sps)) traces
+EYE_MAX_BINS = 4096           # csrc/eye_density.hip kMaxBins (the device path; the host path is NumPy's and has no limit)
+_EYE_STYLES = ("line", "dot", "density")
+
+
+class EyeDensity:
+    """What :func:`eye_density` returns (host arrays): ``grid`` the blurred density, (B, B) float64, ``grid[ix, iy]``; ``counts`` the integer
+    counts before the blur; ``xedges``, ``yedges``; ``extent = (min_x, max_x, min_y, max_y)``; ``n_traces``; with ``colors=True`` also ``x``,
+    ``y``, ``colors`` of the ``n_traces * 2 sps`` plotted points and their grid indices ``ix``, ``iy`` (else None)."""
+    __slots__ = ("grid", "counts", "xedges", "yedges", "extent", "n_traces", "x", "y", "colors", "ix", "iy")
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def _eye_geometry(n: int, sps: int, n_traces):
+    """``(start, P, T)`` of the reference's truncation (``utils.py:1651-1670``), with its errors and their texts."""
+    start, end = sps // 2, n - sps // 2
+    if start >= end:
+        raise ValueError(f"Signal too short for truncation. Need at least {sps} samples, got {n}.")
+    P = 2 * sps
+    if end - start < P:
+        raise ValueError(f"Need at least {P} points for eye diagram, got {end - start} after truncation.")
+    available = (end - start) // P
+    T = min(available, n_traces) if n_traces is not None else available
+    if T == 0:
+        raise ValueError(f"Not enough points to form even one trace of {P} points after truncation.")
+    if T < 0:
+        raise ValueError(f"n_traces must not be negative, got {n_traces}")
+    return start, P, int(T)
+
+
+def _hist_edges(lo, hi, bins: int) -> np.ndarray:
+    """The edges ``np.histogramdd`` forms for an integer ``bins``: its ``_get_outer_edges`` (the error for a range that is not finite, +- 0.5
+    around a single value), then ``np.linspace``."""
+    if not (np.isfinite(lo) and np.isfinite(hi)):
+        raise ValueError(f"autodetected range of [{lo}, {hi}] is not finite")
+    if lo == hi:
+        lo, hi = lo - 0.5, hi + 0.5
+    with np.errstate(all="ignore"):
+        return np.linspace(lo, hi, bins + 1)
+
+
+def _hist_bins(edges: np.ndarray, v: np.ndarray) -> np.ndarray:
+    """``np.histogramdd``'s bin of every value: ``searchsorted(side='right') - 1``, a value equal to the last edge in the last bin."""
+    b = np.searchsorted(edges, v, side="right")
+    b[v == edges[-1]] -= 1
+    return b - 1
+
+
+def _grid_index(v, lo, hi, bins: int) -> np.ndarray:
+    """The reference's grid index of plotted values (``utils.py:1705-1715``)."""
+    with np.errstate(all="ignore"):
+        vn = np.zeros_like(v) if hi == lo else (v - lo) / (hi - lo)
+        return np.clip((vn * (bins - 1)).astype(int), 0, bins - 1)
+
+
+def _gauss_weights(sigma: float):
+    """``scipy.ndimage``'s Gaussian kernel of ``gaussian_filter(sigma, truncate=4)``: ``(radius, weights[radius:])`` -- the centre's weight first --
+    or ``(0, None)`` where SciPy skips the axis (``sigma <= 1e-15``)."""
+    sigma = float(sigma)
+    if not sigma > 1e-15:
+        if sigma < 0 or sigma != sigma:
+            raise ValueError("grid_sigma must not be negative")
+        return 0, None
+    r = int(4.0 * sigma + 0.5)
+    x = np.arange(-r, r + 1)
+    phi = np.exp(-0.5 / (sigma * sigma) * x ** 2)
+    phi = phi / phi.sum()
+    return r, np.ascontiguousarray(phi[r:])
+
+
+def _eye_record(y, device):
+    """``(signal, noise or None, on_device)`` of the record behind ``y``: DeviceArrays where it lies in GPU memory, one float64 host array else."""
+    from .typing import NULL, electrical_signal
+    complex_error = TypeError("the eye diagram takes a real record: pass `.real` or `.abs()` of a complex signal")
+    if isinstance(y, electrical_signal) and y.on_device:
+        s, n = y._device_arrays()
+        if s.dtype.kind == "c":
+            raise complex_error
+        return s, n, True
+    if _is_device(y):
+        if np.dtype(y.dtype) != np.dtype(np.float64):
+            if np.dtype(y.dtype).kind == "c":
+                raise complex_error
+            raise TypeError(f"the eye diagram takes a float64 device array, not {y.dtype}")
+        if y.ndim != 1:
+            raise ValueError(f"the eye diagram takes a 1-D record, got shape {y.shape}")
+        return y, None, True
+    if isinstance(y, electrical_signal):
+        a = np.asarray(y.signal + y.noise)
+    else:
+        a = np.asarray(y)
+    if a.dtype.kind == "c":
+        raise complex_error
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    if a.ndim != 1:
+        raise ValueError(f"the eye diagram takes a 1-D record, got shape {a.shape}")
+    if device is not None:                                         # an explicit device: the host record is uploaded and computed there
+        return _lib.DeviceArray.from_host(a, device=int(device)), None, True
+    return a, None, False
+
+
+def _eye_density_host(a, start, P, T, B, sigma, X1, colors):
+    from scipy.ndimage import gaussian_filter
+    Y = a[start:start + T * P]
+    X = np.tile(X1, T)
+    min_y, max_y = Y.min(), Y.max()
+    with np.errstate(all="ignore"):
+        counts, xe, ye = np.histogram2d(X, Y, bins=B)
+    grid = gaussian_filter(counts, sigma=sigma)
+    out = dict(grid=grid, counts=counts.astype(np.uint32), xedges=xe, yedges=ye, extent=(X1.min(), X1.max(), min_y, max_y), n_traces=T)
+    if colors:
+        ix, iy = _grid_index(X, X1.min(), X1.max(), B), _grid_index(Y, min_y, max_y, B)
+        c = grid[ix, iy]
+        span = c.max() - c.min()
+        out.update(x=X, y=Y, ix=ix, iy=iy, colors=np.zeros_like(c) if span == 0 else (c - c.min()) / span)
+    return EyeDensity(**out)
+
+
+def _eye_density_device(s, nz, start, P, T, B, sigma, X1, colors, n_traces):
+    import ctypes as C
+    if nz is not None and (nz.device != s.device or nz.shape != s.shape):
+        raise ValueError("signal and noise differ in shape or device")
+    if B > EYE_MAX_BINS:
+        raise ValueError(f"the device path takes N_grid_bins up to {EYE_MAX_BINS}, got {B}")
+    n, sps, nt = s.size, P // 2, -1 if n_traces is None else int(n_traces)
+    rng = (C.c_double * 3)()
+    _lib.api.ssfm_eye_density_range(s, nz, n, sps, nt, rng)
+    flags = int(rng[2])
+    min_y, max_y = (np.float64(np.nan),) * 2 if flags & 1 else (np.float64(rng[0]), np.float64(rng[1]))
+    ye = _hist_edges(min_y, max_y, B)                             # (raises NumPy's error for a range that is not finite: nothing further is launched)
+    if not np.isfinite(ye).all() and B > 1:
+        # max - min overflows: linspace gives [nan, inf, ..., inf, max], the maximum's searchsorted index is 0, its shift makes it -1 and
+        # np.ravel_multi_index refuses it -- the maximum is always among the points, so NumPy always raises here
+        raise ValueError("invalid entry in coordinates array")
+    min_x, max_x = X1.min(), X1.max()
+    xe = _hist_edges(min_x, max_x, B)
+    xbin = np.ascontiguousarray(_hist_bins(xe, X1), dtype=np.int32)
+    r, w = _gauss_weights(sigma)
+    counts = _lib.host_empty((B, B), np.uint32)
+    grid = _lib.host_empty((B, B), np.float64)
+    out = dict(xedges=xe, yedges=ye, extent=(min_x, max_x, min_y, max_y), n_traces=T)
+    points = (None, 0.0, 0.0, None, None, None)                   # no colours: the plotted points stay on the device
+    if colors:
+        xidx = np.ascontiguousarray(_grid_index(X1, min_x, max_x, B), dtype=np.int32)
+        pts, iy, col = (_lib.host_empty((T * P,), dt) for dt in (np.float64, np.int32, np.float64))
+        points = (_lib._ptr(xidx), float(min_y), float(max_y), _lib._ptr(pts), _lib._ptr(iy), _lib._ptr(col))
+    _lib.api.ssfm_eye_density(s, nz, n, sps, nt, B, _lib._ptr(ye), _lib._ptr(xbin), None if w is None else _lib._ptr(w), r, _lib._ptr(counts),
+                              _lib._ptr(grid), *points)
+    _lib.TRANSFERS["d2h"] += 2                                     # counts and grid
+    if colors:
+        _lib.TRANSFERS["d2h"] += 3                                 # the points' values, indices and colours
+        out.update(x=np.tile(X1, T), y=pts, colors=col, ix=np.tile(xidx.astype(np.intp), T), iy=iy.astype(np.intp))
+    return EyeDensity(grid=grid, counts=counts, **out)
+
+
+def eye_density(y, sps, n_traces=None, N_grid_bins=200, grid_sigma=5, *, colors=False, device=None):
+    """The density behind an eye diagram (the computed part of the reference's ``opticomlib.utils.eyediagram``): the record is cut by ``sps // 2``
+    samples at both ends and folded into traces of ``2 sps`` points over the abscissa ``linspace(-1, 1 - 1/sps, 2 sps)``; the result holds
+    ``np.histogram2d(X, Y, bins=N_grid_bins)``, its ``scipy.ndimage.gaussian_filter(sigma=grid_sigma)`` and, with ``colors=True``, each plotted
+    point's normalised grid value.
+
+    ``y``: an ``electrical_signal`` (signal + noise), a float64 ``DeviceArray`` or array_like.  A record in GPU memory is computed there by the
+    kernels of ``csrc/eye_density.hip`` -- only the grid (and with ``colors=True`` the plotted points) comes back; host data is NumPy / SciPy on
+    the host and needs no GPU, unless ``device`` names one.  A complex record raises ``TypeError`` (take ``.real`` or ``.abs()``).
+    ``n_traces``: the most traces to take (default: all).  Returns an :class:`EyeDensity`.
+
+    Raises the reference's ``ValueError`` s for a record too short for the truncation, with fewer than ``2 sps`` points after it, or with no trace
+    to draw, and NumPy's ("autodetected range of [...] is not finite") for a NaN or an infinity among the plotted points.  On the device
+    ``N_grid_bins <= 4096`` and the record holds at most 2^31 samples."""
+    sps, B = int(sps), int(N_grid_bins)
+    if sps < 1:
+        raise ValueError(f"sps must be a positive integer, got {sps}")
+    if B < 1:
+        raise ValueError("`bins[0]` must be positive, when an integer")
+    s, nz, on_device = _eye_record(y, device)
+    start, P, T = _eye_geometry(int(s.size), sps, n_traces)
+    X1 = np.linspace(-1, 1 - 1 / sps, P)
+    if on_device:
+        if device is not None and int(device) != s.device:
+            raise ValueError(f"the record lies on GPU {s.device}, not on GPU {int(device)}")
+        return _eye_density_device(s, nz, start, P, T, B, grid_sigma, X1, colors, n_traces)
+    return _eye_density_host(s, start, P, T, B, grid_sigma, X1, colors)
+
+
+def eyediagram(y, sps, n_traces=None, cmap='viridis', N_grid_bins=200, grid_sigma=5, style='dot', ax=None, **plot_kw):
+    """Plot a coloured eye diagram (reference ``opticomlib.utils.eyediagram``) from :func:`eye_density`, which computes where the record lies.
+
+    ``style``: ``'dot'`` one scatter of the points coloured by density (``s`` 0.1, ``alpha`` 0.9), ``'line'`` one ``LineCollection`` per trace
+    (``linewidth`` 1, ``alpha`` 0.05, ``capstyle`` / ``joinstyle`` 'round'), ``'density'`` the blurred grid alone (``imshow``).  ``plot_kw``:
+    ``figsize``, ``dpi`` (100) for a new figure; ``xlabel``, ``ylabel``, ``title`` (``"Eye Diagram ({num_traces} traces)"``), ``grid`` (True),
+    ``grid_alpha`` (0.3), ``xlim`` ((-1, 1)), ``ylim`` ((min_y, max_y)), ``tight_layout`` (True), ``show`` (False) -- the defaults the reference's
+    code uses.  Everything is drawn on ``ax`` (a new figure's axes when None).  Returns the axes."""
+    from .typing import electrical_signal
+    sps = int(sps)
+    size = y.size if isinstance(y, electrical_signal) or _is_device(y) else len(y)
+    _eye_geometry(int(size), sps, n_traces)                        # the reference's errors, in its order, before anything is computed
+    if style not in _EYE_STYLES:
+        raise ValueError(f"Invalid style '{style}'. Choose from 'line', 'dot', or 'density'.")
+    import matplotlib.pyplot as plt
+    try:
+        cmap_obj = getattr(plt.cm, cmap)
+    except AttributeError:
+        warnings.warn(f"Colormap '{cmap}' not found. Using 'viridis' by default.")
+        cmap_obj = plt.cm.viridis
+    d = eye_density(y, sps, n_traces, N_grid_bins, grid_sigma, colors=style != 'density')
+    min_x, max_x, min_y, max_y = d.extent
+    created = ax is None
+    if created:
+        _, ax = plt.subplots(figsize=plot_kw.get('figsize', None), dpi=plot_kw.get('dpi', 100))
+    if style == 'dot':
+        ax.scatter(d.x, d.y, c=d.colors, cmap=cmap_obj, s=plot_kw.get('s', 0.1), alpha=plot_kw.get('alpha', 0.9))
+    elif style == 'density':
+        ax.imshow(d.grid.T, extent=[min_x, max_x, min_y, max_y], origin='lower', aspect='auto', cmap=cmap_obj)
+    else:
+        from matplotlib.collections import LineCollection
+        P = 2 * sps
+        Y, col = d.y.reshape(d.n_traces, P), d.colors.reshape(d.n_traces, P)
+        for i in range(d.n_traces):
+            points = np.array([d.x[:P], Y[i]]).T.reshape(-1, 1, 2)
+            segments = np.concatenate([points[:-1], points[1:]], axis=1)
+            if len(segments) > 0:
+                ax.add_collection(LineCollection(segments, colors=cmap_obj(col[i][:len(segments)]), linewidth=plot_kw.get('linewidth', 1),
+                                                 alpha=plot_kw.get('alpha', 0.05), capstyle=plot_kw.get('capstyle', 'round'),
+                                                 joinstyle=plot_kw.get('joinstyle', 'round')))
+    xlim, ylim = plot_kw.get('xlim', None), plot_kw.get('ylim', None)
+    ax.set_xlim(xlim if xlim is not None else (-1, 1))
+    ax.set_ylim(ylim if ylim is not None else (min_y, max_y))
+    ax.set_xlabel(plot_kw.get('xlabel', "Time (2-symbol segment)"))
+    ax.set_ylabel(plot_kw.get('ylabel', "Amplitude"))
+    ax.set_title(plot_kw.get('title', "Eye Diagram ({num_traces} traces)").format(num_traces=d.n_traces))
+    if plot_kw.get('grid', True):
+        ax.grid(True, alpha=plot_kw.get('grid_alpha', 0.3))
+    if created and plot_kw.get('tight_layout', True):
+        plt.tight_layout()
+    if created and plot_kw.get('show', False):
+        plt.show()
+    return ax
+
+
+__all__ = ["get_psd", "eye_density", "eyediagram", "EyeDensity"]
