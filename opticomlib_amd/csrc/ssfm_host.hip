@@ -951,6 +951,9 @@ template <typename T> struct PlanT : PlanBase {
         HIP_TRY(hipMalloc(&F, cb * n * batch));
         HIP_TRY(hipMalloc(&P, sizeof(T) * n * batch));
         u16 = u16_layout<T>(N1, cols_per_tile<T>(), E);
+        // the unit layout orders the field between the two kernels by N2 / Ef (k_time's Qf): rows of k_freq<FM_FLY> with another number of points per
+        // thread would pair every spectrum bin with another bin's operator (SSFM_EF_FLY != Ef: tests/test_fft_edges_gpu.py, part C) -- such plans keep Ef
+        if (u16) Ef_fly = Ef;
         Y = F;
         if (u16) HIP_TRY(hipMalloc(&Y, cb * n * batch));
         // inter-pass twiddles W_N^(k1 n2): either the n-entry table in k_time's thread order, or (U16 plans) the two

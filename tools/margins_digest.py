@@ -6,7 +6,12 @@
 
 A kind is the record's `what` with the size (`n=...`), the tap count, the chunk size (`chunk=...`) and the fixture's case name taken out; its row carries the record with the
 largest measured / bound of that kind, and how many records it stands for.  A third argument names a file whose text replaces the header's
-description (it follows the record count; further lines start with `#`)."""
+description (it follows the record count; further lines start with `#`).
+
+    python tools/margins_digest.py --table raw.txt profiles/fft_margins.txt tools/fft_margins_head.txt
+
+`--table` (records whose `what` is "<section> <shape> <comparison>", tests/test_fft_edges_gpu.py): one line per shape instead of one per kind, the
+comparisons side by side as columns of measured / bound, the columns named once per section."""
 import collections
 import re
 import sys
@@ -45,5 +50,37 @@ def main(src, dst, head=HEAD):
     print(total, "records,", len(rows), "kinds ->", dst)
 
 
+# --table: what -> (section, shape, comparison)
+TABLE = (r"^(A|B) (log2n=\d+ c\d+ E=\d+ Ef=\d+(?: \(default\))?) (.*)$", r"^(B split) (log2n=\d+ c\d+ R=\d+) (.*)$", r"^(C) (.*? log2n=\d+ c\d+) (.*)$",
+         r"^(D) (len=\d+) (.*)$")
+
+
+def table(src, dst, head=HEAD):
+    sections, total = collections.OrderedDict(), 0          # section -> (columns, shape -> {column: worst ratio})
+    for line in open(src):
+        if line.startswith("#") or not line.strip():
+            continue
+        what, _steps, measured, bound, _ratio = line.rstrip("\n").split(" | ", 1)[1].rsplit(" | ", 4)
+        m = next(filter(None, (re.match(rx, what.strip()) for rx in TABLE[1:] + TABLE[:1])))
+        sec, shape, col = m.groups()
+        cols, rows = sections.setdefault(sec, ([], collections.OrderedDict()))
+        if col not in cols:
+            cols.append(col)
+        r = float(measured) / float(bound)
+        row = rows.setdefault(shape, {})
+        row[col] = max(row.get(col, 0.0), r)
+        total += 1
+    with open(dst, "w") as f:
+        f.write(f"# {total} " + head)
+        for sec, (cols, rows) in sections.items():
+            f.write(f"# section {sec}: measured / bound, columns:\n" + "".join(f"#   {i + 1:2d} {c}\n" for i, c in enumerate(cols)))
+            for shape, row in rows.items():
+                f.write(f"{sec} {shape} | " + " ".join(f"{row[c]:.3g}" if c in row else "-" for c in cols) + "\n")
+    print(total, "records ->", dst)
+
+
 if __name__ == "__main__":
+    if sys.argv[1] == "--table":
+        table(sys.argv[2], sys.argv[3], *([open(sys.argv[4]).read()] if len(sys.argv) > 4 else []))
+        sys.exit(0)
     main(sys.argv[1], sys.argv[2], *([open(sys.argv[3]).read()] if len(sys.argv) > 3 else []))
