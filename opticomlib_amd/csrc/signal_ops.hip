@@ -2,7 +2,10 @@
 // or a signal and a scalar with the reference's signal / noise rules in one pass, the unary and scalar operations, comparison, slicing, the
 // reductions behind power / normalize / sum, unwrap(angle(.)) and the two pointwise ends of filter().  float64 and complex128, (rows, n) with rows = 1.
 // The ssfm_field_* entry points at the end are the same algebra for optical_signal (typing.py:2103-2320): rows = 1 or 2, operands that broadcast
-// along either axis, and complex64 beside the two double-precision types.
+// along either axis, and complex64 beside the two double-precision types.  A signal is the field of one row to the slice and the row
+// reductions: ssfm_signal_slice launches k_field_slice with row0 = 0, and ssfm_signal_reduce and ssfm_field_reduce share reduce_rows (one
+// launch of k_field_reduce, the partials folded on the host), each behind its own argument checks.  The binary entry points stay apart:
+// k_signal_binary_c<C1, C2> reads a float64 operand straight into a complex128 result, k_field_binary takes both operands in the result's type.
 //
 // All of them are bandwidth-bound streaming kernels: 16 bytes per lane and access (a complex128 value, or two float64 values), a grid of at most
 // 256 CUs x 8 workgroups with a grid-stride loop, wavefront shuffles and four LDS words per workgroup for the reductions.  The whole file is
@@ -302,17 +305,6 @@ __global__ __launch_bounds__(256) void k_signal_unary_cr(int op, long long n, co
     }
 }
 
-// ---------------------------------------------------------------------------------------------- slicing
-template <typename T>
-__global__ __launch_bounds__(256) void k_signal_slice(const T* __restrict__ s, const T* __restrict__ nz, long long start, long long step, long long count,
-                                                      T* __restrict__ out_s, T* __restrict__ out_n) {
-    for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (long long)gridDim.x * blockDim.x) {
-        const long long k = start + i * step;
-        out_s[i] = s[k];
-        if (nz) out_n[i] = nz[k];
-    }
-}
-
 // ---------------------------------------------------------------------------------------------- reductions
 // One pair of partial sums per workgroup: lanes by shuffles, the four wavefronts through four LDS words (the scheme of k_sum / k_min in
 // device_mem.hip).  The grid depends on n alone and the host folds the partials in order, so a result is the same bits every time.
@@ -362,11 +354,7 @@ __device__ __forceinline__ void reduce_row(int kind, int cplx, const double* __r
         partial[2 * blockIdx.x + 1] = w[4] + w[5] + w[6] + w[7];
     }
 }
-__global__ __launch_bounds__(256) void k_signal_reduce(int kind, int cplx, const double* __restrict__ s, const double* __restrict__ nz, long long n,
-                                                       double* __restrict__ partial) {
-    reduce_row(kind, cplx, s, nz, n, partial);
-}
-// blockIdx.y: the row of a (rows, n) field; its partials follow those of the rows before it
+// blockIdx.y: the row of a (rows, n) field (a signal is the field of one row); its partials follow those of the rows before it
 __global__ __launch_bounds__(256) void k_field_reduce(int kind, int cplx, const double* __restrict__ s, const double* __restrict__ nz, long long n,
                                                       double* __restrict__ partial) {
     const long long off = (long long)blockIdx.y * n * (cplx ? 2 : 1);
@@ -542,7 +530,9 @@ __global__ __launch_bounds__(256) void k_field_unary_cf(int op, long long count,
     }
 }
 
-// out[r][i] = in[row0 + r][start + i step] of signal and noise (typing.py:2261-2305); T: a value of 8 or of 16 bytes
+// ---------------------------------------------------------------------------------------------- slicing
+// out[r][i] = in[row0 + r][start + i step] of signal and noise (typing.py:1366-1376, :2261-2305; a signal is row 0 of one row); T: a value of 8 or
+// of 16 bytes
 template <typename T>
 __global__ __launch_bounds__(256) void k_field_slice(const T* __restrict__ s, const T* __restrict__ nz, long long n, long long row0, long long start, long long step,
                                                      long long count, T* __restrict__ out_s, T* __restrict__ out_n) {
@@ -583,6 +573,23 @@ void fold_partials(int kind, const double* host, int blocks, int64_t n, double* 
     if (kind == SSFM_SIGNAL_POWER) a0 /= (double)n;
     out[0] = a0;
     if (kind == SSFM_SIGNAL_SUM) out[1] = a1;
+}
+
+// ssfm_signal_reduce and ssfm_field_reduce behind their own checks: every row of a (rows, n) array in one launch of k_field_reduce, the partials
+// read back and folded, two results per row.  The grid depends on n alone, so a row's result does not depend on how many rows there are.
+int reduce_rows(const char* what, int device, int kind, int64_t rows, int64_t n, const void* signal, const void* noise, int is_complex, double* out) {
+    constexpr int kBlocks = 1024, kMaxRows = 2;
+    const int blocks = (int)grid_for(is_complex ? n : (n + 1) / 2, kBlocks);
+    const size_t bytes = sizeof(double) * 2 * kBlocks * rows;
+    double* partial = nullptr;
+    if (int rc = ssfm_device_alloc(device, bytes, (void**)&partial)) return rc;
+    hipLaunchKernelGGL(k_field_reduce, dim3(blocks, (unsigned)rows), dim3(256), 0, 0, kind, is_complex, (const double*)signal, (const double*)noise, (long long)n, partial);
+    static thread_local double host[2 * kBlocks * kMaxRows];
+    hipError_t e = hipMemcpy(host, partial, sizeof(double) * 2 * blocks * rows, hipMemcpyDeviceToHost);
+    (void)ssfm_device_free(device, partial, bytes);
+    if (e != hipSuccess) return fail(SSFM_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+    for (int64_t r = 0; r < rows; ++r) fold_partials(kind, host + 2 * blocks * r, blocks, n, out + 2 * r);
+    return SSFM_OK;
 }
 
 }  // namespace
@@ -665,11 +672,11 @@ extern "C" int ssfm_signal_slice(int64_t rows, int64_t n, const void* signal, co
     if (int rc = device_of(signal, &device)) return rc;
     const dim3 grid(grid_for(count, kGridCap));
     if (is_complex)
-        hipLaunchKernelGGL(k_signal_slice<double2>, grid, dim3(256), 0, 0, (const double2*)signal, (const double2*)noise, (long long)start, (long long)step,
-                           (long long)count, (double2*)out_signal, (double2*)out_noise);
+        hipLaunchKernelGGL(k_field_slice<double2>, grid, dim3(256), 0, 0, (const double2*)signal, (const double2*)noise, (long long)n, 0ll, (long long)start,
+                           (long long)step, (long long)count, (double2*)out_signal, (double2*)out_noise);
     else
-        hipLaunchKernelGGL(k_signal_slice<double>, grid, dim3(256), 0, 0, (const double*)signal, (const double*)noise, (long long)start, (long long)step,
-                           (long long)count, (double*)out_signal, (double*)out_noise);
+        hipLaunchKernelGGL(k_field_slice<double>, grid, dim3(256), 0, 0, (const double*)signal, (const double*)noise, (long long)n, 0ll, (long long)start,
+                           (long long)step, (long long)count, (double*)out_signal, (double*)out_noise);
     return finish("ssfm_signal_slice");
 }
 
@@ -680,17 +687,7 @@ extern "C" int ssfm_signal_reduce(int kind, int64_t rows, int64_t n, const void*
     if (int rc = device_of(signal, &device)) return rc;
     if (kind == SSFM_SIGNAL_POWER && !noise)        // the power of one array is ssfm_device_reduce's
         return ssfm_device_reduce(device, SSFM_REDUCE_POWER, signal, nullptr, 1, n, is_complex, out);
-    constexpr int kBlocks = 1024;
-    const int blocks = (int)grid_for(is_complex ? n : (n + 1) / 2, kBlocks);
-    double* partial = nullptr;
-    if (int rc = ssfm_device_alloc(device, sizeof(double) * 2 * kBlocks, (void**)&partial)) return rc;
-    hipLaunchKernelGGL(k_signal_reduce, dim3(blocks), dim3(256), 0, 0, kind, is_complex, (const double*)signal, (const double*)noise, (long long)n, partial);
-    static thread_local double host[2 * kBlocks];
-    hipError_t e = hipMemcpy(host, partial, sizeof(double) * 2 * blocks, hipMemcpyDeviceToHost);
-    (void)ssfm_device_free(device, partial, sizeof(double) * 2 * kBlocks);
-    if (e != hipSuccess) return fail(SSFM_ERR_HIP, "ssfm_signal_reduce: %s", hipGetErrorString(e));
-    fold_partials(kind, host, blocks, n, out);
-    return SSFM_OK;
+    return reduce_rows("ssfm_signal_reduce", device, kind, 1, n, signal, noise, is_complex, out);
 }
 
 extern "C" int ssfm_signal_phase(int64_t rows, int64_t n, const void* signal, const void* noise, int is_complex, double* out) {
@@ -819,18 +816,8 @@ extern "C" int ssfm_field_reduce(int kind, int64_t rows, int64_t n, const void* 
     int device = 0;
     if (int rc = ssfm::device_of(signal, "ssfm_field_*", &device)) return rc;
     if (noise && !same_device(noise, device)) return fail(SSFM_ERR_INVALID, "ssfm_field_reduce: signal and noise lie on different devices");
-    constexpr int kBlocks = 1024;
-    const int blocks = (int)grid_for(is_complex ? n : (n + 1) / 2, kBlocks);
-    double* partial = nullptr;
-    if (int rc = ssfm_device_alloc(device, sizeof(double) * 4 * kBlocks, (void**)&partial)) return rc;
-    hipLaunchKernelGGL(k_field_reduce, dim3(blocks, (unsigned)rows), dim3(256), 0, 0, kind, is_complex, (const double*)signal, (const double*)noise, (long long)n, partial);
-    static thread_local double host[4 * kBlocks];
-    hipError_t e = hipMemcpy(host, partial, sizeof(double) * 2 * blocks * rows, hipMemcpyDeviceToHost);
-    (void)ssfm_device_free(device, partial, sizeof(double) * 4 * kBlocks);
-    if (e != hipSuccess) return fail(SSFM_ERR_HIP, "ssfm_field_reduce: %s", hipGetErrorString(e));
-    for (int64_t r = 0; r < rows; ++r) {
-        out[2 * r + 1] = 0.0;
-        fold_partials(kind, host + 2 * blocks * r, blocks, n, out + 2 * r);
-    }
+    if (int rc = reduce_rows("ssfm_field_reduce", device, kind, rows, n, signal, noise, is_complex, out)) return rc;
+    if (kind != SSFM_SIGNAL_SUM)        // (the second result of a row is the sum's imaginary part; 0 for the others)
+        for (int64_t r = 0; r < rows; ++r) out[2 * r + 1] = 0.0;
     return SSFM_OK;
 }

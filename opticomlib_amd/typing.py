@@ -11,6 +11,13 @@
 ``electrical_signal.psd()`` / ``optical_signal.psd()`` plot the Welch spectrum of :func:`opticomlib_amd.get_psd` (computed on the
 GPU; matplotlib is imported when the method is called).  :class:`electrical_signal` has the reference's operators and methods, computed
 where the signal lies, and so has :class:`optical_signal`.  The other plots, eye diagrams etc. are out of scope.
+
+The two signal classes are the direct subclasses of the private :class:`_signal_base` (neither is the other's subclass, unlike the
+reference's): the base has the storage, the metadata, the reads and protocols and every operator and method the two share, each class the
+hooks that build, wrap and launch (``_make``, ``_wrap``, ``_parse``, ``_binary_device``, ``_unary_device``, ``_reduce_device``,
+``_div_device``, ``_pow_device``, ``_filter_device``, ``__getitem__``) and the members that really differ.  The different-GPUs check, a
+slice key's ``(start, step, count)`` and an integer index's bounds check are module-level functions that :class:`binary_sequence` shares.
+The HIP binding is imported inside the functions that launch, never at module level: a host-only operation loads no device.
 """
 from __future__ import annotations
 
@@ -134,6 +141,27 @@ class _LazyArray:
         obj.__dict__[self.slot] = value
 
 
+def _one_gpu(what, devices):
+    """The one GPU among ``devices`` (those of the operands that lie on one), or None; operands ``what`` on two GPUs are a ``ValueError``."""
+    devs = set(devices)
+    if len(devs) > 1:
+        raise ValueError(f"Can't operate {what} that lie on different GPUs {sorted(devs)}: move one of them first")
+    return devs.pop() if devs else None
+
+
+def _slice_span(key, size):
+    """``(start, step, count)`` of a slice of ``size`` values, clipped as Python clips it (``count`` may be 0)."""
+    start, stop, step = key.indices(size)
+    return start, step, len(range(start, stop, step))
+
+
+def _checked_index(key, size, axis=0):
+    """An integer index into ``size`` values as a position from the front, or NumPy's ``IndexError``."""
+    if not -size <= key < size:
+        raise IndexError(f"index {key} is out of bounds for axis {axis} with size {size}")
+    return int(key) % size
+
+
 class binary_sequence:
     """Bit sequence (uint8 0 / 1) with the algebra of the reference's class (``typing.py:402-1009``): ``~``, ``&``, ``|``, ``^``, ``!=`` (a
     ``binary_sequence`` mask of the differences), ``+`` (concatenation, either order), ``*`` (an ``int`` above 1 tiles, anything else is ``&``),
@@ -254,10 +282,7 @@ class binary_sequence:
     def _pair(self, other):
         """``(other as a sequence, the GPU the operation runs on or None)``; the lengths are equal or one of them is 1."""
         o = other if isinstance(other, binary_sequence) else binary_sequence(other)
-        devs = {x._raw().device for x in (self, o) if x.on_device}
-        if len(devs) > 1:
-            raise ValueError(f"Can't operate binary_sequences that lie on different GPUs {sorted(devs)}: move one of them first")
-        return o, (devs.pop() if devs else None)
+        return o, _one_gpu("binary_sequences", (x._raw().device for x in (self, o) if x.on_device))
 
     def _check_lengths(self, o):
         if self.size != o.size and 1 not in (self.size, o.size):
@@ -348,11 +373,8 @@ class binary_sequence:
         if _is_device(raw) and isinstance(key, (int, np.integer, slice)) and not isinstance(key, (bool, np.bool_)):
             from . import _lib
             if isinstance(key, slice):
-                start, stop, step = key.indices(raw.size)
-                return binary_sequence.from_device(_lib.bits_slice_device(raw, start, step, len(range(start, stop, step))))
-            if not -raw.size <= key < raw.size:
-                raise IndexError(f"index {key} is out of bounds for axis 0 with size {raw.size}")
-            return _lib.bits_count_device(raw, int(key) % raw.size, 1)
+                return binary_sequence.from_device(_lib.bits_slice_device(raw, *_slice_span(key, raw.size)))
+            return _lib.bits_count_device(raw, _checked_index(key, raw.size), 1)
         r = self.data[key]
         return binary_sequence(r) if isinstance(r, np.ndarray) else int(r)
 
@@ -407,483 +429,18 @@ class binary_sequence:
         return electrical_signal(sg.fftconvolve(xu, h, mode="same"))
 
 
-class electrical_signal:
-    """1-D electrical signal with optional noise and the algebra of the reference's class (``typing.py:1022-1780``).
-
-    ``+ - * / // **``, ``[]``, ``> < ==``, unary ``-``, ``abs``, ``power``, ``normalize``, ``phase``, ``conj``, ``sum``, ``filter``, ``w``,
-    ``f``, ``t``, ``fs``, ``sps``, ``dt``, ``real``, ``imag`` and the NumPy protocols ``__array__`` / ``__array_ufunc__`` carry the reference's
-    names, argument checks, error texts and signal / noise rules.
-
-    Residency: an operation on a signal that lies in GPU memory (``on_device``: what ``PD``, ``LPF``, ``ADC``, ``DAC`` and ``SAMPLER``
-    return) is computed there by the HIP kernels of ``csrc/signal_ops.hip`` and its result lies there too; a Python scalar is a kernel
-    argument, a host array or host signal as the other operand is uploaded once, two signals on different GPUs are a ``ValueError``.
-    Device arrays are float64 or complex128; any other device type raises ``TypeError``.  An operation on a host-only signal is NumPy on
-    the host, as in the reference, and loads no device.  ``power``, ``sum`` and an integer index of a noiseless signal return host scalars;
-    ``==`` returns a host bool array, ``>`` / ``<`` a ``binary_sequence`` (device-resident for device operands).  ``np.asarray(x)``,
-    iteration and a NumPy ufunc other than the three reflected operators and ``np.abs`` materialise the signal on the host.
-
-    On the device, ``filter`` with real signal, noise and taps carries the noise as the imaginary part of the signal's field through one
-    convolution: a noise below ``1e-12`` of the signal loses its digits on that path.  ``**`` of a complex128 device signal takes the
-    exponents NumPy computes by products (integers ``|p| < 100``) and ``0.5``; another exponent raises ``ValueError``.
-
-    Not provided: ``plot``, ``print``, ``grid``, ``legend``, ``show``, ``sizeof``, the reference's ``__getattr__`` delegation
-    to ``ndarray`` and ``__array_function__``."""
-
-    signal = _LazyArray()
-    noise = _LazyArray()
-    __hash__ = None                  # (an `__eq__` that returns an array: unhashable, as the reference's class)
-
-    @classmethod
-    def from_device(cls, signal, noise=NULL):
-        """Wrap device-resident 1-D arrays without copying them to the host."""
-        self = cls.__new__(cls)
-        if signal.ndim != 1 or (noise is not NULL and noise.shape != signal.shape):
-            raise ValueError(f"Signal must be 1D array for electrical_signal, invalid shape {signal.shape}")
-        self.signal, self.noise = signal, noise
-        self.execution_time = 0.0
-        return self
-
-    def _raw(self, name):
-        return self.__dict__.get("_" + name, NULL)
-
-    def __init__(self, signal, noise=NULL, dtype=None):
-        if isinstance(signal, electrical_signal):
-            noise = signal.noise if noise is NULL else np.asarray(noise) + signal.noise
-            signal = signal.signal
-        sig = np.asarray(signal)
-        noi = noise
-        if noi is not NULL:
-            noi = np.asarray(noi)
-            common = np.result_type(sig, noi) if dtype is None else dtype
-            sig, noi = sig.astype(common, copy=False), noi.astype(common, copy=False)
-            if sig.shape != noi.shape:
-                raise ValueError(f"`signal` and `noise` must have the same shape, mismatch shapes {sig.shape} and {noi.shape}!")
-        elif dtype is not None:
-            sig = sig.astype(dtype, copy=False)
-        if sig.ndim > 1 or sig.size < 1:
-            raise ValueError(f"Signal must be scalar or 1D array for electrical_signal, invalid shape {sig.shape}")
-        if sig.ndim == 0:
-            sig = sig[np.newaxis]
-            if noi is not NULL:
-                noi = noi[np.newaxis]
-        self.signal = sig
-        self.noise = noi
-        self.execution_time = 0.0
-
-    # -- metadata (no transfer)
-    @property
-    def size(self) -> int:
-        return int(self._raw("signal").size)
-
-    @property
-    def ndim(self) -> int:
-        return self._raw("signal").ndim
-
-    @property
-    def shape(self):
-        return tuple(self._raw("signal").shape)
-
-    @property
-    def on_device(self) -> bool:
-        """True while ``signal`` lives in GPU memory only (no host copy has been asked for)."""
-        return _is_device(self._raw("signal"))
-
-    @property
-    def type(self):
-        return type(self)
-
-    @property
-    def fs(self):
-        return gv.fs
-
-    @property
-    def sps(self):
-        return gv.sps
-
-    @property
-    def dt(self):
-        return gv.dt
-
-    @property
-    def t(self):
-        return gv.t[:self.size]
-
-    def __len__(self):
-        return self.size
-
-    def __iter__(self):
-        return iter(self.__array__())
-
-    def __array__(self, dtype=None, copy=None):
-        arr = self.signal + self.noise
-        return arr if dtype is None else arr.astype(dtype)
-
-    def to_numpy(self) -> np.ndarray:
-        return np.asarray(self.signal + self.noise)
-
-    def w(self, shift: bool = False) -> np.ndarray:
-        """Angular frequency grid [rad/s], FFT order (reference ``typing.py:1628-1644``)."""
-        w = np.fft.fftfreq(self.size, gv.dt) * 2 * np.pi
-        return np.fft.fftshift(w, axes=-1) if shift else w
-
-    def f(self, shift: bool = False) -> np.ndarray:
-        """Frequency grid [Hz] (reference ``typing.py:1646-1660``)."""
-        return self.w(shift) / (2 * np.pi)
-
-    def __call__(self, domain, shift: bool = False):
-        """New object holding the FFT (``'w'`` / ``'f'``) or inverse FFT (``'t'``) of signal and noise along the last axis
-        (reference ``typing.py:1421-1462``); ``shift`` applies fftshift / ifftshift.  Computed on the GPU."""
-        from . import devices
-        return devices._fourier(self, domain, shift)
-
-    def psd(self, fmt='-', mode='x', n=None, xlabel=None, ylabel=None, yscale='dbm', grid=False, hold=True, show=False, **kwargs):
-        """Plot the power spectral density (reference ``typing.py:1850-1970``): Welch's estimate of the first ``n`` samples
-        (default ``min(size, gv.t.size)``) with ``nperseg = min(2048, n)`` at ``fs = gv.fs * 1e-9`` [GHz], computed on the GPU.
-        ``yscale``: ``'dbm'`` or ``'linear'`` (mW); ``mode``: ``'x'``, ``'y'`` or ``'both'`` polarisations.  Returns ``self``."""
-        from .utils import plot_psd
-        return plot_psd(self, fmt, mode, n, xlabel, ylabel, yscale, grid, hold, show, **kwargs)
-
-    MAX_EYE_TRACES = 4096
-
-    def plot_eye(self, n_traces=None, cmap='jet', N_grid_bins=200, grid_sigma=5, style='dot', ax=None, **plot_kw):
-        """Plot the eye diagram of signal + noise with ``gv.sps`` samples per symbol (reference ``typing.py:1971-2041``): at most
-        ``min(n_traces, 4096)`` traces, the density computed where the signal lies (``utils.eyediagram`` has the styles and ``plot_kw``).
-        Returns ``self``."""
-        from .utils import eyediagram
-        n_traces = self.MAX_EYE_TRACES if n_traces is None else min(n_traces, self.MAX_EYE_TRACES)
-        eyediagram(self, gv.sps, n_traces, cmap, N_grid_bins, grid_sigma, style, ax, **plot_kw)
-        return self
-
-    def __repr__(self):
-        where = " [device]" if self.on_device else ""
-        return f"electrical_signal(size={self.size}, dtype={self._raw('signal').dtype}, noise={'NULL' if self._raw('noise') is NULL else 'array'}){where}"
-
-    # -- device plumbing: the arrays where they lie, uploads of the other operand, launches
-    def _device_arrays(self):
-        """``(signal, noise or None)`` as float64 / complex128 DeviceArrays of one type on one GPU, for a device-resident signal."""
-        from . import _lib
-        s, n = self._raw("signal"), self._raw("noise")
-        if s.dtype not in _DEVICE_DTYPES:
-            raise TypeError(f"electrical_signal: the device algebra takes float64 and complex128, this signal lies on the GPU as {s.dtype}; "
-                            "there is no host fallback for a device-resident signal (convert it, or take .to_numpy())")
-        if n is NULL:
-            return s, None
-        if not _is_device(n):                                   # (a noise that was assigned on the host afterwards)
-            n = _lib.DeviceArray.from_host(np.ascontiguousarray(n, dtype=s.dtype), None, s.device)
-        elif n.dtype != s.dtype or n.device != s.device:
-            raise TypeError(f"electrical_signal: signal ({s.dtype}, GPU {s.device}) and noise ({n.dtype}, GPU {n.device}) differ")
-        return s, n
-
-    def _upload(self, dev):
-        """This host signal's arrays on GPU ``dev`` as float64 / complex128 (the widening ``np.result_type`` would apply anyway)."""
-        from . import _lib
-        s = np.asarray(self.signal)
-        dt = np.complex128 if s.dtype.kind == "c" else np.float64
-        up = lambda a: _lib.DeviceArray.from_host(np.ascontiguousarray(a, dtype=dt), None, dev)       # noqa: E731
-        return up(s), (None if self.noise is NULL else up(self.noise))
-
-    def _wrap(self, s, n=None):
-        return self.__class__.from_device(s, NULL if n is None else n)
-
-    def _shapes_error(self, other):
-        return ValueError(f"Can't operate '{self.__class__.__name__}'s with shapes {self.shape} and {other.shape}")
-
-    def _parse(self, other):
-        """The other operand as a signal of this class whose size is this one's or 1 (reference ``typing.py:1557-1573``)."""
-        if not isinstance(other, self.type):
-            other = self.__class__(other)
-        if self.size != other.size and min(self.size, other.size) != 1:
-            raise self._shapes_error(other)
-        return other
-
-    def _binary(self, op, other):
-        """``op``: 'add', 'sub', 'rsub', 'mul', 'gt' or 'eq' between this signal and ``other``, where the operands lie."""
-        other_dev = isinstance(other, electrical_signal) and other.on_device
-        if self.on_device or other_dev:
-            return self._binary_device(op, other)
-        o = self._parse(other)
-        s1, n1, s2, n2 = self.signal, self.noise, o.signal, o.noise
-        if op in ("gt", "eq"):
-            x, y = s1 + n1, s2 + n2
-            return binary_sequence(x > y) if op == "gt" else x == y
-        return _host_binary(self.__class__, op, s1, n1, s2, n2)
-
-    def _binary_device(self, op, other):
-        from . import _lib
-        scalar = None
-        if isinstance(other, (numbers.Number, np.number, np.bool_)):
-            scalar = complex(other) if isinstance(other, (complex, np.complexfloating)) else float(other)
-            size2, o = 1, None
-        else:
-            # (any electrical_signal is used where it lies, whatever its class: the constructor would read it to the host; the result is self's class)
-            o = other if isinstance(other, electrical_signal) else self.__class__(other)
-            size2 = o.size
-        n = max(self.size, size2)
-        if self.size != size2 and min(self.size, size2) != 1:
-            raise self._shapes_error(o)
-        devs = {x._raw("signal").device for x in (self, o) if x is not None and x.on_device}
-        if len(devs) > 1:
-            raise ValueError(f"Can't operate '{self.__class__.__name__}'s that lie on different GPUs {sorted(devs)}: move one of them first")
-        dev = devs.pop()
-        s1, n1 = self._device_arrays() if self.on_device else self._upload(dev)
-        s2 = n2 = None
-        if o is not None:
-            s2, n2 = o._device_arrays() if o.on_device else o._upload(dev)
-        c1 = s1.dtype.kind == "c"
-        c2 = isinstance(scalar, complex) if o is None else s2.dtype.kind == "c"
-        if op in ("gt", "eq"):
-            out = _lib.DeviceArray((n,), np.uint8, dev)
-            out_n = None
-        else:
-            # the reference adds the noises with NULL as the identity, so a lone noise of size 1 meets a signal of size n in the constructor
-            if op != "mul" and (n1 is None) != (n2 is None) and (n1 if n2 is None else n2).size != n:
-                raise ValueError(f"`signal` and `noise` must have the same shape, mismatch shapes {(n,)} and {(1,)}!")
-            dt = np.complex128 if (c1 or c2) else np.float64
-            out = _lib.DeviceArray((n,), dt, dev)
-            out_n = _lib.DeviceArray((n,), dt, dev) if (n1 is not None or n2 is not None) else None
-        z = complex(scalar) if scalar is not None else 0j
-        _lib.api.ssfm_signal_binary(_BINARY[op], 1, n, s1, n1, s1.size, int(c1), s2, n2, size2, int(c2), z.real, z.imag, out, out_n)
-        if op == "gt":
-            return binary_sequence.from_device(out)
-        if op == "eq":
-            return out.to_host().astype(bool)
-        return self._wrap(out, out_n)
-
-    def _unary_device(self, op, p=0.0, *, real_out=False, single=False, complex_out=False):
-        """One launch of ``ssfm_signal_unary``; ``single``: one result array without noise."""
-        from . import _lib
-        s, n = self._device_arrays()
-        cplx = s.dtype.kind == "c"
-        dt = np.float64 if real_out else (np.complex128 if (cplx or complex_out) else np.float64)
-        out = _lib.DeviceArray(s.shape, dt, s.device)
-        out_n = None if (single or n is None) else _lib.DeviceArray(s.shape, dt, s.device)
-        z = complex(p)
-        _lib.api.ssfm_signal_unary(_UNARY[op], 1, s.size, s, n, int(cplx), z.real, z.imag, int(isinstance(p, (complex, np.complexfloating))), out, out_n)
-        return self._wrap(out, out_n)
-
-    # -- operators (reference typing.py:1308-1419)
-    def __add__(self, other):
-        return self._binary("add", other)
-
-    def __radd__(self, other):
-        return self._binary("add", other)
-
-    def __sub__(self, other):
-        return self._binary("sub", other)
-
-    def __rsub__(self, other):
-        return self._binary("rsub", other)
-
-    def __mul__(self, other):
-        return self._binary("mul", other)
-
-    def __rmul__(self, other):
-        return self._binary("mul", other)
-
-    def __neg__(self):
-        if self.on_device:
-            return self._unary_device("neg")
-        return _host_map(self.__class__, lambda a: -a, self)
-
-    def __truediv__(self, number):
-        _check_divisor(number)
-        if self.on_device:
-            cplx = isinstance(number, (complex, np.complexfloating))
-            return self._unary_device("div", complex(number) if cplx else float(number), complex_out=cplx)
-        return _host_map(self.__class__, lambda a: a / number, self)
-
-    def __floordiv__(self, other):
-        if self.on_device:
-            _check_divisor(other)
-            if self._raw("signal").dtype.kind == "c" or isinstance(other, (complex, np.complexfloating)):
-                np.floor(np.zeros(1, np.complex128))            # NumPy's own TypeError: floor takes no complex values
-            return self._unary_device("floordiv", float(other))
-        return _host_map(self.__class__, np.floor, self / other)
-
-    def __pow__(self, other):
-        """``** 0``: ones; ``** 1``: the signal; ``** 2``: ``signal**2`` with the noise ``2 signal noise + noise**2`` (``2.0`` takes this
-        branch too: the reference compares with ``==``); any other real exponent: ``(signal + noise) ** other`` without noise."""
-        if not isinstance(other, numbers.Real):
-            raise TypeError(f"Can't exponentiate electrical_signal by type {type(other)}")
-        if self.on_device:
-            s, n = self._device_arrays()
-            if other == 0:
-                from . import _lib
-                ones = _lib.zeros_device(s.shape, s.dtype, s.device)
-                return self._wrap(_lib.shift_device(ones, 1.0))
-            if other == 1:
-                return self._wrap(s, n)
-            if other == 2:
-                return self._unary_device("pow2")
-            if s.dtype.kind == "c" and other != 0.5 and not (float(other).is_integer() and abs(other) < 100):
-                raise ValueError(f"electrical_signal ** {other}: a complex128 signal on the GPU takes integer exponents below 100 and 0.5; "
-                                 "there is no host fallback for a device-resident signal")
-            return self._unary_device("pow", float(other), single=True)
-        return _host_pow(self.__class__, self, other)
-
-    def __getitem__(self, key):
-        """A slice: a new signal (an empty one is the constructor's ``ValueError``); an ``int``: the value itself when there is no noise, a
-        signal of size 1 otherwise (reference ``typing.py:1366-1376``)."""
-        if not isinstance(key, (slice, int)):
-            raise TypeError(f"Invalid argument type. {key} of type {type(key)}")
-        if not self.on_device:
-            if isinstance(key, int) and self.noise is NULL:
-                return self.signal[key]
-            return self.__class__(self.signal[key], NULL if self.noise is NULL else self.noise[key])
-        from . import _lib
-        s, n = self._device_arrays()
-        if isinstance(key, slice):
-            start, stop, step = key.indices(s.size)
-            count = len(range(start, stop, step))
-            if count < 1:
-                raise ValueError(f"Signal must be scalar or 1D array for electrical_signal, invalid shape {(0,)}")
-        else:
-            if not -s.size <= key < s.size:
-                raise IndexError(f"index {key} is out of bounds for axis 0 with size {s.size}")
-            start, step, count = key % s.size, 1, 1
-        out = _lib.DeviceArray((count,), s.dtype, s.device)
-        out_n = None if n is None else _lib.DeviceArray((count,), s.dtype, s.device)
-        _lib.api.ssfm_signal_slice(1, s.size, s, n, int(s.dtype.kind == "c"), start, step, count, out, out_n)
-        if isinstance(key, int) and n is None:
-            return out.to_host()[0]
-        return self._wrap(out, out_n)
-
-    def __gt__(self, other):
-        return self._binary("gt", other)
-
-    def __lt__(self, other):
-        return other - self > 0                                 # (the reference's form: through `-`, not a comparison of its own)
-
-    def __eq__(self, other):
-        return self._binary("eq", other)
-
-    def __array_ufunc__(self, ufunc, method, *inputs, **kwargs):
-        """``ndarray + x``, ``ndarray - x`` and ``ndarray * x`` go to the signal's own operators (the noise rules hold and no object array
-        appears); ``np.abs`` of a device-resident signal stays there; any other ufunc sees the materialised ``signal + noise`` and a 1-D
-        result comes back wrapped (reference ``typing.py:1240-1275``)."""
-        if method == "__call__" and not kwargs.get("out"):
-            r = _reflected_ufunc(electrical_signal, ufunc, inputs)
-            if r is not NotImplemented:
-                return r
-            if ufunc is np.absolute and self.on_device and inputs[0] is self:
-                return self._unary_device("abs_all", real_out=True, single=True)
-        args = [a.__array__() if isinstance(a, self.__class__) else a for a in inputs]
-        result = getattr(ufunc, method)(*args, **kwargs)
-        if isinstance(result, np.ndarray) and result.ndim == 1:
-            return self.__class__(result)
-        return result
-
-    # -- methods (reference typing.py:1476-1486, :1599-1780)
-    @property
-    def real(self):
-        if self.on_device:
-            return self._unary_device("real", real_out=True)
-        return _host_map(self.__class__, lambda a: a.real, self)
-
-    @property
-    def imag(self):
-        if self.on_device:
-            return self._unary_device("imag", real_out=True)
-        return _host_map(self.__class__, lambda a: a.imag, self)
-
-    def conj(self):
-        if self.on_device:
-            return self._unary_device("conj")
-        return _host_map(self.__class__, lambda a: a.conj(), self)
-
-    def _reduce_device(self, kind, s, n=None):
-        from . import _lib
-        import ctypes
-        out = (ctypes.c_double * 2)()
-        _lib.api.ssfm_signal_reduce(kind, 1, s.size, s, n, int(s.dtype.kind == "c"), out)
-        return out
-
-    def sum(self, axis=None):
-        """Sums of signal and noise as a signal of size 1 (host values: one small read each on the device)."""
-        if self.on_device:
-            s, n = self._device_arrays()
-            def val(a):
-                o = self._reduce_device(2, a)
-                return np.complex128(complex(o[0], o[1])) if a.dtype.kind == "c" else np.float64(o[0])
-            return self.__class__(val(s), NULL if n is None else val(n))
-        return _host_map(self.__class__, lambda a: a.sum(axis=axis), self)
-
-    def abs(self, of="all"):
-        """``|signal|``, ``|noise|`` (zeros of the real type without noise) or ``|signal + noise|`` as a new signal."""
-        if not isinstance(of, str):
-            raise TypeError('`of` must be a string.')
-        of = of.lower()
-        if of not in ("signal", "noise", "all"):
-            raise ValueError('`of` must be one of the following values ("signal", "noise", "all")')
-        if self.on_device:
-            if of == "noise" and self._raw("noise") is NULL:
-                from . import _lib
-                s = self._raw("signal")
-                return self._wrap(_lib.zeros_device(s.shape, np.float64, s.device))
-            return self._unary_device("abs_" + of, real_out=True, single=True)
-        if of == "signal":
-            return self.__class__(np.abs(self.signal))
-        if of == "noise":
-            return self.__class__(np.zeros_like(self.signal.real) if self.noise is NULL else np.abs(self.noise))
-        return np.abs(self)                                     # through __array_ufunc__, as the reference
-
-    def power(self, unit="W", of="all"):
-        """Mean ``|.|**2`` of the signal, the noise or both, in W or dBm (a host scalar)."""
-        if of.lower() not in ("signal", "noise", "all"):
-            raise ValueError('`of` must be one of the following values ("signal", "noise", "all")')
-        if self.on_device:
-            s, n = self._device_arrays()
-            of = of.lower()
-            if of == "noise" and n is None:
-                p = np.float64(0.0)
-            else:
-                p = np.float64(self._reduce_device(0, n if of == "noise" else s, n if of == "all" else None)[0])
-        else:
-            p = np.mean(np.asarray(self.abs(of).signal) ** 2, axis=-1)
-        unit = unit.lower()
-        if unit == "w":
-            return p
-        if unit == "dbm":
-            with np.errstate(divide="ignore"):
-                return 10 * np.log10(p) + 30
-        raise ValueError('`unit` must be one of the following values ("W", "dBm")')
-
-    def normalize(self, by="power"):
-        """The signal divided by the square root of its signal power, or by its largest ``|signal|``."""
-        if by == "power":
-            return self / self.power("W", "signal") ** 0.5
-        if by == "amplitude":
-            if self.on_device:
-                return self / np.float64(self._reduce_device(1, self._device_arrays()[0])[0])
-            return self / np.abs(self.signal).max()
-        raise ValueError('`by` must be one of the following values ("power", "amplitude")')
-
-    def phase(self):
-        """``unwrap(angle(signal + noise))`` as a signal without noise."""
-        if self.on_device:
-            from . import _lib
-            s, n = self._device_arrays()
-            out = _lib.DeviceArray(s.shape, np.float64, s.device)
-            _lib.api.ssfm_signal_phase(1, s.size, s, n, int(s.dtype.kind == "c"), out)
-            return self._wrap(out)
-        return self.__class__(np.unwrap(np.angle(self.__array__())))
-
-    def filter(self, h):
-        """``scipy.signal.fftconvolve(., h, mode='same')`` of signal and noise (reference ``typing.py:1758-1780``)."""
-        if self.on_device:
-            from . import devices
-            s, n = self._device_arrays()
-            return self._wrap(*devices._filter_device(s, n, h))
-        import scipy.signal as sg
-        return _host_map(self.__class__, lambda a: sg.fftconvolve(a, h, mode="same"), self)
-
-
 _DEVICE_DTYPES = (np.dtype(np.float64), np.dtype(np.complex128))
 # enums of include/ssfm_amd.h (ssfm_signal_binary / ssfm_field_binary, ssfm_signal_unary / ssfm_field_unary)
 _BINARY = {"add": 0, "sub": 1, "rsub": 2, "mul": 3, "gt": 4, "eq": 5}
 _UNARY = {"neg": 0, "conj": 1, "div": 2, "floordiv": 3, "pow2": 4, "real": 5, "imag": 6, "abs_signal": 7, "abs_noise": 8, "abs_all": 9, "pow": 10}
-# ssfm_field_*: the code of a device field's type (enum ssfm_precision and SSFM_F64_REAL of include/ssfm_amd.h)
-_FIELD_CODES = {np.dtype(np.complex64): 0, np.dtype(np.complex128): 1, np.dtype(np.float64): 2}
+# ssfm_field_*: the code of a device field's type (enum ssfm_precision and SSFM_F64_REAL of include/ssfm_amd.h), in the order the messages name them
+_FIELD_CODES = {np.dtype(np.float64): 2, np.dtype(np.complex128): 1, np.dtype(np.complex64): 0}
+
+
+def _type_names(types) -> str:
+    """``'float64 and complex128'``, ``'float64, complex128 and complex64'``: the device types of a class, as its messages list them."""
+    names = [str(t) for t in types]
+    return ", ".join(names[:-1]) + " and " + names[-1]
 
 
 # -- the host algebra that electrical_signal and optical_signal share: NumPy on materialised arrays, NULL for an absent noise
@@ -941,6 +498,530 @@ def _reflected_ufunc(cls, ufunc, inputs):
     return NotImplemented
 
 
+def _signal_arrays(signal, noise, dtype):
+    """The constructors' shared middle: ``signal`` and ``noise`` (or NULL) as arrays of one type, ``dtype`` or their ``result_type``, and of
+    one shape; each class applies its own shape rules to them."""
+    sig = np.asarray(signal)
+    noi = noise
+    if noi is not NULL:
+        noi = np.asarray(noi)
+        common = np.result_type(sig, noi) if dtype is None else dtype
+        sig, noi = sig.astype(common, copy=False), noi.astype(common, copy=False)
+        if sig.shape != noi.shape:
+            raise ValueError(f"`signal` and `noise` must have the same shape, mismatch shapes {sig.shape} and {noi.shape}!")
+    elif dtype is not None:
+        sig = sig.astype(dtype, copy=False)
+    return sig, noi
+
+
+class _signal_base:
+    """What :class:`electrical_signal` and :class:`optical_signal` have in common (in the reference the second inherits the first; here neither
+    is the other's subclass): the lazy ``signal`` / ``noise`` storage, the metadata, the reads and NumPy protocols, and every operator and
+    method whose two versions differed only in how the result is built.  Each operation is NumPy on the host for host-only operands and one
+    launch on the GPU that holds a device-resident one.
+
+    A class supplies the rest through hooks.  Attributes: ``_NOUN`` ("signal" / "field", for the messages), ``_DEVICE_TYPES`` (the types its
+    device arrays take), ``_WRAPPED_NDIMS`` (the ufunc results that come back wrapped), ``_host_conj``; and, set once both classes exist,
+    ``_FAMILY`` (the class of the two that an object descends from: the name in its messages, the operand its reflected ufuncs take) and
+    ``_OPERANDS`` (the signal classes it takes as the other operand where they lie; anything else goes through the constructor).  Methods:
+    ``_make`` (the class of a host result), ``_wrap`` (a device result), ``_parse``, ``_binary_device``, ``_unary_device``,
+    ``_reduce_device`` (a ``(rows, 2)`` float64 array), ``_div_device``, ``_pow_device``, ``_filter_device`` and ``__getitem__``."""
+
+    signal = _LazyArray()
+    noise = _LazyArray()
+    __hash__ = None                  # (an `__eq__` that returns an array: unhashable, as the reference's class)
+
+    def _raw(self, name):
+        return self.__dict__.get("_" + name, NULL)
+
+    # -- metadata (reference typing.py:1216-1229, :1488-1522): no transfer
+    @property
+    def size(self) -> int:
+        """Samples per polarisation (reference ``typing.py:2313-2320``)."""
+        return int(self._raw("signal").shape[-1])
+
+    @property
+    def ndim(self) -> int:
+        return self._raw("signal").ndim
+
+    @property
+    def shape(self):
+        return tuple(self._raw("signal").shape)
+
+    @property
+    def on_device(self) -> bool:
+        """True while ``signal`` lives in GPU memory only (no host copy has been asked for)."""
+        return _is_device(self._raw("signal"))
+
+    @property
+    def type(self):
+        return type(self)
+
+    @property
+    def fs(self):
+        return gv.fs
+
+    @property
+    def sps(self):
+        return gv.sps
+
+    @property
+    def dt(self):
+        return gv.dt
+
+    @property
+    def t(self):
+        return gv.t[:self.size]
+
+    def __len__(self):
+        return self.size
+
+    # -- reads and protocols: __array__ / __iter__ / to_numpy materialise the signal on the host
+    def __iter__(self):
+        return iter(self.__array__())
+
+    def __array__(self, dtype=None, copy=None):
+        arr = self.signal + self.noise
+        return arr if dtype is None else arr.astype(dtype)
+
+    def to_numpy(self) -> np.ndarray:
+        """``signal + noise`` (reference ``typing.py:1593-1597``)."""
+        return np.asarray(self.signal + self.noise)
+
+    def w(self, shift: bool = False) -> np.ndarray:
+        """Angular frequency grid [rad/s], FFT order (reference ``typing.py:1628-1644``)."""
+        w = np.fft.fftfreq(self.size, gv.dt) * 2 * np.pi
+        return np.fft.fftshift(w, axes=-1) if shift else w
+
+    def f(self, shift: bool = False) -> np.ndarray:
+        """Frequency grid [Hz] (reference ``typing.py:1646-1660``)."""
+        return self.w(shift) / (2 * np.pi)
+
+    def __call__(self, domain, shift: bool = False):
+        """New object holding the FFT (``'w'`` / ``'f'``) or inverse FFT (``'t'``) of signal and noise along the last axis
+        (reference ``typing.py:1421-1462``); ``shift`` applies fftshift / ifftshift.  Computed on the GPU."""
+        from . import devices
+        return devices._fourier(self, domain, shift)
+
+    def psd(self, fmt='-', mode='x', n=None, xlabel=None, ylabel=None, yscale='dbm', grid=False, hold=True, show=False, **kwargs):
+        """Plot the power spectral density (reference ``typing.py:1850-1970``): Welch's estimate of the first ``n`` samples
+        (default ``min(size, gv.t.size)``) with ``nperseg = min(2048, n)`` at ``fs = gv.fs * 1e-9`` [GHz], computed on the GPU.
+        ``yscale``: ``'dbm'`` or ``'linear'`` (mW); ``mode``: ``'x'``, ``'y'`` or ``'both'`` polarisations.  Returns ``self``."""
+        from .utils import plot_psd
+        return plot_psd(self, fmt, mode, n, xlabel, ylabel, yscale, grid, hold, show, **kwargs)
+
+    # -- device plumbing: the arrays where they lie
+    def _device_arrays(self):
+        """``(signal, noise or None)`` as DeviceArrays of one type (one of the class's ``_DEVICE_TYPES``) on one GPU, for a device-resident
+        signal."""
+        from . import _lib
+        s, n = self._raw("signal"), self._raw("noise")
+        name, noun = self._FAMILY.__name__, self._NOUN
+        if s.dtype not in self._DEVICE_TYPES:
+            raise TypeError(f"{name}: the device algebra takes {_type_names(self._DEVICE_TYPES)}, this {noun} lies on the GPU as {s.dtype}; "
+                            f"there is no host fallback for a device-resident {noun} (convert it, or take .to_numpy())")
+        if n is NULL:
+            return s, None
+        if not _is_device(n):                                   # (a noise that was assigned on the host afterwards)
+            n = _lib.DeviceArray.from_host(np.ascontiguousarray(n, dtype=s.dtype), None, s.device)
+        elif n.dtype != s.dtype or n.device != s.device:
+            raise TypeError(f"{name}: signal ({s.dtype}, GPU {s.device}) and noise ({n.dtype}, GPU {n.device}) differ")
+        return s, n
+
+    def _shapes_error(self, shape):
+        return ValueError(f"Can't operate '{self._make.__name__}'s with shapes {self.shape} and {tuple(shape)}")
+
+    def _one_gpu(self, other):
+        """The GPU that holds this signal or ``other`` (a signal or None); operands on two GPUs are a ``ValueError``."""
+        return _one_gpu(f"'{self._make.__name__}'s", (x._raw("signal").device for x in (self, other) if x is not None and x.on_device))
+
+    def _binary(self, op, other):
+        """``op``: 'add', 'sub', 'rsub', 'mul', 'gt' or 'eq' between this signal and ``other``, where the operands lie."""
+        if self.on_device or (isinstance(other, self._OPERANDS) and other.on_device):
+            return self._binary_device(op, other)
+        o = self._parse(other)
+        s1, n1, s2, n2 = self.signal, self.noise, o.signal, o.noise
+        if op in ("gt", "eq"):
+            x, y = s1 + n1, s2 + n2
+            return binary_sequence(x > y) if op == "gt" else x == y
+        return _host_binary(self._make, op, s1, n1, s2, n2)
+
+    # -- operators (reference typing.py:1308-1419)
+    def __add__(self, other):
+        return self._binary("add", other)
+
+    def __radd__(self, other):
+        return self._binary("add", other)
+
+    def __sub__(self, other):
+        return self._binary("sub", other)
+
+    def __rsub__(self, other):
+        return self._binary("rsub", other)
+
+    def __mul__(self, other):
+        """``(s1 + n1)(s2 + n2)``: the signal is ``s1 s2``, everything that contains a noise factor is noise."""
+        return self._binary("mul", other)
+
+    def __rmul__(self, other):
+        return self.__mul__(other)
+
+    def __eq__(self, other):
+        """A host bool array (``(a == b).all()``); computed on the GPU for device operands, then read."""
+        return self._binary("eq", other)
+
+    def __neg__(self):
+        if self.on_device:
+            return self._unary_device("neg")
+        return _host_map(self._make, lambda a: -a, self)
+
+    def __truediv__(self, number):
+        _check_divisor(number)
+        if self.on_device:
+            return self._div_device(number)
+        return _host_map(self._make, lambda a: a / number, self)
+
+    def __floordiv__(self, other):
+        if self.on_device:
+            _check_divisor(other)
+            if self._raw("signal").dtype.kind == "c" or isinstance(other, (complex, np.complexfloating)):
+                np.floor(np.zeros(1, np.complex128))            # NumPy's own TypeError: floor takes no complex values
+            return self._unary_device("floordiv", float(other))
+        return _host_map(self._make, np.floor, self / other)
+
+    def __pow__(self, other):
+        """``** 0``: ones; ``** 1``: the signal; ``** 2``: ``signal**2`` with the noise ``2 signal noise + noise**2`` (``2.0`` takes this
+        branch too: the reference compares with ``==``); any other real exponent: ``(signal + noise) ** other`` without noise (on the GPU:
+        of a complex signal, the exponents NumPy computes by products and ``0.5``)."""
+        if not isinstance(other, numbers.Real):
+            raise TypeError(f"Can't exponentiate electrical_signal by type {type(other)}")
+        if self.on_device:
+            return self._pow_device(other)
+        return _host_pow(self._make, self, other)
+
+    def __array_ufunc__(self, ufunc, method, *inputs, **kwargs):
+        """``ndarray + x``, ``ndarray - x`` and ``ndarray * x`` go to the signal's own operators (the noise rules hold and no object array
+        appears); ``np.abs`` of a device-resident signal stays there, as a signal; any other ufunc sees the materialised ``signal + noise``
+        and a result of a dimension the class holds (1-D; for a field also 2-D) comes back wrapped (reference ``typing.py:1240-1275``)."""
+        if method == "__call__" and not kwargs.get("out"):
+            r = _reflected_ufunc(self._FAMILY, ufunc, inputs)
+            if r is not NotImplemented:
+                return r
+            if ufunc is np.absolute and self.on_device and inputs[0] is self:
+                return self._unary_device("abs_all", out_dtype=np.float64, single=True)
+        make = self._make
+        args = [a.__array__() if isinstance(a, make) else a for a in inputs]
+        result = getattr(ufunc, method)(*args, **kwargs)
+        if isinstance(result, np.ndarray) and result.ndim in self._WRAPPED_NDIMS:
+            return make(result)
+        return result
+
+    # -- methods (reference typing.py:1476-1486, :1599-1780)
+    @property
+    def real(self):
+        if self.on_device:
+            return self._unary_device("real", out_dtype=np.float64)
+        return _host_map(self._make, lambda a: a.real, self)
+
+    @property
+    def imag(self):
+        if self.on_device:
+            return self._unary_device("imag", out_dtype=np.float64)
+        return _host_map(self._make, lambda a: a.imag, self)
+
+    def conj(self):
+        if self.on_device:
+            return self._unary_device("conj")
+        return _host_map(self._make, self._host_conj, self)
+
+    def sum(self, axis=None):
+        """Sums of signal and noise over the whole signal as a signal of size 1 (host values; on the device every row is summed in one
+        launch, one small read each, and the rows are added on the host).  ``axis`` is the host path's, as NumPy's."""
+        if self.on_device:
+            s, n = self._device_arrays()
+
+            def val(a):
+                o = self._reduce_device(2, a).sum(axis=0)
+                return a.dtype.type(complex(o[0], o[1])) if a.dtype.kind == "c" else np.float64(o[0])
+            return self._make(val(s), NULL if n is None else val(n))
+        return _host_map(self._make, lambda a: a.sum(axis=axis), self)
+
+    def filter(self, h):
+        """``scipy.signal.fftconvolve(., h, mode='same')`` of signal and noise (reference ``typing.py:1758-1780``): one polarisation,
+        as SciPy's own ``ValueError`` says of a ``(2, N)`` field with 1-D taps.  On the GPU in double precision; a complex64 field is
+        widened and the result rounded once."""
+        if self.on_device:
+            return self._filter_device(h)
+        import scipy.signal as sg
+        return _host_map(self._make, lambda a: sg.fftconvolve(a, h, mode="same"), self)
+
+
+class electrical_signal(_signal_base):
+    """1-D electrical signal with optional noise and the algebra of the reference's class (``typing.py:1022-1780``).
+
+    ``+ - * / // **``, ``[]``, ``> < ==``, unary ``-``, ``abs``, ``power``, ``normalize``, ``phase``, ``conj``, ``sum``, ``filter``, ``w``,
+    ``f``, ``t``, ``fs``, ``sps``, ``dt``, ``real``, ``imag`` and the NumPy protocols ``__array__`` / ``__array_ufunc__`` carry the reference's
+    names, argument checks, error texts and signal / noise rules.
+
+    Residency: an operation on a signal that lies in GPU memory (``on_device``: what ``PD``, ``LPF``, ``ADC``, ``DAC`` and ``SAMPLER``
+    return) is computed there by the HIP kernels of ``csrc/signal_ops.hip`` and its result lies there too; a Python scalar is a kernel
+    argument, a host array or host signal as the other operand is uploaded once, two signals on different GPUs are a ``ValueError``.
+    Device arrays are float64 or complex128; any other device type raises ``TypeError``.  An operation on a host-only signal is NumPy on
+    the host, as in the reference, and loads no device.  ``power``, ``sum`` and an integer index of a noiseless signal return host scalars;
+    ``==`` returns a host bool array, ``>`` / ``<`` a ``binary_sequence`` (device-resident for device operands).  ``np.asarray(x)``,
+    iteration and a NumPy ufunc other than the three reflected operators and ``np.abs`` materialise the signal on the host.
+
+    On the device, ``filter`` with real signal, noise and taps carries the noise as the imaginary part of the signal's field through one
+    convolution: a noise below ``1e-12`` of the signal loses its digits on that path.  ``**`` of a complex128 device signal takes the
+    exponents NumPy computes by products (integers ``|p| < 100``) and ``0.5``; another exponent raises ``ValueError``.
+
+    Not provided: ``plot``, ``print``, ``grid``, ``legend``, ``show``, ``sizeof``, the reference's ``__getattr__`` delegation
+    to ``ndarray`` and ``__array_function__``."""
+
+    _NOUN = "signal"
+    _DEVICE_TYPES = _DEVICE_DTYPES
+    _WRAPPED_NDIMS = (1,)
+    _host_conj = staticmethod(lambda a: a.conj())               # (the reference's form: a real array is returned as it is, not copied)
+
+    @property
+    def _make(self):
+        """A result has the class of the signal, so a subclass keeps its class."""
+        return self.__class__
+
+    @classmethod
+    def from_device(cls, signal, noise=NULL):
+        """Wrap device-resident 1-D arrays without copying them to the host."""
+        self = cls.__new__(cls)
+        if signal.ndim != 1 or (noise is not NULL and noise.shape != signal.shape):
+            raise ValueError(f"Signal must be 1D array for electrical_signal, invalid shape {signal.shape}")
+        self.signal, self.noise = signal, noise
+        self.execution_time = 0.0
+        return self
+
+    def __init__(self, signal, noise=NULL, dtype=None):
+        if isinstance(signal, electrical_signal):
+            noise = signal.noise if noise is NULL else np.asarray(noise) + signal.noise
+            signal = signal.signal
+        sig, noi = _signal_arrays(signal, noise, dtype)
+        if sig.ndim > 1 or sig.size < 1:
+            raise ValueError(f"Signal must be scalar or 1D array for electrical_signal, invalid shape {sig.shape}")
+        if sig.ndim == 0:
+            sig = sig[np.newaxis]
+            if noi is not NULL:
+                noi = noi[np.newaxis]
+        self.signal = sig
+        self.noise = noi
+        self.execution_time = 0.0
+
+    MAX_EYE_TRACES = 4096
+
+    def plot_eye(self, n_traces=None, cmap='jet', N_grid_bins=200, grid_sigma=5, style='dot', ax=None, **plot_kw):
+        """Plot the eye diagram of signal + noise with ``gv.sps`` samples per symbol (reference ``typing.py:1971-2041``): at most
+        ``min(n_traces, 4096)`` traces, the density computed where the signal lies (``utils.eyediagram`` has the styles and ``plot_kw``).
+        Returns ``self``."""
+        from .utils import eyediagram
+        n_traces = self.MAX_EYE_TRACES if n_traces is None else min(n_traces, self.MAX_EYE_TRACES)
+        eyediagram(self, gv.sps, n_traces, cmap, N_grid_bins, grid_sigma, style, ax, **plot_kw)
+        return self
+
+    def __repr__(self):
+        where = " [device]" if self.on_device else ""
+        return f"electrical_signal(size={self.size}, dtype={self._raw('signal').dtype}, noise={'NULL' if self._raw('noise') is NULL else 'array'}){where}"
+
+    # -- device plumbing: uploads of the other operand, launches
+    def _upload(self, dev):
+        """This host signal's arrays on GPU ``dev`` as float64 / complex128 (the widening ``np.result_type`` would apply anyway)."""
+        from . import _lib
+        s = np.asarray(self.signal)
+        dt = np.complex128 if s.dtype.kind == "c" else np.float64
+        up = lambda a: _lib.DeviceArray.from_host(np.ascontiguousarray(a, dtype=dt), None, dev)       # noqa: E731
+        return up(s), (None if self.noise is NULL else up(self.noise))
+
+    def _wrap(self, s, n=None):
+        return self.__class__.from_device(s, NULL if n is None else n)
+
+    def _parse(self, other):
+        """The other operand as a signal of this class whose size is this one's or 1 (reference ``typing.py:1557-1573``)."""
+        if not isinstance(other, self.type):
+            other = self.__class__(other)
+        if self.size != other.size and min(self.size, other.size) != 1:
+            raise self._shapes_error(other.shape)
+        return other
+
+    def _binary_device(self, op, other):
+        from . import _lib
+        scalar = None
+        if isinstance(other, (numbers.Number, np.number, np.bool_)):
+            scalar = complex(other) if isinstance(other, (complex, np.complexfloating)) else float(other)
+            size2, o = 1, None
+        else:
+            # (any electrical_signal is used where it lies, whatever its class: the constructor would read it to the host; the result is self's class)
+            o = other if isinstance(other, self._OPERANDS) else self.__class__(other)
+            size2 = o.size
+        n = max(self.size, size2)
+        if self.size != size2 and min(self.size, size2) != 1:
+            raise self._shapes_error(o.shape)
+        dev = self._one_gpu(o)
+        s1, n1 = self._device_arrays() if self.on_device else self._upload(dev)
+        s2 = n2 = None
+        if o is not None:
+            s2, n2 = o._device_arrays() if o.on_device else o._upload(dev)
+        c1 = s1.dtype.kind == "c"
+        c2 = isinstance(scalar, complex) if o is None else s2.dtype.kind == "c"
+        if op in ("gt", "eq"):
+            out = _lib.DeviceArray((n,), np.uint8, dev)
+            out_n = None
+        else:
+            # the reference adds the noises with NULL as the identity, so a lone noise of size 1 meets a signal of size n in the constructor
+            if op != "mul" and (n1 is None) != (n2 is None) and (n1 if n2 is None else n2).size != n:
+                raise ValueError(f"`signal` and `noise` must have the same shape, mismatch shapes {(n,)} and {(1,)}!")
+            dt = np.complex128 if (c1 or c2) else np.float64
+            out = _lib.DeviceArray((n,), dt, dev)
+            out_n = _lib.DeviceArray((n,), dt, dev) if (n1 is not None or n2 is not None) else None
+        z = complex(scalar) if scalar is not None else 0j
+        _lib.api.ssfm_signal_binary(_BINARY[op], 1, n, s1, n1, s1.size, int(c1), s2, n2, size2, int(c2), z.real, z.imag, out, out_n)
+        if op == "gt":
+            return binary_sequence.from_device(out)
+        if op == "eq":
+            return out.to_host().astype(bool)
+        return self._wrap(out, out_n)
+
+    def _unary_device(self, op, p=0.0, *, out_dtype=None, single=False):
+        """One launch of ``ssfm_signal_unary``; ``out_dtype``: the result's type where it is not the signal's; ``single``: one result array
+        without noise."""
+        from . import _lib
+        s, n = self._device_arrays()
+        dt = s.dtype if out_dtype is None else out_dtype
+        out = _lib.DeviceArray(s.shape, dt, s.device)
+        out_n = None if (single or n is None) else _lib.DeviceArray(s.shape, dt, s.device)
+        z = complex(p)
+        _lib.api.ssfm_signal_unary(_UNARY[op], 1, s.size, s, n, int(s.dtype.kind == "c"), z.real, z.imag, int(isinstance(p, (complex, np.complexfloating))), out, out_n)
+        return self._wrap(out, out_n)
+
+    def _reduce_device(self, kind, s, n=None):
+        """``ssfm_signal_reduce``: a ``(1, 2)`` float64 array."""
+        from . import _lib
+        import ctypes
+        out = (ctypes.c_double * 2)()
+        _lib.api.ssfm_signal_reduce(kind, 1, s.size, s, n, int(s.dtype.kind == "c"), out)
+        return np.array(out[:], dtype=np.float64).reshape(1, 2)
+
+    def _div_device(self, number):
+        cplx = isinstance(number, (complex, np.complexfloating))
+        return self._unary_device("div", complex(number) if cplx else float(number), out_dtype=np.complex128 if cplx else None)
+
+    def _pow_device(self, other):
+        s, n = self._device_arrays()
+        if other == 0:
+            from . import _lib
+            ones = _lib.zeros_device(s.shape, s.dtype, s.device)
+            return self._wrap(_lib.shift_device(ones, 1.0))
+        if other == 1:
+            return self._wrap(s, n)
+        if other == 2:
+            return self._unary_device("pow2")
+        if s.dtype.kind == "c" and other != 0.5 and not (float(other).is_integer() and abs(other) < 100):
+            raise ValueError(f"electrical_signal ** {other}: a complex128 signal on the GPU takes integer exponents below 100 and 0.5; "
+                             "there is no host fallback for a device-resident signal")
+        return self._unary_device("pow", float(other), single=True)
+
+    def _filter_device(self, h):
+        from . import devices
+        s, n = self._device_arrays()
+        return self._wrap(*devices._filter_device(s, n, h))
+
+    def __getitem__(self, key):
+        """A slice: a new signal (an empty one is the constructor's ``ValueError``); an ``int``: the value itself when there is no noise, a
+        signal of size 1 otherwise (reference ``typing.py:1366-1376``)."""
+        if not isinstance(key, (slice, int)):
+            raise TypeError(f"Invalid argument type. {key} of type {type(key)}")
+        if not self.on_device:
+            if isinstance(key, int) and self.noise is NULL:
+                return self.signal[key]
+            return self.__class__(self.signal[key], NULL if self.noise is NULL else self.noise[key])
+        from . import _lib
+        s, n = self._device_arrays()
+        if isinstance(key, slice):
+            start, step, count = _slice_span(key, s.size)
+            if count < 1:
+                raise ValueError(f"Signal must be scalar or 1D array for electrical_signal, invalid shape {(0,)}")
+        else:
+            start, step, count = _checked_index(key, s.size), 1, 1
+        out = _lib.DeviceArray((count,), s.dtype, s.device)
+        out_n = None if n is None else _lib.DeviceArray((count,), s.dtype, s.device)
+        _lib.api.ssfm_signal_slice(1, s.size, s, n, int(s.dtype.kind == "c"), start, step, count, out, out_n)
+        if isinstance(key, int) and n is None:
+            return out.to_host()[0]
+        return self._wrap(out, out_n)
+
+    def __gt__(self, other):
+        return self._binary("gt", other)
+
+    def __lt__(self, other):
+        return other - self > 0                                 # (the reference's form: through `-`, not a comparison of its own)
+
+    # -- methods (reference typing.py:1599-1780)
+    def abs(self, of="all"):
+        """``|signal|``, ``|noise|`` (zeros of the real type without noise) or ``|signal + noise|`` as a new signal."""
+        if not isinstance(of, str):
+            raise TypeError('`of` must be a string.')
+        of = of.lower()
+        if of not in ("signal", "noise", "all"):
+            raise ValueError('`of` must be one of the following values ("signal", "noise", "all")')
+        if self.on_device:
+            if of == "noise" and self._raw("noise") is NULL:
+                from . import _lib
+                s = self._raw("signal")
+                return self._wrap(_lib.zeros_device(s.shape, np.float64, s.device))
+            return self._unary_device("abs_" + of, out_dtype=np.float64, single=True)
+        if of == "signal":
+            return self.__class__(np.abs(self.signal))
+        if of == "noise":
+            return self.__class__(np.zeros_like(self.signal.real) if self.noise is NULL else np.abs(self.noise))
+        return np.abs(self)                                     # through __array_ufunc__, as the reference
+
+    def power(self, unit="W", of="all"):
+        """Mean ``|.|**2`` of the signal, the noise or both, in W or dBm (a host scalar)."""
+        if of.lower() not in ("signal", "noise", "all"):
+            raise ValueError('`of` must be one of the following values ("signal", "noise", "all")')
+        if self.on_device:
+            s, n = self._device_arrays()
+            of = of.lower()
+            if of == "noise" and n is None:
+                p = np.float64(0.0)
+            else:
+                p = self._reduce_device(0, n if of == "noise" else s, n if of == "all" else None)[0, 0]
+        else:
+            p = np.mean(np.asarray(self.abs(of).signal) ** 2, axis=-1)
+        unit = unit.lower()
+        if unit == "w":
+            return p
+        if unit == "dbm":
+            with np.errstate(divide="ignore"):
+                return 10 * np.log10(p) + 30
+        raise ValueError('`unit` must be one of the following values ("W", "dBm")')
+
+    def normalize(self, by="power"):
+        """The signal divided by the square root of its signal power, or by its largest ``|signal|``."""
+        if by == "power":
+            return self / self.power("W", "signal") ** 0.5
+        if by == "amplitude":
+            if self.on_device:
+                return self / self._reduce_device(1, self._device_arrays()[0])[0, 0]
+            return self / np.abs(self.signal).max()
+        raise ValueError('`by` must be one of the following values ("power", "amplitude")')
+
+    def phase(self):
+        """``unwrap(angle(signal + noise))`` as a signal without noise."""
+        if self.on_device:
+            from . import _lib
+            s, n = self._device_arrays()
+            out = _lib.DeviceArray(s.shape, np.float64, s.device)
+            _lib.api.ssfm_signal_phase(1, s.size, s, n, int(s.dtype.kind == "c"), out)
+            return self._wrap(out)
+        return self.__class__(np.unwrap(np.angle(self.__array__())))
+
+
 def _field_total(x, dev):
     """``signal + noise`` of a field or an electrical signal, in its own type, as one array on GPU ``dev`` (the signal itself without noise)."""
     from . import _lib
@@ -955,9 +1036,7 @@ def _field_total(x, dev):
     return out
 
 
-
-
-class optical_signal:
+class optical_signal(_signal_base):
     """Optical field: ``signal`` (and optional ``noise``) of shape ``(N,)`` for one polarisation or ``(2, N)`` for two, with the algebra the
     reference's class inherits from ``electrical_signal`` (``typing.py:1308-1419``) and its own indexing (``typing.py:2261-2305``).
 
@@ -993,8 +1072,15 @@ class optical_signal:
 
     Not provided: ``plot``, ``print``, ``sizeof``, the reference's ``__getattr__`` delegation to ``ndarray`` and ``__array_function__``."""
 
-    signal = _LazyArray()
-    noise = _LazyArray()
+    _NOUN = "field"
+    _DEVICE_TYPES = _FIELD_CODES
+    _WRAPPED_NDIMS = (1, 2)
+    _host_conj = staticmethod(np.conj)                          # (a copy, of a real array too)
+
+    @property
+    def _make(self):
+        """A result is an ``optical_signal`` whose ``n_pol`` follows its shape, as in ``self.__class__(sig, noi)`` of the reference."""
+        return optical_signal
 
     @classmethod
     def from_device(cls, signal, noise=NULL, n_pol=None):
@@ -1008,14 +1094,6 @@ class optical_signal:
         self.n_pol = signal.ndim if n_pol is None else n_pol
         self.execution_time = 0.0
         return self
-
-    def _raw(self, name):
-        return self.__dict__.get("_" + name, NULL)
-
-    @property
-    def on_device(self) -> bool:
-        """True while ``signal`` still lives in GPU memory only (no host copy has been asked for)."""
-        return _is_device(self._raw("signal"))
 
     def __init__(self, signal, noise=NULL, n_pol=None, dtype=None):
         if _is_device(signal) and (noise is NULL or _is_device(noise)) and dtype is None:      # device arrays: no copy to the host
@@ -1035,16 +1113,7 @@ class optical_signal:
             else:
                 noise = signal.noise
             signal = signal.signal
-        sig = np.asarray(signal)
-        noi = noise
-        if noi is not NULL:
-            noi = np.asarray(noi)
-            common = np.result_type(sig, noi) if dtype is None else dtype
-            sig, noi = sig.astype(common, copy=False), noi.astype(common, copy=False)
-            if sig.shape != noi.shape:
-                raise ValueError(f"`signal` and `noise` must have the same shape, mismatch shapes {sig.shape} and {noi.shape}!")
-        elif dtype is not None:
-            sig = sig.astype(dtype, copy=False)
+        sig, noi = _signal_arrays(signal, noise, dtype)
 
         if sig.ndim > 2 or (sig.ndim > 1 and sig.shape[0] > 2) or sig.size < 1:
             raise ValueError(f"Signal must be a scalar, 1D or 2D array for optical_signal, invalid shape {sig.shape}")
@@ -1082,78 +1151,6 @@ class optical_signal:
         self.noise = noi
         self.n_pol = n_pol
         self.execution_time = 0.0
-
-    @property
-    def size(self) -> int:
-        """Samples per polarisation (reference ``typing.py:2313-2320``)."""
-        return int(self._raw("signal").shape[-1])
-
-    def __len__(self):
-        return self.size
-
-    @property
-    def shape(self):
-        return tuple(self._raw("signal").shape)
-
-    @property
-    def dt(self):
-        return gv.dt
-
-    def __call__(self, domain, shift: bool = False):
-        """New object holding the FFT (``'w'`` / ``'f'``) or inverse FFT (``'t'``) of signal and noise along the last axis
-        (reference ``typing.py:1421-1462``); ``shift`` applies fftshift / ifftshift.  Computed on the GPU."""
-        from . import devices
-        return devices._fourier(self, domain, shift)
-
-    def to_numpy(self) -> np.ndarray:
-        """``signal + noise`` (reference ``typing.py:1593-1597``)."""
-        return np.asarray(self.signal + self.noise)
-
-    def psd(self, fmt='-', mode='x', n=None, xlabel=None, ylabel=None, yscale='dbm', grid=False, hold=True, show=False, **kwargs):
-        """Plot the power spectral density (reference ``typing.py:1850-1970``): Welch's estimate of the first ``n`` samples
-        (default ``min(size, gv.t.size)``) with ``nperseg = min(2048, n)`` at ``fs = gv.fs * 1e-9`` [GHz], computed on the GPU.
-        ``yscale``: ``'dbm'`` or ``'linear'`` (mW); ``mode``: ``'x'``, ``'y'`` or ``'both'`` polarisations.  Returns ``self``."""
-        from .utils import plot_psd
-        return plot_psd(self, fmt, mode, n, xlabel, ylabel, yscale, grid, hold, show, **kwargs)
-
-    def w(self, shift: bool = False) -> np.ndarray:
-        """Angular frequency grid [rad/s], FFT order (reference ``typing.py:1628-1644``)."""
-        w = np.fft.fftfreq(self.size, gv.dt) * 2 * np.pi
-        return np.fft.fftshift(w, axes=-1) if shift else w
-
-    # -- metadata and protocols (reference typing.py:1216-1229, :1488-1522): no transfer but for __array__ / __iter__
-    __hash__ = None                  # (an `__eq__` that returns an array: unhashable, as the reference's class)
-
-    @property
-    def ndim(self) -> int:
-        return self._raw("signal").ndim
-
-    @property
-    def type(self):
-        return type(self)
-
-    @property
-    def fs(self):
-        return gv.fs
-
-    @property
-    def sps(self):
-        return gv.sps
-
-    @property
-    def t(self):
-        return gv.t[:self.size]
-
-    def f(self, shift: bool = False) -> np.ndarray:
-        """Frequency grid [Hz] (reference ``typing.py:1646-1660``)."""
-        return self.w(shift) / (2 * np.pi)
-
-    def __iter__(self):
-        return iter(self.__array__())
-
-    def __array__(self, dtype=None, copy=None):
-        arr = self.signal + self.noise
-        return arr if dtype is None else arr.astype(dtype)
 
     # -- reads: NumPy arrays on the host, like `.signal` (the reference returns signal objects here; the device-resident |x| is np.abs(x))
     def abs(self, of: str = "all") -> np.ndarray:
@@ -1196,22 +1193,7 @@ class optical_signal:
             return p.astype(np.float32) if single else p
         raise ValueError('`unit` must be one of the following values ("W", "dBm")')
 
-    # -- device plumbing: the arrays where they lie, the one upload of a host operand, launches
-    def _device_arrays(self):
-        """``(signal, noise or None)`` as DeviceArrays of one type (float64, complex128 or complex64) on one GPU, for a device-resident field."""
-        from . import _lib
-        s, n = self._raw("signal"), self._raw("noise")
-        if s.dtype not in _FIELD_CODES:
-            raise TypeError(f"optical_signal: the device algebra takes float64, complex128 and complex64, this field lies on the GPU as {s.dtype}; "
-                            "there is no host fallback for a device-resident field (convert it, or take .to_numpy())")
-        if n is NULL:
-            return s, None
-        if not _is_device(n):                                   # (a noise that was assigned on the host afterwards)
-            n = _lib.DeviceArray.from_host(np.ascontiguousarray(n, dtype=s.dtype), None, s.device)
-        elif n.dtype != s.dtype or n.device != s.device:
-            raise TypeError(f"optical_signal: signal ({s.dtype}, GPU {s.device}) and noise ({n.dtype}, GPU {n.device}) differ")
-        return s, n
-
+    # -- device plumbing: the one upload of a host operand, launches
     @staticmethod
     def _wrap(s, n=None):
         """A device result as a field; ``n_pol`` follows the shape, as in ``self.__class__(sig, noi)`` of the reference."""
@@ -1227,9 +1209,6 @@ class optical_signal:
             return a if a.dtype == dt else a.astype(dt)
         return _lib.DeviceArray.from_host(np.ascontiguousarray(a, dtype=dt), None, dev)
 
-    def _shapes_error(self, shape):
-        return ValueError(f"Can't operate 'optical_signal's with shapes {self.shape} and {tuple(shape)}")
-
     def _parse(self, other):
         """The other operand as a field whose size is this one's or 1 (reference ``typing.py:1557-1573``); an ``electrical_signal`` keeps its
         signal and noise apart and broadcasts over the polarisations."""
@@ -1241,16 +1220,6 @@ class optical_signal:
             raise self._shapes_error(other.shape)
         return other
 
-    def _binary(self, op, other):
-        """``op``: 'add', 'sub', 'rsub', 'mul' or 'eq' between this field and ``other``, where the operands lie."""
-        if self.on_device or (isinstance(other, (optical_signal, electrical_signal)) and other.on_device):
-            return self._binary_device(op, other)
-        o = self._parse(other)
-        s1, n1, s2, n2 = self.signal, self.noise, o.signal, o.noise
-        if op == "eq":
-            return (s1 + n1) == (s2 + n2)
-        return _host_binary(optical_signal, op, s1, n1, s2, n2)
-
     def _binary_device(self, op, other):
         """One launch of ``ssfm_field_binary`` on the GPU that holds a device-resident operand.  The result's type is NumPy's
         ``result_type`` of the arrays the reference would form (a scalar is ``np.array(scalar)``: a Python float is float64 there);
@@ -1261,24 +1230,21 @@ class optical_signal:
             scalar, o = complex(other), None
             shape2, dt2 = (1,), np.asarray(other).dtype
         else:
-            if isinstance(other, (optical_signal, electrical_signal)):
+            if isinstance(other, self._OPERANDS):
                 o = other
             else:
                 o = optical_signal(other)                       # a host array: the constructor's shape rules and errors
             shape2, dt2 = tuple(o._raw("signal").shape), o._raw("signal").dtype
         if self.size != shape2[-1] and min(self.size, shape2[-1]) != 1:
             raise self._shapes_error(shape2)
-        devs = {x._raw("signal").device for x in (self, o) if x is not None and x.on_device}
-        if len(devs) > 1:
-            raise ValueError(f"Can't operate 'optical_signal's that lie on different GPUs {sorted(devs)}: move one of them first")
-        dev = devs.pop()
+        dev = self._one_gpu(o)
         for x in (self, o):
             if x is not None and x.on_device:
                 x._device_arrays()                              # (the TypeError of a device type the kernels do not take)
         shape = np.broadcast_shapes(self.shape, shape2)
         dt = np.result_type(self._raw("signal").dtype, dt2)
         if dt not in _FIELD_CODES:
-            raise TypeError(f"optical_signal: the device algebra takes float64, complex128 and complex64, not the {dt} this operation gives")
+            raise TypeError(f"optical_signal: the device algebra takes {_type_names(_FIELD_CODES)}, not the {dt} this operation gives")
         part = lambda x: [None if a is NULL else a for a in (x._raw("signal"), x._raw("noise"))]     # noqa: E731
         (s1, n1), (s2, n2) = part(self), ((None, None) if o is None else part(o))
         if op == "eq":                                          # signal + noise of each operand in its own type first, as NumPy forms it
@@ -1305,10 +1271,16 @@ class optical_signal:
         return self._wrap(out, out_n)
 
     def _unary_device(self, op, p=0.0, *, out_dtype=None, single=False, wide=False, back=False):
-        """One launch of ``ssfm_field_unary``.  ``single``: one result array without noise; ``wide``: a complex64 field is widened
-        (exact) and computed in double precision; ``back``: the result of that is rounded once to complex64."""
+        """One launch of ``ssfm_field_unary``.  ``out_dtype``: the result's type where it is not the field's; ``single``: one result array
+        without noise; ``wide``: a complex64 field is widened (exact) and computed in double precision; ``back``: the result of that is
+        rounded once to complex64.  ``real``, ``imag`` and ``np.abs`` of a complex64 field are float32 arrays in NumPy, a type the device
+        arrays do not have: ``TypeError``."""
         from . import _lib
         s, n = self._device_arrays()
+        what = {"real": "real", "imag": "imag", "abs_all": "np.abs"}.get(op)
+        if what and s.dtype == np.complex64:
+            raise TypeError(f"optical_signal: {what} of a complex64 field on the GPU would be float32, which the device arrays do not hold; "
+                            "widen the field first (x * np.complex128(1)) or take .to_numpy()")
         narrow = back and wide and s.dtype == np.complex64
         if wide and s.dtype == np.complex64:
             s, n = s.astype(np.complex128), (None if n is None else n.astype(np.complex128))
@@ -1322,12 +1294,6 @@ class optical_signal:
             out, out_n = out.astype(np.complex64), (None if out_n is None else out_n.astype(np.complex64))
         return self._wrap(out, out_n)
 
-    def _no_float32(self, what):
-        """``real``, ``imag`` and ``np.abs`` of a complex64 field are float32 arrays in NumPy, a type the device arrays do not have."""
-        if self._raw("signal").dtype == np.complex64:
-            raise TypeError(f"optical_signal: {what} of a complex64 field on the GPU would be float32, which the device arrays do not hold; "
-                            "widen the field first (x * np.complex128(1)) or take .to_numpy()")
-
     def _reduce_device(self, kind, s, n=None):
         """``ssfm_field_reduce`` of every row in one launch: a ``(rows, 2)`` float64 array (a complex64 field is widened first)."""
         from . import _lib
@@ -1339,19 +1305,42 @@ class optical_signal:
         _lib.api.ssfm_field_reduce(kind, rows, s.shape[-1], s, n, int(s.dtype.kind == "c"), out)
         return np.array(out[:], dtype=np.float64).reshape(rows, 2)
 
-    # -- operators (reference typing.py:1308-1419)
-    def __add__(self, other):
-        return self._binary("add", other)
+    def _div_device(self, number):
+        s, _ = self._device_arrays()
+        dt = np.result_type(s.dtype, number)                    # NumPy >= 2: a Python scalar does not widen a complex64 field, a float64 scalar does
+        cplx = isinstance(number, (complex, np.complexfloating))
+        return self._unary_device("div", complex(number) if cplx else float(number), out_dtype=dt, wide=dt != np.complex64)
 
-    def __radd__(self, other):
-        return self._binary("add", other)
+    def _pow_device(self, other):
+        s, n = self._device_arrays()
+        if other == 0:
+            from . import _lib
+            ones = _lib.shift_device(_lib.zeros_device(s.shape, np.complex128 if s.dtype.kind == "c" else np.float64, s.device), 1.0)
+            return self._wrap(ones if ones.dtype == s.dtype or s.dtype.kind != "c" else ones.astype(s.dtype))
+        if other == 1:
+            return self._wrap(s, n)
+        if other == 2:
+            return self._unary_device("pow2", wide=True, back=True)
+        if s.dtype.kind == "c" and other != 0.5 and not (float(other).is_integer() and abs(other) < 100):
+            raise ValueError(f"optical_signal ** {other}: a complex field on the GPU takes integer exponents below 100 and 0.5; "
+                             "there is no host fallback for a device-resident field")
+        return self._unary_device("pow", float(other), single=True, wide=True, back=True)
 
-    def __sub__(self, other):
-        return self._binary("sub", other)
+    def _filter_device(self, h):
+        from . import devices
+        s, n = self._device_arrays()
+        h = np.asarray(h)
+        if s.ndim != h.ndim:
+            raise ValueError("in1 and in2 should have the same dimensionality")
+        single = s.dtype == np.complex64
+        if single:
+            s, n = s.astype(np.complex128), (None if n is None else n.astype(np.complex128))
+        out, out_n = devices._filter_device(s, n, h)
+        if single and np.result_type(np.complex64, h.dtype) == np.complex64:
+            out, out_n = out.astype(np.complex64), (None if out_n is None else out_n.astype(np.complex64))
+        return self._wrap(out, out_n)
 
-    def __rsub__(self, other):
-        return self._binary("rsub", other)
-
+    # -- operators of its own (reference typing.py:1308-1419, :2261-2305)
     def __mul__(self, other):
         """``(s1 + n1)(s2 + n2)``: the signal is ``s1 s2``, everything that contains a noise factor is noise."""
         raw_s, raw_n = self._raw("signal"), self._raw("noise")
@@ -1361,56 +1350,6 @@ class optical_signal:
             return optical_signal.from_device(_lib.scale_add_device(raw_s, float(other)),
                                               NULL if raw_n is NULL else _lib.scale_add_device(raw_n, float(other)), n_pol=self.n_pol)
         return self._binary("mul", other)
-
-    def __rmul__(self, other):
-        return self.__mul__(other)
-
-    def __neg__(self):
-        if self.on_device:
-            return self._unary_device("neg")
-        return _host_map(optical_signal, lambda a: -a, self)
-
-    def __truediv__(self, number):
-        _check_divisor(number)
-        if self.on_device:
-            s, _ = self._device_arrays()
-            dt = np.result_type(s.dtype, number)                # NumPy >= 2: a Python scalar does not widen a complex64 field, a float64 scalar does
-            cplx = isinstance(number, (complex, np.complexfloating))
-            return self._unary_device("div", complex(number) if cplx else float(number), out_dtype=dt, wide=dt != np.complex64)
-        return _host_map(optical_signal, lambda a: a / number, self)
-
-    def __floordiv__(self, other):
-        if self.on_device:
-            _check_divisor(other)
-            if self._device_arrays()[0].dtype.kind == "c" or isinstance(other, (complex, np.complexfloating)):
-                np.floor(np.zeros(1, np.complex128))            # NumPy's own TypeError: floor takes no complex values
-            return self._unary_device("floordiv", float(other))
-        return _host_map(optical_signal, np.floor, self / other)
-
-    def __pow__(self, other):
-        """``** 0``: ones; ``** 1``: the field; ``** 2``: ``signal**2`` with the noise ``2 signal noise + noise**2``; any other real exponent:
-        ``(signal + noise) ** other`` without noise (on the GPU: the exponents ``electrical_signal`` takes there)."""
-        if not isinstance(other, numbers.Real):
-            raise TypeError(f"Can't exponentiate electrical_signal by type {type(other)}")
-        if self.on_device:
-            s, n = self._device_arrays()
-            if other == 0:
-                from . import _lib
-                ones = _lib.shift_device(_lib.zeros_device(s.shape, np.complex128 if s.dtype.kind == "c" else np.float64, s.device), 1.0)
-                return self._wrap(ones if ones.dtype == s.dtype or s.dtype.kind != "c" else ones.astype(s.dtype))
-            if other == 1:
-                return self._wrap(s, n)
-            if other == 2:
-                return self._unary_device("pow2", wide=True, back=True)
-            if s.dtype.kind == "c" and other != 0.5 and not (float(other).is_integer() and abs(other) < 100):
-                raise ValueError(f"optical_signal ** {other}: a complex field on the GPU takes integer exponents below 100 and 0.5; "
-                                 "there is no host fallback for a device-resident field")
-            return self._unary_device("pow", float(other), single=True, wide=True, back=True)
-        return _host_pow(optical_signal, self, other)
-
-    def __eq__(self, other):
-        """A host bool array (``(a == b).all()``); computed on the GPU for device operands, then read."""
-        return self._binary("eq", other)
 
     def __gt__(self, other):
         raise NotImplementedError('The > operator is not implemented for optical_signal objects.')
@@ -1466,24 +1405,19 @@ class optical_signal:
         def column(k):
             """(start, step, count, is a single sample) of the samples' key."""
             if isinstance(k, slice):
-                start, stop, step = k.indices(size)
-                return start, step, len(range(start, stop, step)), False
+                return *_slice_span(k, size), False
             if not is_int(k):
                 probe((slice(None), k) if two else k)
                 raise TypeError(f"optical_signal on the GPU takes an integer or a slice for the samples, not {k!r} of type {type(k)}; "
                                 "there is no host fallback for a device-resident field")
-            if not -size <= k < size:
-                raise IndexError(f"index {k} is out of bounds for axis {1 if two else 0} with size {size}")
-            return int(k) % size, 1, 1, True
+            return _checked_index(k, size, 1 if two else 0), 1, 1, True
 
         def row(k):
             if not is_int(k):
                 probe(k)
                 raise TypeError(f"optical_signal on the GPU takes an integer or ':' for the polarisation, not {k!r} of type {type(k)}; "
                                 "there is no host fallback for a device-resident field")
-            if not -2 <= k < 2:
-                raise IndexError(f"index {k} is out of bounds for axis 0 with size 2")
-            return int(k) % 2
+            return _checked_index(k, 2)
 
         def cut(row0, nrows, start, step, count, shape):
             out = _lib.DeviceArray(shape, s.dtype, s.device)
@@ -1504,9 +1438,7 @@ class optical_signal:
             if n is None and isinstance(time_idx, int):         # the reference indexes its result once more by the sample's key
                 if nrows == 1:
                     raise IndexError("invalid index to scalar variable.")
-                if not -2 <= time_idx < 2:
-                    raise IndexError(f"index {time_idx} is out of bounds for axis 0 with size 2")
-                return cut(time_idx % 2, 1, start, 1, 1, (1,))[0].to_host()[0]
+                return cut(_checked_index(time_idx, 2), 1, start, 1, 1, (1,))[0].to_host()[0]
             if count < 1:
                 raise bad_shape((2, 0) if nrows == 2 else (0,))
             shape = ((2,) if nrows == 2 else (1,)) if one else ((2, count) if nrows == 2 else (count,))
@@ -1521,58 +1453,6 @@ class optical_signal:
             out, out_n = cut(0, 1, start, 1, 1, (1,))
             return out.to_host()[0] if n is None else self._wrap(out, out_n)
         return self._wrap(*cut(row(key), 1, 0, 1, size, (size,)))
-
-    def __array_ufunc__(self, ufunc, method, *inputs, **kwargs):
-        """``ndarray + x``, ``ndarray - x`` and ``ndarray * x`` go to the field's own operators; ``np.abs`` of a device-resident field stays
-        there as a field; any other ufunc sees the materialised ``signal + noise`` and a 1-D or 2-D result comes back wrapped (reference
-        ``typing.py:1240-1275``)."""
-        if method == "__call__" and not kwargs.get("out"):
-            r = _reflected_ufunc(optical_signal, ufunc, inputs)
-            if r is not NotImplemented:
-                return r
-            if ufunc is np.absolute and self.on_device and inputs[0] is self:
-                self._device_arrays()
-                self._no_float32("np.abs")
-                return self._unary_device("abs_all", out_dtype=np.float64, single=True)
-        args = [a.__array__() if isinstance(a, optical_signal) else a for a in inputs]
-        result = getattr(ufunc, method)(*args, **kwargs)
-        if isinstance(result, np.ndarray) and result.ndim in (1, 2):
-            return optical_signal(result)
-        return result
-
-    # -- methods (reference typing.py:1476-1486, :1599-1780)
-    @property
-    def real(self):
-        if self.on_device:
-            self._device_arrays()
-            self._no_float32("real")
-            return self._unary_device("real", out_dtype=np.float64)
-        return _host_map(optical_signal, lambda a: a.real, self)
-
-    @property
-    def imag(self):
-        if self.on_device:
-            self._device_arrays()
-            self._no_float32("imag")
-            return self._unary_device("imag", out_dtype=np.float64)
-        return _host_map(optical_signal, lambda a: a.imag, self)
-
-    def conj(self):
-        if self.on_device:
-            return self._unary_device("conj")
-        return _host_map(optical_signal, np.conj, self)
-
-    def sum(self, axis=None):
-        """Sums of signal and noise over the whole field as a field of size 1 (host values; on the device every row is summed in one
-        launch and the rows are added on the host).  ``axis`` is the host path's, as NumPy's."""
-        if self.on_device:
-            s, n = self._device_arrays()
-
-            def val(a):
-                o = self._reduce_device(2, a).sum(axis=0)
-                return a.dtype.type(complex(o[0], o[1])) if a.dtype.kind == "c" else np.float64(o[0])
-            return optical_signal(val(s), NULL if n is None else val(n))
-        return _host_map(optical_signal, lambda a: a.sum(axis=axis), self)
 
     def normalize(self, by="power"):
         """The field divided by the square root of its signal power (one polarisation: the quotient is by a scalar), or by its largest
@@ -1592,29 +1472,15 @@ class optical_signal:
             return self / (d.astype(np.float32) if s.dtype == np.complex64 else d)
         return self._unary_device("div", float(d), wide=True, back=True)      # float64 up to the end, then rounded once to complex64
 
-    def filter(self, h):
-        """``scipy.signal.fftconvolve(., h, mode='same')`` of signal and noise (reference ``typing.py:1758-1780``): one polarisation,
-        as SciPy's own ``ValueError`` says of a ``(2, N)`` field with 1-D taps.  On the GPU in complex128; a complex64 field is widened
-        and the result rounded once."""
-        if self.on_device:
-            from . import devices
-            s, n = self._device_arrays()
-            h = np.asarray(h)
-            if s.ndim != h.ndim:
-                raise ValueError("in1 and in2 should have the same dimensionality")
-            single = s.dtype == np.complex64
-            if single:
-                s, n = s.astype(np.complex128), (None if n is None else n.astype(np.complex128))
-            out, out_n = devices._filter_device(s, n, h)
-            if single and np.result_type(np.complex64, h.dtype) == np.complex64:
-                out, out_n = out.astype(np.complex64), (None if out_n is None else out_n.astype(np.complex64))
-            return self._wrap(out, out_n)
-        import scipy.signal as sg
-        return _host_map(optical_signal, lambda a: sg.fftconvolve(a, h, mode="same"), self)
-
     def __repr__(self):
         where = " [device]" if self.on_device else ""
         return f"optical_signal(n_pol={self.n_pol}, size={self.size}, dtype={self._raw('signal').dtype}, noise={'NULL' if self._raw('noise') is NULL else 'array'}){where}"
+
+
+# set once both classes exist: the class of the two that an object descends from, and the signal classes it takes as the other operand where
+# they lie (a host electrical_signal reads a device-resident optical_signal through its constructor, as it reads an array)
+electrical_signal._FAMILY, electrical_signal._OPERANDS = electrical_signal, (electrical_signal,)
+optical_signal._FAMILY, optical_signal._OPERANDS = optical_signal, (optical_signal, electrical_signal)
 
 
 class _KnownSlots(_LazyArray):

@@ -107,3 +107,33 @@ def test_lt_is_the_references_subtraction():
     """`a < b` is `b - a > 0` (typing.py:1387-1389): with a NaN on either side both orders are False."""
     a, b = electrical_signal([1.0, np.nan, 3.0]), electrical_signal([2.0, 2.0, np.nan])
     assert list((a < b).data) == [1, 0, 0] and list((a > b).data) == [0, 0, 0]
+
+
+PUBLIC = ["abs", "conj", "dt", "f", "filter", "from_device", "fs", "imag", "ndim", "noise", "normalize", "on_device", "phase", "power", "psd", "real",
+          "shape", "signal", "size", "sps", "sum", "t", "to_numpy", "type", "w"]
+DUNDERS = {"__add__", "__array__", "__array_ufunc__", "__call__", "__eq__", "__floordiv__", "__getitem__", "__gt__", "__hash__", "__init__", "__iter__",
+           "__len__", "__lt__", "__mul__", "__neg__", "__pow__", "__radd__", "__repr__", "__rmul__", "__rsub__", "__sub__", "__truediv__"}
+SHARED = ("signal", "noise", "_raw", "on_device", "shape", "ndim", "size", "type", "fs", "sps", "dt", "t", "__len__", "__hash__", "__iter__", "__array__",
+          "to_numpy", "w", "f", "__call__", "psd", "_device_arrays", "__add__", "__radd__", "__sub__", "__rsub__", "__rmul__", "__eq__", "__neg__", "conj",
+          "real", "imag", "sum", "filter", "__truediv__", "__floordiv__", "__pow__", "__array_ufunc__")
+
+
+def test_the_two_signal_classes_share_one_base_and_keep_their_surface():
+    """electrical_signal and optical_signal are siblings under one private base: neither is the other's subclass, the public names and the
+    protocols of each are the lists below (written down from the classes as they were while they were unrelated), and every member the base
+    holds is one object for both, so that an edit cannot fork them again."""
+    from opticomlib_amd import optical_signal
+    assert not issubclass(optical_signal, electrical_signal) and not issubclass(electrical_signal, optical_signal)
+    public = lambda cls: sorted(n for n in dir(cls) if not n.startswith("_"))                            # noqa: E731
+    assert public(optical_signal) == PUBLIC                                              # (`n_pol` and `execution_time` are instance attributes)
+    assert public(electrical_signal) == sorted(PUBLIC + ["MAX_EYE_TRACES", "plot_eye"])
+    x = optical_signal(np.arange(4.0))
+    assert sorted(vars(x)) == ["_noise", "_signal", "execution_time", "n_pol"] and not hasattr(electrical_signal(np.arange(4.0)), "n_pol")
+    housekeeping = {"__dict__", "__doc__", "__module__", "__weakref__", "__firstlineno__", "__static_attributes__"}
+    for cls in (electrical_signal, optical_signal):
+        own = {n for n in dir(cls) if n.startswith("__") and n.endswith("__") and any(n in k.__dict__ for k in cls.__mro__[:-1])}
+        assert own - housekeeping == DUNDERS, cls
+        assert cls.__hash__ is None
+    for m in SHARED:
+        assert getattr(electrical_signal, m) is getattr(optical_signal, m), m
+    assert "_signal_base" not in dir(__import__("opticomlib_amd"))

@@ -508,3 +508,48 @@ def test_the_example_prints_zero_device_to_host_copies():
     out = subprocess.run([sys.executable, os.path.join(root, "examples", "signal_algebra.py")], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0, out.stderr[-2000:]
     assert "device-to-host copies between PD and the bits: 0; result on the GPU: True" in out.stdout
+
+
+@pytest.mark.parametrize("cplx", (False, True), ids=("float64", "complex128"))
+@pytest.mark.parametrize("n", (1, 2, 513, 524291))
+def test_the_signal_and_field_entry_points_share_their_kernels(n, cplx):
+    """ssfm_signal_reduce / ssfm_signal_slice are ssfm_field_reduce / ssfm_field_slice of one row: the same kernels on the same grid, so the
+    same bits.  524291 is odd and just past 1024 workgroups x 256 lanes x 2 values, where the reduction's grid stops growing.  The values
+    against NumPy on the host copy: slices exactly, sum and power within 1e-12 of the peak, max |.| exactly for float64 and within the
+    hypot bound for complex128 (module docstring)."""
+    import ctypes
+    rng = np.random.default_rng(n)
+    dtype, code = (np.complex128, 1) if cplx else (np.float64, 2)            # the field entry points' code of the type (ssfm_amd.h)
+    ok = True
+    for noise in (False, True):
+        s, z = operands(n, rng, cplx, noise)
+        total = s if z is None else s + z
+        ds, dz = _lib.DeviceArray.from_host(s), (None if z is None else _lib.DeviceArray.from_host(z))
+        tag = f"shared n={n} {'c' if cplx else 'r'}{' noise' if noise else ''}"
+        for kind, name in ((2, "sum"), (1, "maxabs")) + (((0, "power"),) if noise else ()):      # (a lone array's power goes another way)
+            a, b = (ctypes.c_double * 2)(), (ctypes.c_double * 2)()
+            _lib.api.ssfm_signal_reduce(kind, 1, n, ds, dz, int(cplx), a)
+            _lib.api.ssfm_field_reduce(kind, 1, n, ds, dz, int(cplx), b)
+            k = 2 if name == "sum" else 1
+            assert same(np.array(a[:k]), np.array(b[:k])), (tag, name)
+            if name == "sum":
+                got = np.complex128(complex(a[0], a[1])) if cplx else np.float64(a[0])
+                ok &= peak(got, np.sum(total), f"{tag} sum", pk=float(np.sum(np.abs(total))))
+            elif name == "power":
+                ok &= peak(np.float64(a[0]), np.mean(np.abs(total) ** 2), f"{tag} power")
+            elif cplx:
+                ok &= ulps(np.float64(a[0]), np.max(np.abs(total)), f"{tag} max", ULP["hypot"])
+            else:
+                assert a[0] == np.max(np.abs(total)), (tag, name)
+        for key in (slice(n // 3, None, 1), slice(None, None, 3), slice(None, None, -2), slice(n - 1, n), slice(None)):
+            start, stop, step = key.indices(n)
+            count = len(range(start, stop, step))
+            room = lambda: (_lib.zeros_device((count,), dtype), _lib.zeros_device((count,), dtype) if noise else None)     # noqa: E731
+            by_signal, by_field = room(), room()
+            _lib.api.ssfm_signal_slice(1, n, ds, dz, int(cplx), start, step, count, *by_signal)
+            _lib.api.ssfm_field_slice(code, 1, n, ds, dz, 0, 1, start, step, count, *by_field)
+            for src, o_sig, o_fld in zip((s, z), by_signal, by_field):
+                if src is not None:
+                    g_sig, g_fld = o_sig.to_host(), o_fld.to_host()
+                    assert np.array_equal(g_sig, g_fld) and same(g_sig, src[key]), (tag, key)
+    assert ok
