@@ -24,6 +24,8 @@
 #include "ssfm_common.hpp"
 #include "ssfm_kernels.hpp"
 #include "ssfm_medium.hpp"
+#include "ssfm_owned.hpp"
+#include "ssfm_schedule.hpp"
 #include "ssfm_split.hpp"
 
 using namespace ssfm;
@@ -519,26 +521,30 @@ template <typename T> struct PlanT : PlanBase {
     int64_t n = 0;
     int batch = 0;
     int N1 = 0, N2 = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    // Everything the plan holds is a member that frees itself (ssfm_owned.hpp); free_all() below is only what must happen in a certain ORDER before that.
+    hipStream_t stream = nullptr;       // == lane_stream[0], which owns it
+    Event ev0, ev1;
+    // F / Y / P are what the launches read (targs / fargs): the plan's own buffers F_own / Y_own / P_own, except while measure_lanes points them at scratch fields
     cx<T>* F = nullptr;        // batch * n
-    cx<T>* Y = nullptr;        // the field between the kernels: == F (plain layout, in place) or a buffer of its own (U16 layout)
+    cx<T>* Y = nullptr;        // the field between the kernels: == F (plain layout, in place) or a buffer of its own (U16 layout: Y_own)
     T* P = nullptr;            // batch * n
-    cx<T>* twN = nullptr;      // n
-    cx<T>* twA = nullptr;      // (N1/16)*N2: W_N^m
-    cx<T>* twB = nullptr;      // 16*N2: W_N^(m*N1/16)
-    cx<T>* tw1 = nullptr;      // N1
-    cx<T>* tw2 = nullptr;      // N2
-    cx<T>* dnat = nullptr;     // n  (D~ or H, natural order, staging)
-    cx<T>* dperm = nullptr;    // n  (D~ transposed order)
-    cx<T>* dperm_fly = nullptr;  // the same for the rows of k_freq<FM_FLY> where they use another number of points per thread (Ef_fly)
-    T* dimag_fly = nullptr;      // a fibre's operator (flat real part) for k_freq<FM_FLY_IM>: the imaginary parts alone (complex64 plans in the unit layout, lazily)
+    DeviceBuffer<cx<T>> F_own, Y_own;
+    DeviceBuffer<T> P_own;
+    DeviceBuffer<cx<T>> twN;      // n
+    DeviceBuffer<cx<T>> twA;      // (N1/16)*N2: W_N^m
+    DeviceBuffer<cx<T>> twB;      // 16*N2: W_N^(m*N1/16)
+    DeviceBuffer<cx<T>> tw1;      // N1
+    DeviceBuffer<cx<T>> tw2;      // N2
+    DeviceBuffer<cx<T>> dnat;     // n  (D~ or H, natural order, staging)
+    DeviceBuffer<cx<T>> dperm;    // n  (D~ transposed order)
+    DeviceBuffer<cx<T>> dperm_fly;  // the same for the rows of k_freq<FM_FLY> where they use another number of points per thread (Ef_fly)
+    DeviceBuffer<T> dimag_fly;      // a fibre's operator (flat real part) for k_freq<FM_FLY_IM>: the imaginary parts alone (complex64 plans in the unit layout, lazily)
     bool dimag_valid = false;
-    cx<T>* tw2_fly = nullptr;
-    cx<T>* scratch = nullptr;  // batch * n, lazily
-    cx<T>* xfer_tab[2] = {nullptr, nullptr};   // resident transfer functions of ssfm_transfer_table (n each, lazily)
-    struct Tab { T h; cx<T>* ptr; bool valid; int kind; };      // kind 0: exp(D~ h)/N as complex numbers; 1: its phases (FM_PHASE)
-    Tab tabs[kMaxTables] = {};
+    DeviceBuffer<cx<T>> tw2_fly;
+    DeviceBuffer<cx<T>> scratch;  // batch * n, lazily (ensure_scratch)
+    DeviceBuffer<cx<T>> xfer_tab[2];   // resident transfer functions of ssfm_transfer_table (n each, lazily: ensure_xfer)
+    struct Tab { T h = 0; DeviceBuffer<cx<T>> ptr; bool valid = false; int kind = 0; };      // kind 0: exp(D~ h)/N as complex numbers; 1: its phases (FM_PHASE)
+    Tab tabs[kMaxTables];
     // Re D~ is the same number at every frequency (a fibre: -alpha/2, reference devices.py:1145): |exp(D~ h)| is a scalar and the
     // table may hold phases only.  Decided when the operator is set; env SSFM_PHASE_TABLE=0 keeps the complex tables.
     bool op_flat_re = false;
@@ -548,16 +554,17 @@ template <typename T> struct PlanT : PlanBase {
     int tab_rr = 0;
     // single-launch engine of small plans (ssfm_kernels.hpp k_small): its own row twiddles and operator tables (another order)
     bool small = false;        // env SSFM_SMALL=0 turns it off
-    cx<T>* tw_small = nullptr;
-    cx<T>* tw_chirp = nullptr; // stage twiddles of the line for the chirp-z kernels where they take other points per thread than k_small (made on first use)
-    cx<T>* dsmall = nullptr;   // D~ in the one-line order (k_small_adapt)
+    DeviceBuffer<cx<T>> tw_small;
+    DeviceBuffer<cx<T>> tw_chirp; // stage twiddles of the line for the chirp-z kernels where they take other points per thread than k_small (made on first use)
+    DeviceBuffer<cx<T>> dsmall;   // D~ in the one-line order (k_small_adapt)
     // single-launch engine of medium plans (ssfm_kernels.hpp k_medium): its barrier counters and error word in device memory, a pinned
     // host copy of the error word, and what a repeat of the run on the two-kernel engine needs
     bool medium_ok = true;     // env SSFM_MEDIUM=0, or a run whose barrier once ran out of patience, clears it
-    unsigned long long* medium_st = nullptr;       // kBarShards counters, kBarWords flag words, the error word, the ticket counter
-    unsigned* medium_err_host = nullptr;        // two words: a dual-polarisation plan of long rows runs its rows as two launches (run_medium)
-    hipStream_t medium_stream2 = nullptr;       // ... the second one here, on another XCD
-    hipEvent_t medium_ev2 = nullptr;
+    static constexpr size_t kSet = kBarShards + kBarWords + 2;      // one launch's words in medium_st
+    DeviceBuffer<unsigned long long> medium_st;    // two sets of: kBarShards counters, kBarWords flag words, the error word, the ticket counter (ensure_medium_state)
+    PinnedBuffer<unsigned> medium_err_host;     // two words: a dual-polarisation plan of long rows runs its rows as two launches (run_medium)
+    Stream medium_stream2;                      // ... the second one here, on another XCD
+    Event medium_ev2;
     bool medium_pending = false;
     bool medium_split_ok = true;   // env SSFM_MEDIUM_SPLIT=0: a dual-polarisation plan's rows stay in one launch
     bool medium_adapt_ok = true;   // env SSFM_MEDIUM_ADAPT=0, or a run whose workgroups once did not all get to run, clears it
@@ -567,15 +574,13 @@ template <typename T> struct PlanT : PlanBase {
     double medium_gamma = 0;
     long long medium_patience = 2000000ll;
     bool fused_ok = true;      // TM_MID_A may be used (env SSFM_ADAPT_FUSED=0, or a grid that once did not run as a whole, clears it)
-    cx<T>* fused_backup = nullptr;   // the input of a fused adaptive run, for the fall-back
-    Tab stabs[kMaxTables] = {};
+    DeviceBuffer<cx<T>> fused_backup;   // the input of a fused adaptive run, for the fall-back (backup_field)
+    Tab stabs[kMaxTables];
     int stab_rr = 0;
-    T* d_hs = nullptr;         // the schedule on the device: step sizes, then one table index per step
-    size_t d_hs_cap = 0;
+    DeviceBuffer<T> d_hs;      // the schedule on the device: step sizes, then one table index per step (upload_schedule)
     std::vector<unsigned char> h_sched;
-    AdaptState<T>* st = nullptr;
-    T* zlog = nullptr;
-    int64_t zlog_cap = 0;
+    DeviceBuffer<AdaptState<T>> st;
+    DeviceBuffer<T> zlog;      // (ensure_zlog)
     bool have_op = false;
     // ---- split plans (ssfm_split.hpp; round 6): rows of more than 2^22 samples.  `n` / `batch` / N1 / N2 below describe the SUB-SEQUENCES (n = M samples,
     // batch = rows x R of them) that every kernel of this file works on; `n_full` / `batch_full` are what the caller sees.  The caller's field lives in
@@ -584,10 +589,10 @@ template <typename T> struct PlanT : PlanBase {
     int split_R = 1;
     int64_t n_full = 0;
     int batch_full = 0;
-    cx<T>* Fnat = nullptr;
-    double2* split_twA = nullptr;      // W_N^(a k1), W_N^(a N1 k2) in double (one rounding of their product in k_split_mid)
-    double2* split_twB = nullptr;
-    cx<T>* dsplit = nullptr;           // D~ in the split order [p][k1][k2] (SM_FLY: adaptive runs, more step sizes than tables), lazily
+    DeviceBuffer<cx<T>> Fnat;
+    DeviceBuffer<double2> split_twA;   // W_N^(a k1), W_N^(a N1 k2) in double (one rounding of their product in k_split_mid)
+    DeviceBuffer<double2> split_twB;
+    DeviceBuffer<cx<T>> dsplit;        // D~ in the split order [p][k1][k2] (SM_FLY: adaptive runs, more step sizes than tables), lazily
     bool dsplit_valid = false;
     bool sub_valid = true, nat_valid = false;
     bool is_split() const { return split_R > 1; }
@@ -643,7 +648,7 @@ template <typename T> struct PlanT : PlanBase {
     // D~ in the split order, for SM_FLY
     int split_fly_ready() {
         if (dsplit_valid) return SSFM_OK;
-        if (!dsplit) HIP_TRY(hipMalloc(&dsplit, sizeof(cx<T>) * (size_t)n_full));
+        HIP_TRY(dsplit.reserve(sizeof(cx<T>) * (size_t)n_full));
         hipLaunchKernelGGL((k_make_split_table<T, 0>), dim3((unsigned)((n_full + 255) / 256)), dim3(256), 0, stream, (const cx<T>*)dnat, dsplit, N1, N2, split_R, (T)0, inv_n_full(), split_qf());
         HIP_TRY(hipGetLastError());
         dsplit_valid = true;
@@ -676,22 +681,20 @@ template <typename T> struct PlanT : PlanBase {
     float lane_score = 0.f;            // last rating: period with the other lane / period alone
     bool lane_check_pending = false;   // the last run was a two-lane run of >= 64 steps whose period has not been looked at yet
     int64_t lane_check_launches = 0;
-    hipEvent_t lane_e0 = nullptr, lane_e1 = nullptr;      // brackets of a rating measurement
-    hipEvent_t run_e0 = nullptr, run_e1 = nullptr;        // brackets of the last run that lane_health looks at (its own pair: ev0 / ev1 are re-recorded by every entry point)
+    Event lane_e0, lane_e1;      // brackets of a rating measurement
+    Event run_e0, run_e1;        // brackets of the last run that lane_health looks at (its own pair: ev0 / ev1 are re-recorded by every entry point)
     // ---- z-resolved capture that does not stall the loop (propagate_fixed_capture, round 5): a stream of its own for the transfers, a ring of plan-owned
     // device blocks of snapshots (filled by the capture steps' END launches, sent to the host by a helper thread -- cap_worker -- as they fill), the scalar log.
     // Nothing on the device waits across streams: a stream blocked on another stream's event slows every other queue's launches (see propagate_fixed_capture).
     static constexpr int kCapBlocksMax = 8;
-    hipStream_t cap_stream = nullptr;
-    std::vector<hipEvent_t> cap_ev_ends[kMaxLanesConst];  // per lane and flush: the lane's END that filled the block
-    hipEvent_t cap_ev_in = nullptr;                       // on the plan's stream, ahead of the run: the input is in F
-    char* cap_blocks = nullptr;                           // kCapBlocksMax blocks at most, cap_block_bytes each
-    char* cap_in = nullptr;                               // plans whose engine works in place (Y == F): a copy of the input, taken ahead of the run
-    size_t cap_in_bytes = 0;
+    Stream cap_stream;                                    // (ensure_cap_stream)
+    std::vector<Event> cap_ev_ends[kMaxLanesConst];       // per lane and flush: the lane's END that filled the block
+    Event cap_ev_in;                                      // on the plan's stream, ahead of the run: the input is in F
+    DeviceBuffer<char> cap_blocks;                        // kCapBlocksMax blocks at most, cap_block_bytes each
+    DeviceBuffer<char> cap_in;                            // plans whose engine works in place (Y == F): a copy of the input, taken ahead of the run
     size_t cap_block_bytes = 0;
     int cap_nblocks = 0;
-    double* cap_scal = nullptr;                           // the wavefronts' pairs, then the reduced log
-    size_t cap_scal_bytes = 0;
+    DeviceBuffer<double> cap_scal;                        // the wavefronts' pairs, then the reduced log
     LaneWorker cap_worker;                                // the helper thread of a capture run
     bool cap_pending = false;                             // a capture run's helper may still be at work: the next entry point (use_device) joins it
     // A caller that has asked for ssfm_stream() or ssfm_field_device_ptr() may order its own work behind a run without ssfm_synchronize(): for it a
@@ -700,21 +703,59 @@ template <typename T> struct PlanT : PlanBase {
     bool external_order = false;
     // plan-owned device workspaces that grow on demand (ssfm_plan_workspace): what a driver loop outside this file (chirpz.hip) needs per call
     // without a hipMalloc / hipFree pair per call -- hipFree waits for the whole device and stalls the streams of every other plan
-    void* work[4] = {nullptr, nullptr, nullptr, nullptr};
-    size_t work_cap[4] = {0, 0, 0, 0};
+    DeviceBuffer<char> work[4];
+    // A buffer that work queued on the plan's stream may still read grows like this everywhere: the stream is drained, then the old block is freed
+    template <typename B> int grow(B& b, size_t bytes, size_t slack = 0) {
+        if (b.capacity() >= bytes) return SSFM_OK;
+        if (b.get()) HIP_TRY(hipStreamSynchronize(stream));
+        HIP_TRY(b.reserve(bytes, slack));
+        return SSFM_OK;
+    }
     int workspace(int slot, size_t bytes, void** out) {
         if (slot < 0 || slot > 3 || !out) return fail(SSFM_ERR_INVALID, "ssfm_plan_workspace: slot %d", slot);
         if (int rc = use_device()) return rc;
-        if (work_cap[slot] < bytes) {
-            HIP_TRY(hipStreamSynchronize(stream));
-            (void)hipFree(work[slot]); work[slot] = nullptr; work_cap[slot] = 0;
-            const size_t want = bytes + bytes / 2 + 256;
-            HIP_TRY(hipMalloc(&work[slot], want));
-            work_cap[slot] = want;
-        }
-        *out = work[slot];
+        if (int rc = grow(work[slot], bytes, bytes / 2 + 256)) return rc;
+        *out = work[slot].get();
         return SSFM_OK;
     }
+    // ---- what is made on first use, each in one place
+    int ensure_scratch() { HIP_TRY(scratch.reserve(sizeof(cx<T>) * n * batch)); return SSFM_OK; }
+    int ensure_xfer(int slot) { HIP_TRY(xfer_tab[slot].reserve(sizeof(cx<T>) * n)); return SSFM_OK; }
+    int ensure_zlog(int64_t max_steps) { return grow(zlog, sizeof(T) * (size_t)(max_steps + 1)); }
+    // the one-launch engines' barrier words (two sets: run_medium's second launch has its own) and the pinned copy of their error words
+    int ensure_medium_state() {
+        if (medium_st) return SSFM_OK;
+        HIP_TRY(medium_st.reserve(sizeof(unsigned long long) * 2 * kSet));
+        HIP_TRY(medium_err_host.reserve(2 * sizeof(unsigned)));
+        medium_err_host[0] = medium_err_host[1] = 0u;
+        return SSFM_OK;
+    }
+    // the field as it is now, kept for a run that may have to be repeated on another engine
+    int backup_field() {
+        const size_t fb = sizeof(cx<T>) * n * batch;
+        HIP_TRY(fused_backup.reserve(fb));
+        HIP_TRY(hipMemcpyAsync(fused_backup, F, fb, hipMemcpyDeviceToDevice, stream));
+        return SSFM_OK;
+    }
+    // a capture's copy stream: normal priority -- the plan's high-priority class keeps its queues for the lanes
+    int ensure_cap_stream() {
+        if (cap_stream) return SSFM_OK;
+        HIP_TRY(hipStreamCreateWithFlags(cap_stream.out(), hipStreamNonBlocking));
+        HIP_TRY(hipEventCreateWithFlags(cap_ev_in.out(), hipEventDisableTiming));
+        return SSFM_OK;
+    }
+    // `hs | which` of a schedule -> d_hs, behind everything queued on the plan's stream; the table indices start `sizeof(T) * size()` bytes in (d_which)
+    int upload_schedule(const Schedule<T>& sch) {
+        const size_t hb = sizeof(T) * (size_t)sch.size(), need = hb + (size_t)sch.size();
+        if (int rc = grow(d_hs, need, need / 2)) return rc;
+        HIP_TRY(hipStreamSynchronize(stream));             // the staging vector may still feed the previous run's copy
+        h_sched.resize(need);
+        std::memcpy(h_sched.data(), sch.steps.data(), hb);
+        std::memcpy(h_sched.data() + hb, sch.which.data(), (size_t)sch.size());
+        HIP_TRY(hipMemcpyAsync(d_hs, h_sched.data(), need, hipMemcpyHostToDevice, stream));
+        return SSFM_OK;
+    }
+    const unsigned char* d_which(const Schedule<T>& sch) const { return reinterpret_cast<const unsigned char*>(d_hs.get()) + sizeof(T) * (size_t)sch.size(); }
     LaneWorker lane_worker[8];        // (lane g > 0: a host thread of its own for its launches; env SSFM_LANE_THREADS=0: all from the caller's thread)
     bool lane_threads = true;
     bool profiling = false;
@@ -727,16 +768,16 @@ template <typename T> struct PlanT : PlanBase {
     int E = 16;                // points per thread of k_time (env SSFM_E = 8 | 16)
     int Ef = 16;               // ... and of k_freq (env SSFM_EF); the two kernels only share the field layout
     int Ef_fly = 16;           // ... and of k_freq when it forms exp(D~ h) itself (adaptive runs, more step sizes than tables)
-    hipStream_t lane_stream[kMaxLanes] = {};
-    hipEvent_t lane_ev[kMaxLanes] = {};
-    hipEvent_t fork_ev = nullptr;
+    Stream lane_stream[kMaxLanes];         // (lane 0's is the plan's `stream`)
+    Event lane_ev[kMaxLanes];
+    Event fork_ev;
     // per-lane pools of events (profiling).  mode 1: an event after every launch (per-class times, but
     // the marker packets slow a launch-dense run by ~30 %); mode 2: an event after every 64th launch
     // (negligible overhead; the interval is split between the classes by launch count); mode 3: after every
     // kSampleStride launches ONE launch of each class is bracketed by two events (3 extra markers per 16 launches: the
     // host keeps ahead of the GPU) -- kernel_times() then reports those single-launch intervals only.
     struct LaneProf {
-        std::vector<hipEvent_t> ev;
+        std::vector<Event> ev;
         std::vector<int> c0, c1;          // launches of class 0 / 1 between event i-1 and event i
         size_t n = 0;
         int pend0 = 0, pend1 = 0;
@@ -750,9 +791,9 @@ template <typename T> struct PlanT : PlanBase {
 
     int prof_record(LaneProf& p, int lane) {
         if (p.n == p.ev.size()) {
-            hipEvent_t e;
-            HIP_TRY(hipEventCreate(&e));
-            p.ev.push_back(e);
+            Event e;
+            HIP_TRY(hipEventCreate(e.out()));
+            p.ev.push_back(std::move(e));
             p.c0.push_back(0);
             p.c1.push_back(0);
         }
@@ -801,56 +842,21 @@ template <typename T> struct PlanT : PlanBase {
 
     T inv_n() const { return (T)1 / (T)n; }
 
+    // What has to happen in order before the members free themselves: the helper threads end, the streams drain, and a good pair of lane streams goes
+    // to the pool with its rating (lane_pool above) instead of being destroyed.
     int free_all() {
         cap_worker.stop();                                  // (finishes a capture run's transfers first)
         for (auto& w : lane_worker) w.stop();
         if (stream) (void)hipStreamSynchronize(stream);
-        void* bufs[] = {F, Y != F ? Y : nullptr, P, twN, twA, twB, tw1, tw2, tw2_fly, dnat, dperm, dperm_fly, dimag_fly, scratch, st, zlog, xfer_tab[0], xfer_tab[1]};
-        for (void* b : bufs) (void)hipFree(b);
-        for (auto& t : tabs) (void)hipFree(t.ptr);
-        for (auto& t : stabs) (void)hipFree(t.ptr);
-        (void)hipFree(Fnat); (void)hipFree(split_twA); (void)hipFree(split_twB); (void)hipFree(dsplit);
-        (void)hipFree(tw_small);
-        (void)hipFree(tw_chirp);
-        (void)hipFree(dsmall);
-        (void)hipFree(fused_backup);
-        (void)hipFree(medium_st);
-        if (medium_err_host) (void)hipHostFree(medium_err_host);
-        if (adapt_look) (void)hipHostFree(adapt_look);
-        if (medium_ev2) (void)hipEventDestroy(medium_ev2);
-        if (medium_stream2) (void)hipStreamDestroy(medium_stream2);
-        (void)hipFree(d_hs);
-        for (void* w : work) (void)hipFree(w);
-        // a good pair of lane streams goes to the pool with its rating (lane_pool above) instead of being destroyed
-        bool pooled = false;
+        if (cap_stream) (void)hipStreamSynchronize(cap_stream);
         if (nlanes == 2 && lanes_ok && !lanes_dropped && !lanes_share_queue && lane_fault == 0 && stream && lane_stream[1] && lane_stream[1] != stream
             && !std::getenv("SSFM_LANE_POOL_OFF")) {
             (void)hipStreamSynchronize(lane_stream[1]);
-            pooled = lane_pool().give(LanePair{device, stream, lane_stream[1], lane_score, lane_alone_us, lane_pair_us});
-            if (pooled) lane_stream[1] = nullptr;
+            if (lane_pool().give(LanePair{device, stream, lane_stream[1], lane_score, lane_alone_us, lane_pair_us})) {
+                (void)lane_stream[0].release(); (void)lane_stream[1].release();
+            }
         }
-        for (int g = 1; g < kMaxLanes; ++g) {
-            if (lane_ev[g]) (void)hipEventDestroy(lane_ev[g]);
-            if (lane_stream[g]) (void)hipStreamDestroy(lane_stream[g]);
-        }
-        if (fork_ev) (void)hipEventDestroy(fork_ev);
-        if (lane_e0) (void)hipEventDestroy(lane_e0);
-        if (lane_e1) (void)hipEventDestroy(lane_e1);
-        if (run_e0) (void)hipEventDestroy(run_e0);
-        if (run_e1) (void)hipEventDestroy(run_e1);
-        if (cap_stream) (void)hipStreamSynchronize(cap_stream);
-        for (auto& v : cap_ev_ends) for (hipEvent_t e : v) (void)hipEventDestroy(e);
-        if (cap_ev_in) (void)hipEventDestroy(cap_ev_in);
-        for (auto& e : acap_ev) if (e) (void)hipEventDestroy(e);
-        (void)hipFree(cap_blocks); (void)hipFree(cap_in); (void)hipFree(cap_scal);
-        if (cap_stream) (void)hipStreamDestroy(cap_stream);
-        for (auto& p : prof) {
-            for (hipEvent_t e : p.ev) (void)hipEventDestroy(e);
-            p.ev.clear();
-        }
-        if (ev0) (void)hipEventDestroy(ev0);
-        if (ev1) (void)hipEventDestroy(ev1);
-        if (stream && !pooled) (void)hipStreamDestroy(stream);
+        stream = nullptr;
         return SSFM_OK;
     }
     ~PlanT() override { free_all(); }
@@ -898,15 +904,16 @@ template <typename T> struct PlanT : PlanBase {
             if (const char* e = std::getenv("SSFM_LANES")) want2 = std::atoi(e);
             LanePair lp;
             if (want2 == 2 && batch_full >= 2 && batch_full % 2 == 0 && !std::getenv("SSFM_LANE_POOL_OFF") && lane_pool().take(device, &lp)) {
-                stream = lp.main; lane_stream[1] = lp.lane;
+                lane_stream[0].reset(lp.main); lane_stream[1].reset(lp.lane);
                 lane_score = lp.score; lane_alone_us = 0.f; lane_pair_us = 0.f;           // (the periods are this plan's own kernels': the first long run sets them)
                 lanes_from_pool = true;
                 ++g_lane_pairs_reused;
             }
         }
-        if (!stream) HIP_TRY(hipStreamCreateWithPriority(&stream, hipStreamNonBlocking, prio_hi));
-        HIP_TRY(hipEventCreate(&ev0));
-        HIP_TRY(hipEventCreate(&ev1));
+        if (!lane_stream[0]) HIP_TRY(hipStreamCreateWithPriority(lane_stream[0].out(), hipStreamNonBlocking, prio_hi));
+        stream = lane_stream[0];
+        HIP_TRY(hipEventCreate(ev0.out()));
+        HIP_TRY(hipEventCreate(ev1.out()));
         // measured: complex64 with 8 points per thread (twice the waves, one more exchange) is 10 % slower;
         // complex128 is 5 % FASTER with 8 (16 need the whole register file: 1 wave per SIMD, AGPR spills)
         E = sizeof(T) == 8 ? 8 : 16;
@@ -937,54 +944,54 @@ template <typename T> struct PlanT : PlanBase {
         nlanes = want < 1 ? 1 : (want > kMaxLanes ? kMaxLanes : want);
         if (nlanes > batch_full) nlanes = batch_full;
         while (batch_full % nlanes) --nlanes;            // (a lane holds whole rows: all sub-sequences of a row of a split plan)
-        lane_stream[0] = stream;
-        HIP_TRY(hipEventCreateWithFlags(&fork_ev, hipEventDisableTiming));
+        HIP_TRY(hipEventCreateWithFlags(fork_ev.out(), hipEventDisableTiming));
         if (lanes_from_pool && nlanes != 2) {           // (cannot happen with the rule above; a pooled lane stream must not leak)
-            (void)hipStreamDestroy(lane_stream[1]); lane_stream[1] = nullptr; lanes_from_pool = false;
+            lane_stream[1].reset(); lanes_from_pool = false;
         }
         for (int g = 1; g < nlanes; ++g) {
-            if (!(lanes_from_pool && g == 1)) HIP_TRY(hipStreamCreateWithPriority(&lane_stream[g], hipStreamNonBlocking, prio_hi));
-            HIP_TRY(hipEventCreateWithFlags(&lane_ev[g], hipEventDisableTiming));
+            if (!(lanes_from_pool && g == 1)) HIP_TRY(hipStreamCreateWithPriority(lane_stream[g].out(), hipStreamNonBlocking, prio_hi));
+            HIP_TRY(hipEventCreateWithFlags(lane_ev[g].out(), hipEventDisableTiming));
         }
         lanes_active = nlanes;
         const size_t cb = sizeof(cx<T>);
-        HIP_TRY(hipMalloc(&F, cb * n * batch));
-        HIP_TRY(hipMalloc(&P, sizeof(T) * n * batch));
+        HIP_TRY(F_own.reserve(cb * n * batch));
+        HIP_TRY(P_own.reserve(sizeof(T) * n * batch));
+        F = F_own; P = P_own;
         u16 = u16_layout<T>(N1, cols_per_tile<T>(), E);
         // the unit layout orders the field between the two kernels by N2 / Ef (k_time's Qf): rows of k_freq<FM_FLY> with another number of points per
         // thread would pair every spectrum bin with another bin's operator (SSFM_EF_FLY != Ef: tests/test_fft_edges_gpu.py, part C) -- such plans keep Ef
         if (u16) Ef_fly = Ef;
         Y = F;
-        if (u16) HIP_TRY(hipMalloc(&Y, cb * n * batch));
+        if (u16) { HIP_TRY(Y_own.reserve(cb * n * batch)); Y = Y_own; }
         // inter-pass twiddles W_N^(k1 n2): either the n-entry table in k_time's thread order, or (U16 plans) the two
         // small factor tables the kernel multiplies (ssfm_kernels.hpp twn_compute)
         if (u16 || sizeof(T) == 8) {
             const long long nA = (long long)(N1 / E) * N2, nB = (long long)E * N2;      // [tile][j][c], j < N1/E;  [tile][t][c], t < E
-            HIP_TRY(hipMalloc(&twA, cb * nA));
-            HIP_TRY(hipMalloc(&twB, cb * nB));
+            HIP_TRY(twA.reserve(cb * nA));
+            HIP_TRY(twB.reserve(cb * nB));
             const int C_ = cols_per_tile<T>();
-            hipLaunchKernelGGL(k_make_tw_tiles<T>, dim3((unsigned)((nA + 255) / 256)), dim3(256), 0, stream, twA, N1 / E, 1ll, N2, C_, (long long)n, (int)u16, N2 / Ef);
-            hipLaunchKernelGGL(k_make_tw_tiles<T>, dim3((unsigned)((nB + 255) / 256)), dim3(256), 0, stream, twB, E, (long long)(N1 / E), N2, C_, (long long)n, (int)u16, N2 / Ef);
+            hipLaunchKernelGGL(k_make_tw_tiles<T>, dim3((unsigned)((nA + 255) / 256)), dim3(256), 0, stream, twA.get(), N1 / E, 1ll, N2, C_, (long long)n, (int)u16, N2 / Ef);
+            hipLaunchKernelGGL(k_make_tw_tiles<T>, dim3((unsigned)((nB + 255) / 256)), dim3(256), 0, stream, twB.get(), E, (long long)(N1 / E), N2, C_, (long long)n, (int)u16, N2 / Ef);
         } else {
-            HIP_TRY(hipMalloc(&twN, cb * n));
-            hipLaunchKernelGGL(k_make_twN<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, twN, N1, N2, cols_per_tile<T>(), E, (int)u16, N2 / Ef);
+            HIP_TRY(twN.reserve(cb * n));
+            hipLaunchKernelGGL(k_make_twN<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, twN.get(), N1, N2, cols_per_tile<T>(), E, (int)u16, N2 / Ef);
         }
         if (int rc = make_line_table(&tw1, N1, E)) return rc;
         if (int rc = make_line_table(&tw2, N2, Ef)) return rc;
-        HIP_TRY(hipMalloc(&dnat, cb * n_full));
-        HIP_TRY(hipMalloc(&dperm, cb * n));
+        HIP_TRY(dnat.reserve(cb * n_full));
+        HIP_TRY(dperm.reserve(cb * n));
         if (is_split()) {
-            HIP_TRY(hipMalloc(&Fnat, cb * n_full * batch_full));
+            HIP_TRY(Fnat.reserve(cb * n_full * batch_full));
             HIP_TRY(hipMemsetAsync(Fnat, 0, cb * n_full * batch_full, stream));
-            HIP_TRY(hipMalloc(&split_twA, sizeof(double2) * (size_t)split_R * N1));
-            HIP_TRY(hipMalloc(&split_twB, sizeof(double2) * (size_t)split_R * N2));
+            HIP_TRY(split_twA.reserve(sizeof(double2) * (size_t)split_R * N1));
+            HIP_TRY(split_twB.reserve(sizeof(double2) * (size_t)split_R * N2));
             const long long nt = (long long)split_R * (N1 + N2);
-            hipLaunchKernelGGL(k_make_split_twiddles, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, stream, split_twA, split_twB, N1, N2, split_R);
+            hipLaunchKernelGGL(k_make_split_twiddles, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, stream, split_twA.get(), split_twB.get(), N1, N2, split_R);
             HIP_TRY(hipGetLastError());
         }
         if (Ef_fly != Ef) {
             if (int rc = make_line_table(&tw2_fly, N2, Ef_fly)) return rc;
-            HIP_TRY(hipMalloc(&dperm_fly, cb * n));
+            HIP_TRY(dperm_fly.reserve(cb * n));
         }
         if (const char* e = std::getenv("SSFM_ADAPT_FUSED")) fused_ok = std::atoi(e) != 0;
         if (const char* e = std::getenv("SSFM_MEDIUM")) medium_ok = std::atoi(e) != 0;
@@ -999,19 +1006,19 @@ template <typename T> struct PlanT : PlanBase {
         if (const char* e = std::getenv("SSFM_SMALL")) small = small && std::atoi(e) != 0;
         if (small) {
             if (int rc = make_line_table(&tw_small, (int)n, small_points<T>((int)n))) return rc;
-            HIP_TRY(hipMalloc(&dsmall, cb * n));
+            HIP_TRY(dsmall.reserve(cb * n));
         }
-        HIP_TRY(hipMalloc(&st, sizeof(AdaptState<T>)));
+        HIP_TRY(st.reserve(sizeof(AdaptState<T>)));
         HIP_TRY(hipMemsetAsync(P, 0, sizeof(T) * n * batch, stream));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(stream));
         if (nlanes > 1 && nlanes <= 4) {
             // every lane on a hardware queue of its own, and one on which its kernels really run beside lane 0's (rate_lane): rated with the plan's own
             // kernels on its own buffers, which hold nothing yet -- zeros (a transform of zeros is zeros; D~ = 0 is the identity)
-            HIP_TRY(hipEventCreate(&lane_e0));
-            HIP_TRY(hipEventCreate(&lane_e1));
-            HIP_TRY(hipEventCreate(&run_e0));
-            HIP_TRY(hipEventCreate(&run_e1));
+            HIP_TRY(hipEventCreate(lane_e0.out()));
+            HIP_TRY(hipEventCreate(lane_e1.out()));
+            HIP_TRY(hipEventCreate(run_e0.out()));
+            HIP_TRY(hipEventCreate(run_e1.out()));
             HIP_TRY(hipMemsetAsync(F, 0, cb * n * batch, stream));
             if (Y != F) HIP_TRY(hipMemsetAsync(Y, 0, cb * n * batch, stream));
             HIP_TRY(hipMemsetAsync(dperm, 0, cb * n, stream));
@@ -1080,15 +1087,16 @@ template <typename T> struct PlanT : PlanBase {
     // 0 = good, 1 = on a queue of its own but in lane 0's way (score = the ratio), 2 = shares a hardware queue with an earlier lane; < 0: error (g_err set)
     int rate_lane(int g, cx<T>* Fx, cx<T>* Yx, T* Px, float* score, float* alone_out, float* pair_out) {
         *score = 1e30f;
-        unsigned* words = nullptr;
-        if (hipMalloc(&words, 2 * sizeof(unsigned)) != hipSuccess) { (void)hipGetLastError(); return -1; }
         int shared = 0;
-        for (int k = 0; k < g && !shared; ++k) {
-            const int side = streams_run_side_by_side(lane_stream[k], lane_stream[g], words, fork_ev);
-            if (side < 0) { (void)hipFree(words); return -1; }
-            shared = side == 0;
+        {
+            DeviceBuffer<unsigned> words;
+            if (words.reserve(2 * sizeof(unsigned)) != hipSuccess) { (void)hipGetLastError(); return -1; }
+            for (int k = 0; k < g && !shared; ++k) {
+                const int side = streams_run_side_by_side(lane_stream[k], lane_stream[g], words, fork_ev);
+                if (side < 0) return -1;
+                shared = side == 0;
+            }
         }
-        (void)hipFree(words);
         if (shared) return 2;
         float alone = 1e30f, pair = 0.f;
         // (rows of 32 MiB and more -- complex128 plans of 2^21 points up, the lines of long chirp-z runs: a launch is 30-100 us long, a third of the probe steps measure it as well)
@@ -1124,9 +1132,9 @@ template <typename T> struct PlanT : PlanBase {
             int state = rate_lane(g, Fx, Yx, Px, &score, &alone, &pair);
             if (state < 0) return fail(SSFM_ERR_HIP, "lane rating failed: %s", hipGetErrorString(hipGetLastError()));
             for (int round = 0; round < 2 && state > 0; ++round) {
-                hipStream_t cand[4] = {nullptr, nullptr, nullptr, nullptr};
+                Stream cand[4];                  // (those that do not replace the lane's stream go when the round is over)
                 for (auto& c : cand)
-                    if (hipStreamCreateWithPriority(&c, hipStreamNonBlocking, prio_hi) != hipSuccess) { (void)hipGetLastError(); c = nullptr; }
+                    if (hipStreamCreateWithPriority(c.out(), hipStreamNonBlocking, prio_hi) != hipSuccess) { (void)hipGetLastError(); c.reset(); }
                 for (auto& c : cand) {
                     if (!c || state == 0) continue;
                     float sc = 0.f, al = 0.f, pr = 0.f;
@@ -1135,8 +1143,6 @@ template <typename T> struct PlanT : PlanBase {
                     if (st_c >= 0 && (st_c < state || (st_c == state && sc < score))) { state = st_c; score = sc; alone = al; pair = pr; *replaced = true; }
                     else std::swap(c, lane_stream[g]);
                 }
-                for (auto& c : cand)
-                    if (c) (void)hipStreamDestroy(c);
             }
             if (state != 0) all_good = false;
             if (state == 2) lanes_share_queue = true;
@@ -1178,12 +1184,12 @@ template <typename T> struct PlanT : PlanBase {
         ++lane_heals;
         HIP_TRY(hipStreamSynchronize(stream));
         const size_t cb = sizeof(cx<T>) * (size_t)n * batch;
-        cx<T>* Fx = nullptr; cx<T>* Yx = nullptr; T* Px = nullptr;
-        auto drop = [&]() { (void)hipFree(Fx); if (Yx != Fx) (void)hipFree(Yx); (void)hipFree(Px); };
-        if (hipMalloc(&Fx, cb) != hipSuccess) { (void)hipGetLastError(); return SSFM_OK; }       // (no memory for the scratch fields: the run's result is right, only slow)
-        Yx = Fx;
-        if (Y != F && hipMalloc(&Yx, cb) != hipSuccess) { (void)hipGetLastError(); Yx = Fx; drop(); return SSFM_OK; }
-        if (hipMalloc(&Px, sizeof(T) * (size_t)n * batch) != hipSuccess) { (void)hipGetLastError(); drop(); return SSFM_OK; }
+        DeviceBuffer<cx<T>> Fx_own, Yx_own;          // (scratch fields that live for this rating)
+        DeviceBuffer<T> Px_own;
+        if (Fx_own.reserve(cb) != hipSuccess) { (void)hipGetLastError(); return SSFM_OK; }       // (no memory for the scratch fields: the run's result is right, only slow)
+        if (Y != F && Yx_own.reserve(cb) != hipSuccess) { (void)hipGetLastError(); return SSFM_OK; }
+        if (Px_own.reserve(sizeof(T) * (size_t)n * batch) != hipSuccess) { (void)hipGetLastError(); return SSFM_OK; }
+        cx<T>* const Fx = Fx_own; cx<T>* const Yx = Y != F ? Yx_own.get() : Fx; T* const Px = Px_own;
         (void)hipMemsetAsync(Fx, 0, cb, stream);
         if (Yx != Fx) (void)hipMemsetAsync(Yx, 0, cb, stream);
         (void)hipMemsetAsync(Px, 0, sizeof(T) * (size_t)n * batch, stream);
@@ -1191,7 +1197,6 @@ template <typename T> struct PlanT : PlanBase {
         bool replaced = false;
         const int rc = rate_and_replace_lanes(Fx, Yx, Px, &replaced);
         (void)hipStreamSynchronize(stream);
-        drop();
         if (rc != SSFM_OK) return rc;
         if (replaced) ++lanes_remade;
         if (lanes_ok) {
@@ -1209,7 +1214,7 @@ template <typename T> struct PlanT : PlanBase {
 
     // stage twiddles of a line of length L in thread-load order (wgfft.hpp "Table layout"), computed
     // in double on the host and rounded once
-    int make_line_table(cx<T>** out, int L, int E) {
+    int make_line_table(DeviceBuffer<cx<T>>* out, int L, int E) {
         const int M = fft_nstages(L, E);
         const int total = fft_tw_entries(L, E, (int)sizeof(T));
         std::vector<cx<T>> tab((size_t)(total > 0 ? total : 1));
@@ -1228,20 +1233,19 @@ template <typename T> struct PlanT : PlanBase {
                         tab[(size_t)off + (size_t)fft_tw_index(L, S, E, (int)sizeof(T), i * (R - 1) + (u - 1), ku)] = w;
                     }
         }
-        HIP_TRY(hipMalloc(out, sizeof(cx<T>) * tab.size()));
-        HIP_TRY(hipMemcpy(*out, tab.data(), sizeof(cx<T>) * tab.size(), hipMemcpyHostToDevice));
+        HIP_TRY(out->reserve(sizeof(cx<T>) * tab.size()));
+        HIP_TRY(hipMemcpy(out->get(), tab.data(), sizeof(cx<T>) * tab.size(), hipMemcpyHostToDevice));
         return SSFM_OK;
     }
 
 #if SSFM_TRACE
-    unsigned long long* trace_buf = nullptr;
+    DeviceBuffer<unsigned long long> trace_buf;
     int trace_cap = 0; std::atomic<int> trace_next{0};
     std::vector<int> trace_kind;        // per slot: kind*16 + lane
     int trace_begin(int launches) {
         if (!std::getenv("SSFM_TRACE_FILE")) return SSFM_OK;
         if (trace_cap < launches) {
-            (void)hipFree(trace_buf);
-            HIP_TRY(hipMalloc(&trace_buf, sizeof(unsigned long long) * 1024 * launches));
+            HIP_TRY(trace_buf.reserve(sizeof(unsigned long long) * 1024 * launches));
             trace_cap = launches;
         }
         HIP_TRY(hipMemset(trace_buf, 0, sizeof(unsigned long long) * 1024 * launches));
@@ -1333,41 +1337,21 @@ template <typename T> struct PlanT : PlanBase {
     // fixed-step runs of a dual-polarisation plan of long rows: one launch per row (see run_medium)
     bool medium_rows_split() const { return medium_split_ok && batch == 2 && n >= (1ll << 16); }
     // the whole schedule in one launch (k_medium); `distinct` holds at most kMaxTables step sizes
-    int run_medium(T gamma, double gamma_d, const T* h, int64_t nsteps, const std::vector<T>& distinct, bool phase) {
-        if constexpr (sizeof(T) != 4) { (void)gamma; (void)gamma_d; (void)h; (void)nsteps; (void)distinct; (void)phase; return fail(SSFM_ERR_STATE, "the medium engine is complex64 only"); }
+    int run_medium(T gamma, double gamma_d, const Schedule<T>& sch, bool phase) {
+        if constexpr (sizeof(T) != 4) { (void)gamma; (void)gamma_d; (void)sch; (void)phase; return fail(SSFM_ERR_STATE, "the medium engine is complex64 only"); }
         else {
+        const std::vector<T>& distinct = sch.distinct;
+        const int64_t nsteps = sch.size();
         MediumArgs<T> a;
         std::memset(&a, 0, sizeof(a));
         if (int rc = tables_for(distinct, a.tab, false, phase ? 1 : 0)) return rc;
         for (size_t i = 0; i < distinct.size(); ++i) { const T xr = op_re0 * distinct[i]; a.amp[i] = (T)std::exp((double)xr) * inv_n(); }
-        const size_t hb = sizeof(T) * (size_t)nsteps, need = hb + (size_t)nsteps;
-        if (d_hs_cap < need) {
-            (void)hipFree(d_hs); d_hs = nullptr; d_hs_cap = 0;
-            HIP_TRY(hipMalloc(&d_hs, need + need / 2));
-            d_hs_cap = need + need / 2;
-        }
-        HIP_TRY(hipStreamSynchronize(stream));             // the staging vector may still feed the previous run's copy
-        h_sched.resize(need);
-        std::memcpy(h_sched.data(), h, hb);
-        for (int64_t s = 0; s < nsteps; ++s) {
-            unsigned char w = 0;
-            for (size_t i = 0; i < distinct.size(); ++i)
-                if (std::memcmp(&distinct[i], &h[s], sizeof(T)) == 0) w = (unsigned char)i;
-            h_sched[hb + (size_t)s] = w;
-        }
-        HIP_TRY(hipMemcpyAsync(d_hs, h_sched.data(), need, hipMemcpyHostToDevice, stream));
-        const size_t fb = sizeof(cx<T>) * n * batch;
-        if (!fused_backup) HIP_TRY(hipMalloc(&fused_backup, fb));
-        HIP_TRY(hipMemcpyAsync(fused_backup, F, fb, hipMemcpyDeviceToDevice, stream));          // for a repeat on the two-kernel engine
-        if (!medium_st) {
-            HIP_TRY(hipMalloc(&medium_st, sizeof(unsigned long long) * 2 * (kBarShards + kBarWords + 2)));
-            HIP_TRY(hipHostMalloc(&medium_err_host, 2 * sizeof(unsigned)));
-            medium_err_host[0] = medium_err_host[1] = 0u;
-        }
-        constexpr size_t kSet = kBarShards + kBarWords + 2;
+        if (int rc = upload_schedule(sch)) return rc;
+        if (int rc = backup_field()) return rc;                  // for a repeat on the two-kernel engine
+        if (int rc = ensure_medium_state()) return rc;
         HIP_TRY(hipMemsetAsync(medium_st, 0, sizeof(unsigned long long) * 2 * kSet, stream));
         a.F = F; a.Y = Y; a.P = P; a.twA = twA; a.twB = twB; a.tw1 = tw1; a.tw2 = tw2;
-        a.hs = d_hs; a.which = reinterpret_cast<const unsigned char*>(d_hs) + hb;
+        a.hs = d_hs; a.which = d_which(sch);
         a.bar = medium_st; a.error = reinterpret_cast<unsigned*>(medium_st + kBarShards + kBarWords); a.patience = medium_patience;
         if (int rc = pick_xcc()) return rc;
         a.xcc = (unsigned)medium_xcc;
@@ -1379,8 +1363,8 @@ template <typename T> struct PlanT : PlanBase {
         a.nblk = (unsigned)((N2 / cols_per_tile<T>()) * a.rows);
         if (two) {
             if (!medium_stream2) {
-                HIP_TRY(hipStreamCreateWithFlags(&medium_stream2, hipStreamNonBlocking));
-                HIP_TRY(hipEventCreateWithFlags(&medium_ev2, hipEventDisableTiming));
+                HIP_TRY(hipStreamCreateWithFlags(medium_stream2.out(), hipStreamNonBlocking));
+                HIP_TRY(hipEventCreateWithFlags(medium_ev2.out(), hipEventDisableTiming));
             }
             HIP_TRY(hipEventRecord(fork_ev, stream));                  // (behind the uploads and the backup copy, ahead of the first launch)
             HIP_TRY(hipStreamWaitEvent(medium_stream2, fork_ev, 0));
@@ -1404,7 +1388,7 @@ template <typename T> struct PlanT : PlanBase {
             HIP_TRY(hipEventRecord(medium_ev2, medium_stream2));
             HIP_TRY(hipStreamWaitEvent(stream, medium_ev2, 0));
         }
-        medium_sched.assign(h, h + nsteps);
+        medium_sched = sch.steps;
         medium_gamma = gamma_d;
         medium_pending = true;
         return SSFM_OK;
@@ -1469,23 +1453,23 @@ template <typename T> struct PlanT : PlanBase {
             rr = (v + 1) % kMaxTables;
             pinned[v] = true;
             t.valid = false;
-            if (!t.ptr) HIP_TRY(hipMalloc(&t.ptr, sizeof(cx<T>) * n_full));
+            HIP_TRY(t.ptr.reserve(sizeof(cx<T>) * n_full));
             t.kind = kind;
             if (is_split() && kind == 1)
                 hipLaunchKernelGGL(k_make_split_phase_table<T>, dim3((unsigned)((n_full + 255) / 256)), dim3(256), 0, stream,
-                                   (const cx<T>*)dnat, reinterpret_cast<unsigned*>(t.ptr), N1, N2, split_R, distinct[i], split_qf());
+                                   (const cx<T>*)dnat, reinterpret_cast<unsigned*>(t.ptr.get()), N1, N2, split_R, distinct[i], split_qf());
             else if (is_split())
                 hipLaunchKernelGGL((k_make_split_table<T, 2>), dim3((unsigned)((n_full + 255) / 256)), dim3(256), 0, stream,
-                                   (const cx<T>*)dnat, t.ptr, N1, N2, split_R, distinct[i], inv_n_full(), split_qf());
+                                   (const cx<T>*)dnat, t.ptr.get(), N1, N2, split_R, distinct[i], inv_n_full(), split_qf());
             else if (one_line)
                 hipLaunchKernelGGL((k_make_freq_table<T, 2>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
-                                   (const cx<T>*)dnat, t.ptr, 1, (int)n, (int)n / small_points<T>((int)n), distinct[i], inv_n());
+                                   (const cx<T>*)dnat, t.ptr.get(), 1, (int)n, (int)n / small_points<T>((int)n), distinct[i], inv_n());
             else if (kind == 1)
                 hipLaunchKernelGGL(k_make_phase_table<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
-                                   (const cx<T>*)dnat, reinterpret_cast<unsigned*>(t.ptr), N1, N2, N2 / Ef, distinct[i]);
+                                   (const cx<T>*)dnat, reinterpret_cast<unsigned*>(t.ptr.get()), N1, N2, N2 / Ef, distinct[i]);
             else
                 hipLaunchKernelGGL((k_make_freq_table<T, 2>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
-                                   (const cx<T>*)dnat, t.ptr, N1, N2, N2 / Ef, distinct[i], inv_n());
+                                   (const cx<T>*)dnat, t.ptr.get(), N1, N2, N2 / Ef, distinct[i], inv_n());
             HIP_TRY(hipGetLastError());
             t.h = distinct[i]; t.valid = true;
             out[i] = t.ptr;
@@ -1520,8 +1504,8 @@ template <typename T> struct PlanT : PlanBase {
         else {
         if (!u16 || !op_flat_re || Ef_fly % 4 != 0) return false;
         if (!dimag_valid) {
-            if (!dimag_fly && hipMalloc(&dimag_fly, sizeof(T) * n) != hipSuccess) { (void)hipGetLastError(); return false; }
-            hipLaunchKernelGGL(k_make_imag_table<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const cx<T>*)dnat, dimag_fly, N1, N2, N2 / Ef_fly);
+            if (dimag_fly.reserve(sizeof(T) * n) != hipSuccess) { (void)hipGetLastError(); return false; }
+            hipLaunchKernelGGL(k_make_imag_table<T>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream, (const cx<T>*)dnat, dimag_fly.get(), N1, N2, N2 / Ef_fly);
             if (hipGetLastError() != hipSuccess) return false;
             dimag_valid = true;
         }
@@ -1530,7 +1514,7 @@ template <typename T> struct PlanT : PlanBase {
     }
     // k_freq<FM_FLY>: D~ and the row twiddles in the order of ITS points per thread
     FreqArgs<T> fargs_fly(T h, const AdaptState<T>* s, int row0 = 0, int lane = 0) {
-        FreqArgs<T> a = fargs(dperm_fly ? dperm_fly : dperm, h, s, row0, lane);
+        FreqArgs<T> a = fargs(dperm_fly ? dperm_fly.get() : dperm.get(), h, s, row0, lane);
         if (tw2_fly) a.tw2 = tw2_fly;
         return a;
     }
@@ -1543,27 +1527,12 @@ template <typename T> struct PlanT : PlanBase {
     }
 
     // the whole schedule in one launch (k_small); `distinct` holds at most kMaxTables step sizes
-    int run_small(T gamma, const T* h, int64_t nsteps, const std::vector<T>& distinct, cx<T>* dsnap = nullptr) {
+    int run_small(T gamma, const Schedule<T>& sch, cx<T>* dsnap = nullptr) {
         SmallArgs<T> a;
         std::memset(&a, 0, sizeof(a));
-        if (int rc = tables_for(distinct, a.tab, true)) return rc;
-        const size_t hb = sizeof(T) * (size_t)nsteps, need = hb + (size_t)nsteps;
-        if (d_hs_cap < need) {
-            (void)hipFree(d_hs); d_hs = nullptr; d_hs_cap = 0;
-            HIP_TRY(hipMalloc(&d_hs, need + need / 2));
-            d_hs_cap = need + need / 2;
-        }
-        HIP_TRY(hipStreamSynchronize(stream));             // the staging vector may still feed the previous run's copy
-        h_sched.resize(need);
-        std::memcpy(h_sched.data(), h, hb);
-        for (int64_t s = 0; s < nsteps; ++s) {
-            unsigned char w = 0;
-            for (size_t i = 0; i < distinct.size(); ++i)
-                if (std::memcmp(&distinct[i], &h[s], sizeof(T)) == 0) w = (unsigned char)i;
-            h_sched[hb + (size_t)s] = w;
-        }
-        HIP_TRY(hipMemcpyAsync(d_hs, h_sched.data(), need, hipMemcpyHostToDevice, stream));
-        a.F = F; a.hs = d_hs; a.which = reinterpret_cast<const unsigned char*>(d_hs) + hb; a.tw = tw_small; a.snap = dsnap; a.gamma = gamma; a.nsteps = (int)nsteps;
+        if (int rc = tables_for(sch.distinct, a.tab, true)) return rc;
+        if (int rc = upload_schedule(sch)) return rc;
+        a.F = F; a.hs = d_hs; a.which = d_which(sch); a.tw = tw_small; a.snap = dsnap; a.gamma = gamma; a.nsteps = (int)sch.size();
         ++last_launches;
         HIP_TRY(launch_small<T>((int)n, batch, stream, a));
         return SSFM_OK;
@@ -1606,22 +1575,16 @@ template <typename T> struct PlanT : PlanBase {
         if (int rc = use_device()) return rc;
         if (int rc = lane_health()) return rc;             // (the previous run, if it was a long two-lane run: slow lanes are repaired before this one is enqueued)
         const T gamma = (T)gamma_d;
-        const int nrows = N1 * batch;
         const int nlanes = lanes_active;                   // (shadows the configured number: a plan that dropped to one lane drives its rows on one stream)
         last_launches = 0;
         timed = false;
         if (nsteps <= 0) return SSFM_OK;
-        for (int64_t s = 0; s < nsteps; ++s)
-            if (!(h[s] > (T)0) || !std::isfinite((double)h[s]))
-                return fail(SSFM_ERR_INVALID, "ssfm_propagate_fixed: step %lld is %g km (must be finite and > 0)", (long long)s, (double)h[s]);
         // distinct step sizes -> operator tables (normally 1, +1 for a short last step)
-        std::vector<T> distinct;
-        for (int64_t s = 0; s < nsteps && distinct.size() <= (size_t)kMaxTables; ++s) {
-            bool seen = false;
-            for (T d : distinct) seen = seen || std::memcmp(&d, &h[s], sizeof(T)) == 0;
-            if (!seen) distinct.push_back(h[s]);
-        }
-        const bool use_tables = distinct.size() <= (size_t)kMaxTables && !force_fly;
+        const Schedule<T> sch(h, nsteps, kMaxTables);
+        if (!sch.valid())
+            return fail(SSFM_ERR_INVALID, "ssfm_propagate_fixed: step %lld is %g km (must be finite and > 0)", (long long)sch.first_bad, (double)h[sch.first_bad]);
+        const std::vector<T>& distinct = sch.distinct;
+        const bool use_tables = sch.fits_tables() && !force_fly;
         std::vector<const cx<T>*> tabptr(distinct.size(), nullptr);
         const bool small_sched = small && use_tables && !profiling && nsteps <= 0x7fffffff;
         // a fibre's operator has one modulus for all frequencies: 4-byte phase tables (ssfm_kernels.hpp FM_PHASE)
@@ -1643,22 +1606,17 @@ template <typename T> struct PlanT : PlanBase {
         last_engine = (go_small || (small_sched && snapshots != nullptr)) ? SSFM_ENGINE_SMALL : go_medium ? SSFM_ENGINE_MEDIUM : is_split() ? SSFM_ENGINE_SPLIT : SSFM_ENGINE_TWO_KERNEL;
         if (use_tables && !go_small && !go_medium)
             if (int rc = tables_for(distinct, tabptr.data(), false, use_phase ? 1 : 0)) return rc;
-        auto freq_rows = [&](T hs, int row0, int rows, hipStream_t st_) -> hipError_t {
+        auto freq_rows = [&](int64_t s, int row0, int rows, hipStream_t st_) -> hipError_t {
             const int lane_ = rows > 0 ? row0 / rows : 0;
+            const T hs = h[s];
+            const cx<T>* const tp = use_tables ? tabptr[sch.which[(size_t)s]] : nullptr;
             ++last_launches;
             if (is_split()) {
-                const cx<T>* tp = nullptr;
-                if (use_tables)
-                    for (size_t i = 0; i < distinct.size(); ++i)
-                        if (std::memcmp(&distinct[i], &hs, sizeof(T)) == 0) tp = tabptr[i];
                 last_launches += 2;
                 const T xr = op_re0 * hs;
                 return split_freq(tp, hs, nullptr, 0, row0, rows, st_, use_phase, (T)std::exp((double)xr) * inv_n_full());
             }
             if (use_tables) {
-                const cx<T>* tp = nullptr;
-                for (size_t i = 0; i < distinct.size(); ++i)
-                    if (std::memcmp(&distinct[i], &hs, sizeof(T)) == 0) tp = tabptr[i];
                 if (use_phase) {
                     FreqArgs<T> fa = fargs(tp, hs, nullptr, row0, lane_);
                     // the modulus as the complex table forms it: e = exp(Re * h) with the product in T, then e * (1/N) (exact: N = 2^k)
@@ -1670,13 +1628,29 @@ template <typename T> struct PlanT : PlanBase {
             }
             return launch_freq<T, FM_FLY>(N2, N1 * rows, st_, fargs_fly(hs, nullptr, row0, lane_), Ef_fly);
         };
-        auto freq = [&](T hs) -> hipError_t { return freq_rows(hs, 0, batch, stream); };
-        (void)nrows;
+        auto freq = [&](int64_t s) -> hipError_t { return freq_rows(s, 0, batch, stream); };
         const T half = (T)0.5;
         for (auto& p : prof) p.n = 0;
         HIP_TRY(hipEventRecord(ev0, stream));
         const bool health = snapshots == nullptr && !go_small && !go_medium && nlanes > 1 && !profiling && !SSFM_TRACE && nsteps >= 64 && run_e0 != nullptr && cap_run == nullptr;
         if (health) HIP_TRY(hipEventRecord(run_e0, stream));
+        // The sequence of a run is BEGIN, (row pass, MID)*, row pass, END on every lane: lane g drives `rows` rows from row g * rows on lane_stream[g] (one lane:
+        // all rows on the plan's stream, which is lane 0's).  The three launches of it, spelled once; the drivers below differ in the ORDER they issue them in.
+        const int rows = batch / nlanes;
+        auto col_begin = [&](int g, int rows_, hipStream_t st_) -> hipError_t {
+            TimeArgs<T> a = targs(gamma, 0, h[0] * half, nullptr, g * rows_, g);
+            if (cap_run) a.scal = cap_run->scal_at(0, g * rows_);
+            ++last_launches;
+            return launch_time<T, TM_BEGIN>(N1, rows_, st_, a, E);
+        };
+        auto row_pass = [&](int g, int64_t s) -> hipError_t { return freq_rows(s, g * rows, rows, lane_stream[g]); };
+        auto col_after = [&](int g, int64_t s) -> hipError_t {            // MID between two steps, END behind the last one
+            const bool last = s + 1 == nsteps;
+            TimeArgs<T> a = targs(gamma, h[s] * half, last ? (T)0 : h[s + 1] * half, nullptr, g * rows, g);
+            if (cap_run) a.scal = cap_run->scal_at(s + 1, g * rows);
+            ++last_launches;
+            return last ? launch_time<T, TM_END>(N1, rows, lane_stream[g], a, E) : launch_time<T, TM_MID>(N1, rows, lane_stream[g], a, E);
+        };
         // one lane's launches, start to end.  A capture run (cap_run) adds: the scalar log's address to the column launches, and at a capture step an END
         // launch BESIDE the run -- it only reads the half-transformed field and writes this step's time-order field straight into a slot of a device block
         // (no copy of F); the MID behind it continues exactly as a run without capture does, so the snapshots and the end field are a plain run's, bit for
@@ -1684,18 +1658,14 @@ template <typename T> struct PlanT : PlanBase {
         // through.  Before a block is written again the lane's THREAD waits (on the host) until the helper has seen its transfer complete: the lanes'
         // threads run ahead of the GPU by at most the ring of blocks, the GPU never waits as long as PCIe keeps up.
         auto lane_run = [&](int g) -> int {
-            const int rows = batch / nlanes;
             CapRun* const cr = cap_run;
             const bool snaps = cr && cr->every > 0;
             auto body = [&]() -> int {
                 // (round 6 A/B: starting lane 1 of a complex128 run 5 ... 40 us late changes nothing -- 38.6-39.4 against 38.6-38.9 us per step, profiles/r06_c1_ab.txt)
-                TimeArgs<T> tb = targs(gamma, 0, h[0] * half, nullptr, g * rows, g);
-                if (cr) tb.scal = cr->scal_at(0, g * rows);
-                ++last_launches;
-                HIP_TRY((launch_time<T, TM_BEGIN>(N1, rows, lane_stream[g], tb, E)));
+                HIP_TRY(col_begin(g, rows, lane_stream[g]));
                 int64_t k = 1;                                       // the next snapshot
                 for (int64_t s = 0; s < nsteps; ++s) {
-                    HIP_TRY(freq_rows(h[s], g * rows, rows, lane_stream[g]));
+                    HIP_TRY(row_pass(g, s));
                     const bool last = s + 1 == nsteps;
                     if (snaps && !last && (s + 1) % cr->every == 0) {
                         const int64_t j = k - 1, fl = j / cr->per_block, slot = j % cr->per_block;
@@ -1712,19 +1682,9 @@ template <typename T> struct PlanT : PlanBase {
                         }
                         ++k;
                     }
-                    if (last) {
-                        if (snaps && !in_place() && !cr->wait_for(cr->input_done, 1))    // (the input's transfer reads F, which this launch overwrites)
-                            return fail(SSFM_ERR_HIP, "ssfm_propagate_fixed_capture: the transfers failed");
-                        TimeArgs<T> te = targs(gamma, h[s] * half, 0, nullptr, g * rows, g);
-                        if (cr) te.scal = cr->scal_at(s + 1, g * rows);
-                        ++last_launches;
-                        HIP_TRY((launch_time<T, TM_END>(N1, rows, lane_stream[g], te, E)));
-                    } else {
-                        TimeArgs<T> tm = targs(gamma, h[s] * half, h[s + 1] * half, nullptr, g * rows, g);
-                        if (cr) tm.scal = cr->scal_at(s + 1, g * rows);
-                        ++last_launches;
-                        HIP_TRY((launch_time<T, TM_MID>(N1, rows, lane_stream[g], tm, E)));
-                    }
+                    if (last && snaps && !in_place() && !cr->wait_for(cr->input_done, 1))    // (the input's transfer reads F, which the END overwrites)
+                        return fail(SSFM_ERR_HIP, "ssfm_propagate_fixed_capture: the transfers failed");
+                    HIP_TRY(col_after(g, s));
                 }
                 return SSFM_OK;
             };
@@ -1732,78 +1692,57 @@ template <typename T> struct PlanT : PlanBase {
             if (rc != SSFM_OK && cr) cr->failed.store(1);
             return rc;
         };
+        auto fork_lanes = [&]() -> int {
+            HIP_TRY(hipEventRecord(fork_ev, stream));
+            for (int g = 1; g < nlanes; ++g) HIP_TRY(hipStreamWaitEvent(lane_stream[g], fork_ev, 0));
+            return SSFM_OK;
+        };
+        auto join_lanes = [&]() -> int {
+            for (int g = 1; g < nlanes; ++g) {
+                HIP_TRY(hipEventRecord(lane_ev[g], lane_stream[g]));
+                HIP_TRY(hipStreamWaitEvent(stream, lane_ev[g], 0));
+            }
+            return SSFM_OK;
+        };
         auto enqueue_steps = [&]() -> int {
             if (cap_run != nullptr && nlanes == 1) return lane_run(0);
             if (nlanes > 1 && ((lane_threads && !profiling && nsteps >= 16) || cap_run != nullptr)) {
                 // every lane from a host thread of its own (LaneWorker): lane 0 from this one
-                HIP_TRY(hipEventRecord(fork_ev, stream));
-                for (int g = 1; g < nlanes; ++g) HIP_TRY(hipStreamWaitEvent(lane_stream[g], fork_ev, 0));
+                if (int rc = fork_lanes()) return rc;
                 for (int g = 1; g < nlanes; ++g) { lane_worker[g].start(device); lane_worker[g].submit([&lane_run, g] { return lane_run(g); }); }
                 int rc = lane_run(0);
                 for (int g = 1; g < nlanes; ++g) { const int r = lane_worker[g].wait(); if (rc == SSFM_OK) rc = r; }
                 if (rc != SSFM_OK) return rc;
-                for (int g = 1; g < nlanes; ++g) {
-                    HIP_TRY(hipEventRecord(lane_ev[g], lane_stream[g]));
-                    HIP_TRY(hipStreamWaitEvent(stream, lane_ev[g], 0));
-                }
-                return SSFM_OK;
+                return join_lanes();
             }
-            if (nlanes > 1) {
-                const int rows = batch / nlanes;
-                HIP_TRY(hipEventRecord(fork_ev, stream));
-                for (int g = 1; g < nlanes; ++g) HIP_TRY(hipStreamWaitEvent(lane_stream[g], fork_ev, 0));
+            // all lanes from this thread, interleaved: every lane's row pass, then every lane's column pass, step by step (one lane: the plan's stream alone)
+            if (nlanes > 1) if (int rc = fork_lanes()) return rc;
+            for (int g = 0; g < nlanes; ++g) {
+                if (int rc = prof_mark(-1, g)) return rc;
+                HIP_TRY(col_begin(g, rows, lane_stream[g]));
+                if (int rc = prof_mark(0, g)) return rc;
+            }
+            for (int64_t s = 0; s < nsteps; ++s) {
                 for (int g = 0; g < nlanes; ++g) {
-                    if (int rc = prof_mark(-1, g)) return rc;
-                    ++last_launches;
-                    HIP_TRY((launch_time<T, TM_BEGIN>(N1, rows, lane_stream[g], targs(gamma, 0, h[0] * half, nullptr, g * rows, g), E)));
+                    HIP_TRY(row_pass(g, s));
+                    if (int rc = prof_mark(1, g)) return rc;
+                }
+                for (int g = 0; g < nlanes; ++g) {
+                    HIP_TRY(col_after(g, s));
                     if (int rc = prof_mark(0, g)) return rc;
                 }
-                for (int64_t s = 0; s < nsteps; ++s) {
-                    for (int g = 0; g < nlanes; ++g) {
-                        HIP_TRY(freq_rows(h[s], g * rows, rows, lane_stream[g]));
-                        if (int rc = prof_mark(1, g)) return rc;
-                    }
-                    for (int g = 0; g < nlanes; ++g) {
-                        ++last_launches;
-                        if (s + 1 < nsteps)
-                            HIP_TRY((launch_time<T, TM_MID>(N1, rows, lane_stream[g], targs(gamma, h[s] * half, h[s + 1] * half, nullptr, g * rows, g), E)));
-                        else
-                            HIP_TRY((launch_time<T, TM_END>(N1, rows, lane_stream[g], targs(gamma, h[s] * half, 0, nullptr, g * rows, g), E)));
-                        if (int rc = prof_mark(0, g)) return rc;
-                    }
-                }
-                for (int g = 0; g < nlanes; ++g) if (int rc = prof_mark(2, g)) return rc;
-                for (int g = 1; g < nlanes; ++g) {
-                    HIP_TRY(hipEventRecord(lane_ev[g], lane_stream[g]));
-                    HIP_TRY(hipStreamWaitEvent(stream, lane_ev[g], 0));
-                }
-            } else {
-                if (int rc = prof_mark(-1)) return rc;
-                ++last_launches;
-                HIP_TRY((launch_time<T, TM_BEGIN>(N1, batch, stream, targs(gamma, 0, h[0] * half, nullptr), E)));
-                if (int rc = prof_mark(0)) return rc;
-                for (int64_t s = 0; s < nsteps; ++s) {
-                    HIP_TRY(freq(h[s]));
-                    if (int rc = prof_mark(1)) return rc;
-                    ++last_launches;
-                    if (s + 1 < nsteps)
-                        HIP_TRY((launch_time<T, TM_MID>(N1, batch, stream, targs(gamma, h[s] * half, h[s + 1] * half, nullptr), E)));
-                    else
-                        HIP_TRY((launch_time<T, TM_END>(N1, batch, stream, targs(gamma, h[s] * half, 0, nullptr), E)));
-                    if (int rc = prof_mark(0)) return rc;
-                }
-                if (int rc = prof_mark(2)) return rc;
             }
-            return SSFM_OK;
+            for (int g = 0; g < nlanes; ++g) if (int rc = prof_mark(2, g)) return rc;
+            return join_lanes();
         };
         if (snapshots == nullptr) {
 #if SSFM_TRACE
             if (int rc = trace_begin((int)(2 * nsteps + 1) * nlanes)) return rc;
 #endif
             if (go_small) {
-                if (int rc = run_small(gamma, h, nsteps, distinct)) return rc;
+                if (int rc = run_small(gamma, sch)) return rc;
             } else if (go_medium) {
-                if (int rc = run_medium(gamma, gamma_d, h, nsteps, distinct, use_phase)) return rc;
+                if (int rc = run_medium(gamma, gamma_d, sch, use_phase)) return rc;
                 if (external_order) {          // (see external_order: the caller may consume the field stream-ordered, without ssfm_synchronize)
                     HIP_TRY(hipEventRecord(ev1, stream));
                     timed = true;
@@ -1822,19 +1761,19 @@ template <typename T> struct PlanT : PlanBase {
             size_t free_b = 0, total_b = 0;
             HIP_TRY(hipMemGetInfo(&free_b, &total_b));
             int64_t block = (int64_t)std::min<size_t>((size_t)(nsteps + 1), std::max<size_t>(1, std::min<size_t>(free_b / 2, size_t(8) << 30) / fb));
-            char* dsnap = nullptr;
-            HIP_TRY(hipMalloc(&dsnap, fb * (size_t)block));
+            DeviceBuffer<char> dsnap;                       // (lives for this call)
+            HIP_TRY(dsnap.reserve(fb * (size_t)block));
             if (!(small_sched && block == nsteps + 1)) last_engine = is_split() ? SSFM_ENGINE_SPLIT : SSFM_ENGINE_TWO_KERNEL;
             if (small_sched && block == nsteps + 1) {
                 // a small plan whose whole capture fits the device: the single launch writes every snapshot itself
                 hipError_t e = hipMemcpyAsync(dsnap, F, fb, hipMemcpyDeviceToDevice, stream);             // the input
-                int rc = e == hipSuccess ? run_small(gamma, h, nsteps, distinct, reinterpret_cast<cx<T>*>(dsnap)) : fail(SSFM_ERR_HIP, "snapshot copy failed: %s", hipGetErrorString(e));
+                int rc = e == hipSuccess ? run_small(gamma, sch, reinterpret_cast<cx<T>*>(dsnap.get())) : fail(SSFM_ERR_HIP, "snapshot copy failed: %s", hipGetErrorString(e));
                 if (rc == SSFM_OK) {
                     e = hipMemcpyAsync(snap, dsnap, fb * (size_t)(nsteps + 1), hipMemcpyDeviceToHost, stream);
                     if (e == hipSuccess) e = hipStreamSynchronize(stream);
                     if (e != hipSuccess) rc = fail(SSFM_ERR_HIP, "snapshot download failed: %s", hipGetErrorString(e));
                 }
-                (void)hipFree(dsnap);
+                dsnap.free();
                 if (rc != SSFM_OK) return rc;
                 HIP_TRY(hipEventRecord(ev1, stream));
                 timed = true;
@@ -1843,7 +1782,7 @@ template <typename T> struct PlanT : PlanBase {
             auto flush = [&](int64_t first, int64_t count) -> int {
                 hipError_t e = hipMemcpyAsync(snap + fb * first, dsnap, fb * (size_t)count, hipMemcpyDeviceToHost, stream);
                 if (e == hipSuccess) e = hipStreamSynchronize(stream);
-                if (e != hipSuccess) { (void)hipFree(dsnap); return fail(SSFM_ERR_HIP, "snapshot download failed: %s", hipGetErrorString(e)); }
+                if (e != hipSuccess) return fail(SSFM_ERR_HIP, "snapshot download failed: %s", hipGetErrorString(e));
                 return SSFM_OK;
             };
             int64_t first = 0, held = 0;                    // snapshots [first, first + held) are in dsnap
@@ -1853,13 +1792,13 @@ template <typename T> struct PlanT : PlanBase {
                 if (held == block) { if (int rc = flush(first, held)) return rc; first += held; held = 0; }
                 last_launches += 2;
                 ce = launch_time<T, TM_BEGIN>(N1, batch, stream, targs(gamma, 0, h[s] * half, nullptr), E);
-                if (ce == hipSuccess) ce = freq(h[s]);
+                if (ce == hipSuccess) ce = freq(s);
                 if (ce == hipSuccess) ce = launch_time<T, TM_END>(N1, batch, stream, targs(gamma, h[s] * half, 0, nullptr), E);
                 if (ce == hipSuccess) ce = capture();
             }
-            if (ce != hipSuccess) { (void)hipFree(dsnap); return fail(SSFM_ERR_HIP, "snapshot run failed: %s", hipGetErrorString(ce)); }
+            if (ce != hipSuccess) return fail(SSFM_ERR_HIP, "snapshot run failed: %s", hipGetErrorString(ce));
             if (int rc = flush(first, held)) return rc;
-            HIP_TRY(hipFree(dsnap));
+            dsnap.free();                                   // (here, not at the end of the call: the run's closing event goes behind the wait that hipFree is)
         }
         ran();
         if (int rc = publish_if_external()) return rc;          // (a caller that orders its own work on the stream finds the natural-order field)
@@ -1897,7 +1836,7 @@ template <typename T> struct PlanT : PlanBase {
             const bool snaps = cr->every > 0;
             if (snaps) {                                                // snapshot 0: the input, from F
                 HIP_TRY(hipEventSynchronize(cap_ev_in));
-                HIP_TRY(hipMemcpyAsync(cr->host, in_place() ? cap_in : reinterpret_cast<const char*>(F), cr->fb, hipMemcpyDeviceToHost, cap_stream));
+                HIP_TRY(hipMemcpyAsync(cr->host, in_place() ? cap_in.get() : reinterpret_cast<const char*>(F), cr->fb, hipMemcpyDeviceToHost, cap_stream));
                 HIP_TRY(hipStreamSynchronize(cap_stream));
                 cr->input_done.store(1, std::memory_order_release);
             }
@@ -1937,15 +1876,14 @@ template <typename T> struct PlanT : PlanBase {
         if (int rc = no_split("ssfm_propagate_fixed_capture")) return rc;
         if (int rc = use_device()) return rc;                          // (joins the previous capture run's helper)
         if (int rc = lane_health()) return rc;
-        for (int64_t s = 0; s < nsteps; ++s)
-            if (!(h[s] > (T)0) || !std::isfinite((double)h[s]))
-                return fail(SSFM_ERR_INVALID, "ssfm_propagate_fixed_capture: step %lld is %g km (must be finite and > 0)", (long long)s, (double)h[s]);
-        const int nl = lanes_active;
-        // the capture's own resources, made on first use (the copy stream: normal priority -- the plan's high-priority class keeps its queues for the lanes)
-        if (!cap_stream) {
-            HIP_TRY(hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&cap_ev_in, hipEventDisableTiming));
+        {
+            const Schedule<T> sch(h, nsteps, kMaxTables);
+            if (!sch.valid())
+                return fail(SSFM_ERR_INVALID, "ssfm_propagate_fixed_capture: step %lld is %g km (must be finite and > 0)", (long long)sch.first_bad, (double)h[sch.first_bad]);
         }
+        const int nl = lanes_active;
+        // the capture's own resources, made on first use
+        if (int rc = ensure_cap_stream()) return rc;
         const size_t fb = sizeof(cx<T>) * (size_t)n * batch;
         const int64_t nsnap = capture_count(nsteps, every);
         int64_t per_block = 1, nflush = 0;
@@ -1959,8 +1897,8 @@ template <typename T> struct PlanT : PlanBase {
             const size_t bb = fb * (size_t)per_block;
             nblocks = (int)std::min<int64_t>(nflush, std::max<int64_t>(2, std::min<int64_t>(kCapBlocksMax, (int64_t)((size_t(1) << 30) / bb))));
             if (cap_block_bytes != bb || cap_nblocks < nblocks) {
-                (void)hipFree(cap_blocks); cap_blocks = nullptr; cap_block_bytes = 0; cap_nblocks = 0;
-                HIP_TRY(hipMalloc(&cap_blocks, bb * (size_t)nblocks));
+                cap_blocks.free(); cap_block_bytes = 0; cap_nblocks = 0;           // (another block size as well: the ring is made anew)
+                HIP_TRY(cap_blocks.reserve(bb * (size_t)nblocks));
                 cap_block_bytes = bb; cap_nblocks = nblocks;
             }
         }
@@ -1968,20 +1906,16 @@ template <typename T> struct PlanT : PlanBase {
         const int per_row = (N2 / cols_per_tile<T>()) * ((N1 * cols_per_tile<T>() / E + 63) / 64);
         const size_t step_doubles = (size_t)batch * per_row * 2, raw_b = sizeof(double) * step_doubles * (size_t)(nsteps + 1);
         const size_t red_b = sizeof(double) * 2 * (size_t)batch * (size_t)(nsteps + 1);
-        if (scalars_host && cap_scal_bytes < raw_b + red_b) {
-            (void)hipFree(cap_scal); cap_scal = nullptr; cap_scal_bytes = 0;
-            HIP_TRY(hipMalloc(&cap_scal, raw_b + red_b));
-            cap_scal_bytes = raw_b + red_b;
-        }
+        if (scalars_host) if (int rc = grow(cap_scal, raw_b + red_b)) return rc;
         // an event per lane and flush (an event that is recorded again before its waiter has looked at it would tie a transfer to a LATER END)
         for (int g = 0; g < nl; ++g)
             while ((int64_t)cap_ev_ends[g].size() < nflush) {
-                hipEvent_t e;
-                HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                cap_ev_ends[g].push_back(e);
+                Event e;
+                HIP_TRY(hipEventCreateWithFlags(e.out(), hipEventDisableTiming));
+                cap_ev_ends[g].push_back(std::move(e));
             }
         CapRun& cr = cap_cr;
-        cr.every = fields_host ? every : 0; cr.host = static_cast<char*>(fields_host); cr.scalars_host = scalars_host; cr.scal = scalars_host ? cap_scal : nullptr;
+        cr.every = fields_host ? every : 0; cr.host = static_cast<char*>(fields_host); cr.scalars_host = scalars_host; cr.scal = scalars_host ? cap_scal.get() : nullptr;
         cr.step_doubles = step_doubles; cr.per_row = per_row; cr.fb = fb; cr.per_block = per_block; cr.nsnap = nsnap; cr.nflush = nflush; cr.nsteps = nsteps;
         cr.nblocks = nblocks; cr.nlanes = nl;
         for (auto& e : cr.ends_done) e.store(0);
@@ -1990,11 +1924,7 @@ template <typename T> struct PlanT : PlanBase {
             // the input is in F once everything queued on the plan's stream so far is through.  The plans whose engine transforms F in place (Y == F:
             // complex128 and the complex64 plans outside the unit layout) overwrite it with their first launch: they keep a copy, made on the plan's stream
             if (in_place()) {
-                if (cap_in_bytes < fb) {
-                    (void)hipFree(cap_in); cap_in = nullptr; cap_in_bytes = 0;
-                    HIP_TRY(hipMalloc(&cap_in, fb));
-                    cap_in_bytes = fb;
-                }
+                if (int rc = grow(cap_in, fb)) return rc;
                 HIP_TRY(hipMemcpyAsync(cap_in, F, fb, hipMemcpyDeviceToDevice, stream));
             }
             HIP_TRY(hipEventRecord(cap_ev_in, stream));
@@ -2054,7 +1984,7 @@ template <typename T> struct PlanT : PlanBase {
         int half_slots = 0;
         int chunk_no = 0;
     } acap;
-    hipEvent_t acap_ev[2] = {nullptr, nullptr};      // behind the transfers of the chunk that used half 0 / 1 of the ring (the host waits for it before that half is written again)
+    Event acap_ev[2];      // behind the transfers of the chunk that used half 0 / 1 of the ring (the host waits for it before that half is written again)
     bool acap_wants(int64_t after) {
         if (!acap.on) return false;
         if (acap.every > 0) return after % acap.every == 0;
@@ -2083,15 +2013,12 @@ template <typename T> struct PlanT : PlanBase {
         acap.half_slots = half;
         const size_t need = fb * (size_t)half * 2;
         if (cap_block_bytes * (size_t)cap_nblocks < need) {
-            (void)hipFree(cap_blocks); cap_blocks = nullptr; cap_block_bytes = 0; cap_nblocks = 0;
-            HIP_TRY(hipMalloc(&cap_blocks, need));
+            cap_blocks.free(); cap_block_bytes = 0; cap_nblocks = 0;
+            HIP_TRY(cap_blocks.reserve(need));
             cap_block_bytes = need; cap_nblocks = 1;
         }
-        if (!cap_stream) {
-            HIP_TRY(hipStreamCreateWithFlags(&cap_stream, hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&cap_ev_in, hipEventDisableTiming));
-        }
-        for (auto& e : acap_ev) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        if (int rc = ensure_cap_stream()) return rc;
+        for (auto& e : acap_ev) if (!e) HIP_TRY(hipEventCreateWithFlags(e.out(), hipEventDisableTiming));
         if (ar.deferred) {            // (a small plan: the capture needs the launch-per-pass engine)
             const AdaptRun keep = ar;
             if (int rc = adaptive_begin_chunked(keep.gamma, keep.length, keep.phi_max, keep.single_step, keep.max_steps, 0)) return rc;
@@ -2104,11 +2031,7 @@ template <typename T> struct PlanT : PlanBase {
         if (max_steps < 1 || max_steps > (1ll << 30)) return fail(SSFM_ERR_INVALID, "ssfm_propagate_adaptive: max_steps=%lld", (long long)max_steps);
         if (int rc = use_device()) return rc;
         const T gamma = (T)gamma_d;
-        if (zlog_cap < max_steps + 1) {
-            (void)hipFree(zlog); zlog = nullptr; zlog_cap = 0;
-            HIP_TRY(hipMalloc(&zlog, sizeof(T) * (max_steps + 1)));
-            zlog_cap = max_steps + 1;
-        }
+        if (int rc = ensure_zlog(max_steps)) return rc;
         last_launches = 0;
         last_fell_back = 0;
         last_engine = SSFM_ENGINE_NONE;
@@ -2140,11 +2063,8 @@ template <typename T> struct PlanT : PlanBase {
     // what the host reads back during an adaptive run (the step state, the give-up word) lands in page-locked memory: a transfer of a few bytes into
     // pageable memory goes through the runtime's staging path (measured per look at the state: profiles/r05_adaptive_looks.txt)
     struct AdaptLook { StepState<T> now; unsigned gave_up; unsigned pad[3]; };
-    AdaptLook* adapt_look = nullptr;
-    int ensure_adapt_look() {
-        if (!adapt_look) HIP_TRY(hipHostMalloc(&adapt_look, sizeof(AdaptLook), hipHostMallocDefault));
-        return SSFM_OK;
-    }
+    PinnedBuffer<AdaptLook> adapt_look;
+    int ensure_adapt_look() { HIP_TRY(adapt_look.reserve(sizeof(AdaptLook))); return SSFM_OK; }
     int upload_adapt_state(T gamma, T length, T phi_max, int max_steps) {
         std::memset(&adapt_host, 0, sizeof(adapt_host));
         adapt_host.length = length;
@@ -2171,7 +2091,7 @@ template <typename T> struct PlanT : PlanBase {
         // the first step size comes back at once: it tells how many steps to queue before the first look at the state
         // (a run of a few dozen steps is then two or three chunks, not five: every look is a 25 us stall)
         if (int rc = ensure_adapt_look()) return rc;
-        HIP_TRY(hipMemcpyAsync(&adapt_look->now, reinterpret_cast<const char*>(st) + offsetof(AdaptState<T>, cur), sizeof(StepState<T>), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(&adapt_look->now, reinterpret_cast<const char*>(st.get()) + offsetof(AdaptState<T>, cur), sizeof(StepState<T>), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
         const StepState<T> first = adapt_look->now;
         ar = AdaptRun();
@@ -2196,11 +2116,7 @@ template <typename T> struct PlanT : PlanBase {
         if (col_blocks > kAdaptSlots && (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || col_blocks > 2ll * cus || col_blocks % 64 != 0))
             fused_max = kAdaptSlots;                              // (the whole grid must be resident at once: two workgroups per CU)
         ar.fused = fused_ok && !capture && (N1 == 128 || N1 == 256) && col_blocks <= fused_max && !is_split();
-        if (ar.fused) {
-            const size_t fb = sizeof(cx<T>) * n * batch;
-            if (!fused_backup) HIP_TRY(hipMalloc(&fused_backup, fb));
-            HIP_TRY(hipMemcpyAsync(fused_backup, F, fb, hipMemcpyDeviceToDevice, stream));
-        }
+        if (ar.fused) if (int rc = backup_field()) return rc;
         // (Two engines that drove the polarisations of an adaptive run on two streams, a lane's kernel waiting INSIDE the launch for the other lane's
         // maxima, were built in round 3 and removed in round 4: both lost their A/B -- 36-38 and 28.9-29.7 against 32-33 and 29.6-31.1 us per step at
         // 2^20 x 2, profiles/r03_adaptive_two_lanes.txt, r03_adaptive_fused_large.txt -- and both stall until their patience runs out whenever the
@@ -2223,18 +2139,13 @@ template <typename T> struct PlanT : PlanBase {
                 if constexpr (sizeof(T) == 4) {
                     // the whole run in one launch on one XCD (k_medium_adapt); the input is kept for the case that its workgroups do not all get to run
                     const size_t fb = sizeof(cx<T>) * n * batch;
-                    if (!fused_backup) HIP_TRY(hipMalloc(&fused_backup, fb));
-                    HIP_TRY(hipMemcpyAsync(fused_backup, F, fb, hipMemcpyDeviceToDevice, stream));
+                    if (int rc = backup_field()) return rc;
                     if (int rc = upload_adapt_state(keep.gamma, keep.length, keep.phi_max, keep.max_steps)) return rc;
                     hipLaunchKernelGGL(k_absmax<T>, dim3(1024), dim3(256), 0, stream, (const cx<T>*)F, (long long)n * batch, st);
                     hipLaunchKernelGGL(k_step_control<T>, dim3(1), dim3(64), 0, stream, st, zlog, 0, 0, 0);
                     last_launches += 2;
-                    if (!medium_st) {
-                        HIP_TRY(hipMalloc(&medium_st, sizeof(unsigned long long) * 2 * (kBarShards + kBarWords + 2)));
-                        HIP_TRY(hipHostMalloc(&medium_err_host, 2 * sizeof(unsigned)));
-                        medium_err_host[0] = medium_err_host[1] = 0u;
-                    }
-                    HIP_TRY(hipMemsetAsync(medium_st, 0, sizeof(unsigned long long) * (kBarShards + kBarWords + 2), stream));
+                    if (int rc = ensure_medium_state()) return rc;
+                    HIP_TRY(hipMemsetAsync(medium_st, 0, sizeof(unsigned long long) * kSet, stream));
                     if (int rc = pick_xcc()) return rc;
                     MediumAdaptArgs<T> ma;
                     ma.F = F; ma.Y = Y; ma.P = P; ma.twA = twA; ma.twB = twB; ma.tw1 = tw1; ma.tw2 = tw2; ma.D = dperm; ma.st = st; ma.zlog = zlog;
@@ -2245,8 +2156,8 @@ template <typename T> struct PlanT : PlanBase {
                     HIP_TRY(launch_medium_adapt(N1, N2, (int)ma.nblk, medium_xccs, stream, ma));
                     unsigned gave_up = 0, gave_up2 = 0;
                     HIP_TRY(hipMemcpyAsync(&gave_up, ma.error, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-                    HIP_TRY(hipMemcpyAsync(&gave_up2, reinterpret_cast<const char*>(st) + offsetof(AdaptState<T>, error), sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-                    HIP_TRY(hipMemcpyAsync(&ar.now, reinterpret_cast<const char*>(st) + offsetof(AdaptState<T>, cur), sizeof(ar.now), hipMemcpyDeviceToHost, stream));
+                    HIP_TRY(hipMemcpyAsync(&gave_up2, reinterpret_cast<const char*>(st.get()) + offsetof(AdaptState<T>, error), sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+                    HIP_TRY(hipMemcpyAsync(&ar.now, reinterpret_cast<const char*>(st.get()) + offsetof(AdaptState<T>, cur), sizeof(ar.now), hipMemcpyDeviceToHost, stream));
                     HIP_TRY(hipStreamSynchronize(stream));
                     if (!gave_up && !gave_up2) {
                         ar.deferred = false;
@@ -2271,7 +2182,7 @@ template <typename T> struct PlanT : PlanBase {
                 sa.F = F; sa.D = dsmall; sa.tw = tw_small; sa.st = st; sa.zlog = zlog; sa.gamma = keep.gamma; sa.inv_n = inv_n(); sa.single_step = keep.single_step;
                 ++last_launches;
                 HIP_TRY(launch_small_adapt<T>((int)n, batch, stream, sa));
-                HIP_TRY(hipMemcpyAsync(&ar.now, reinterpret_cast<const char*>(st) + offsetof(AdaptState<T>, cur), sizeof(ar.now), hipMemcpyDeviceToHost, stream));
+                HIP_TRY(hipMemcpyAsync(&ar.now, reinterpret_cast<const char*>(st.get()) + offsetof(AdaptState<T>, cur), sizeof(ar.now), hipMemcpyDeviceToHost, stream));
                 HIP_TRY(hipStreamSynchronize(stream));
                 ar.deferred = false;
                 last_engine = SSFM_ENGINE_SMALL_ADAPT;
@@ -2338,7 +2249,7 @@ template <typename T> struct PlanT : PlanBase {
                     last_launches += 2;
                 } else
                 if (fly_imag) {           // (half the operator's bytes: 23.7 -> 22.6 us per step at 2^20 x 2, the same bits)
-                    fa.tab = reinterpret_cast<const cx<T>*>(dimag_fly); fa.amp = op_re0;
+                    fa.tab = reinterpret_cast<const cx<T>*>(dimag_fly.get()); fa.amp = op_re0;
                     HIP_TRY((launch_freq<T, FM_FLY_IM>(N2, nrows, stream, fa, Ef_fly)));
                 } else
                 HIP_TRY((launch_freq<T, FM_FLY>(N2, nrows, stream, fa, Ef_fly)));
@@ -2363,9 +2274,9 @@ template <typename T> struct PlanT : PlanBase {
             }
             const int before = ar.now.steps;
             adapt_look->gave_up = 0u;
-            HIP_TRY(hipMemcpyAsync(&adapt_look->now, reinterpret_cast<const char*>(st) + offsetof(AdaptState<T>, cur) + sizeof(StepState<T>) * (ar.step & 1),
+            HIP_TRY(hipMemcpyAsync(&adapt_look->now, reinterpret_cast<const char*>(st.get()) + offsetof(AdaptState<T>, cur) + sizeof(StepState<T>) * (ar.step & 1),
                                    sizeof(StepState<T>), hipMemcpyDeviceToHost, stream));
-            if (ar.fused) HIP_TRY(hipMemcpyAsync(&adapt_look->gave_up, reinterpret_cast<const char*>(st) + offsetof(AdaptState<T>, error), sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+            if (ar.fused) HIP_TRY(hipMemcpyAsync(&adapt_look->gave_up, reinterpret_cast<const char*>(st.get()) + offsetof(AdaptState<T>, error), sizeof(unsigned), hipMemcpyDeviceToHost, stream));
             HIP_TRY(hipStreamSynchronize(stream));
             ar.now = adapt_look->now;
             const unsigned gave_up = adapt_look->gave_up;
@@ -2447,7 +2358,7 @@ template <typename T> struct PlanT : PlanBase {
     int apply_transfer(const void* H_host) {
         if (int rc = use_device()) return rc;
         const int nrows = N1 * batch;
-        if (!scratch) HIP_TRY(hipMalloc(&scratch, sizeof(cx<T>) * n * batch));
+        if (int rc = ensure_scratch()) return rc;
         cx<T>* hperm = scratch;   // n entries are enough (a split plan: n_full <= n * batch)
         // dnat is a staging buffer: the propagator's own D~ must be re-set after a DM call
         HIP_TRY(hipMemcpyAsync(dnat, H_host, sizeof(cx<T>) * n_full, hipMemcpyHostToDevice, stream));
@@ -2477,7 +2388,7 @@ template <typename T> struct PlanT : PlanBase {
     int apply_dispersion(double dt_s, double D_s2, void* H_out) {
         if (int rc = use_device()) return rc;
         const int nrows = N1 * batch;
-        if (!scratch) HIP_TRY(hipMalloc(&scratch, sizeof(cx<T>) * n * batch));
+        if (int rc = ensure_scratch()) return rc;
         cx<T>* hperm = scratch;
         cx<T>* hnat = nullptr;
         if (H_out) {                       // dnat doubles as staging for the natural-order H
@@ -2516,7 +2427,7 @@ template <typename T> struct PlanT : PlanBase {
         if (slot < 0 || slot > 1) return fail(SSFM_ERR_INVALID, "ssfm_transfer_table: slot %d", slot);
         if (int rc = no_split("ssfm_transfer_table")) return rc;
         if (int rc = use_device()) return rc;
-        if (!xfer_tab[slot]) HIP_TRY(hipMalloc(&xfer_tab[slot], sizeof(cx<T>) * n));
+        if (int rc = ensure_xfer(slot)) return rc;
         HIP_TRY(hipMemcpyAsync(dnat, H_host, sizeof(cx<T>) * n, hipMemcpyHostToDevice, stream));      // dnat = staging
         drop_operator();
         tags[1 + slot] = 0;
@@ -2693,20 +2604,18 @@ template <typename T> struct PlanT : PlanBase {
         if (int rc = no_split("chirp-z")) return rc;
         if (!small || !tw_small || n > 4096) return fail(SSFM_ERR_UNSUPPORTED, "ssfm_chirp_small: a plan of 256 ... 4096 samples is needed");
         if (!A || !chirp || !Dt || !hs || nn < 2 || 2 * nn - 1 > n || nsteps < 1 || nsteps > 0x7fffffff) return fail(SSFM_ERR_INVALID, "ssfm_chirp_small: bad arguments");
-        for (int64_t s = 0; s < nsteps; ++s)
-            if (!(hs[s] > 0) || !std::isfinite(hs[s])) return fail(SSFM_ERR_INVALID, "ssfm_chirp_small: step %lld is %g km (must be finite and > 0)", (long long)s, hs[s]);
+        {
+            const Schedule<double> sch(hs, nsteps, kMaxTables);           // (the kernel takes the sizes as float64, whatever the plan's precision)
+            if (!sch.valid()) return fail(SSFM_ERR_INVALID, "ssfm_chirp_small: step %lld is %g km (must be finite and > 0)", (long long)sch.first_bad, hs[sch.first_bad]);
+        }
         if (int rc = use_device()) return rc;
         const size_t need = sizeof(double) * (size_t)nsteps;
-        if (d_hs_cap < need) {
-            (void)hipFree(d_hs); d_hs = nullptr; d_hs_cap = 0;
-            HIP_TRY(hipMalloc(&d_hs, need + need / 2));
-            d_hs_cap = need + need / 2;
-        }
+        if (int rc = grow(d_hs, need, need / 2)) return rc;
         HIP_TRY(hipStreamSynchronize(stream));
         HIP_TRY(hipMemcpyAsync(d_hs, hs, need, hipMemcpyHostToDevice, stream));
         HIP_TRY(hipStreamSynchronize(stream));             // (hs is the caller's)
         SmallChirpArgs<T> a;
-        a.A = static_cast<cx<T>*>(A); a.chirp = static_cast<const cx<T>*>(chirp); a.Dt = static_cast<const cx<T>*>(Dt); a.hs = reinterpret_cast<const double*>(d_hs);
+        a.A = static_cast<cx<T>*>(A); a.chirp = static_cast<const cx<T>*>(chirp); a.Dt = static_cast<const cx<T>*>(Dt); a.hs = reinterpret_cast<const double*>(d_hs.get());
         if (int rc = chirp_line_table(&a.tw)) return rc;
         a.gamma = (T)gamma; a.n = (int)nn; a.nsteps = (int)nsteps;
         last_launches = 1;
@@ -2717,11 +2626,11 @@ template <typename T> struct PlanT : PlanBase {
     // ... and the adaptive run (k_small_chirp_adapt): the rows' workgroups exchange their maxima through memory every step, so all of them must be
     // resident at once (at most kChirpAdaptRows rows).  Synchronous: the z log and the step count come back.
     int chirp_line_table(const cx<T>** tw) {
-        *tw = tw_small;
+        *tw = tw_small.get();
         if (chirp_points<T>((int)n) == small_points<T>((int)n)) return SSFM_OK;
         if (!tw_chirp)
             if (int rc = make_line_table(&tw_chirp, (int)n, chirp_points<T>((int)n))) return rc;
-        *tw = tw_chirp;
+        *tw = tw_chirp.get();
         return SSFM_OK;
     }
     static constexpr int kChirpAdaptRows = 16;
@@ -2733,13 +2642,8 @@ template <typename T> struct PlanT : PlanBase {
             return fail(SSFM_ERR_INVALID, "ssfm_chirp_small_adapt: bad arguments");
         if (int rc = use_device()) return rc;
         const size_t words = 2 * (size_t)batch * 2, need = sizeof(double) * (size_t)(max_steps + 1) + 8 * words + 16;
-        if (d_hs_cap < need) {
-            HIP_TRY(hipStreamSynchronize(stream));
-            (void)hipFree(d_hs); d_hs = nullptr; d_hs_cap = 0;
-            HIP_TRY(hipMalloc(&d_hs, need + need / 2));
-            d_hs_cap = need + need / 2;
-        }
-        unsigned char* base = reinterpret_cast<unsigned char*>(d_hs);
+        if (int rc = grow(d_hs, need, need / 2)) return rc;
+        unsigned char* base = reinterpret_cast<unsigned char*>(d_hs.get());
         SmallChirpAdaptArgs<T> a;
         a.A = static_cast<cx<T>*>(A); a.chirp = static_cast<const cx<T>*>(chirp); a.Dt = static_cast<const cx<T>*>(Dt);
         if (int rc = chirp_line_table(&a.tw)) return rc;
@@ -2795,8 +2699,8 @@ template <typename T> struct PlanT : PlanBase {
             // the forward one's, and both are symmetric on the line: H1 = conj(H0).
             tags[1] = tags[2] = 0;
             for (int slot = 0; slot < 2; ++slot)
-                if (!xfer_tab[slot]) HIP_TRY(hipMalloc(&xfer_tab[slot], sizeof(cx<T>) * n));
-            if (!scratch) HIP_TRY(hipMalloc(&scratch, sizeof(cx<T>) * n * batch));
+                if (int rc = ensure_xfer(slot)) return rc;
+            if (int rc = ensure_scratch()) return rc;
             std::unique_ptr<PlanT<double>> wide(new (std::nothrow) PlanT<double>());
             if (!wide) return fail(SSFM_ERR_INVALID, "out of host memory");
             wide->precision = SSFM_C128;
@@ -2825,15 +2729,12 @@ template <typename T> struct PlanT : PlanBase {
         if constexpr (sizeof(T) != 4) { (void)A_; (void)chirp_; (void)Dt_; (void)nn; (void)gamma; (void)hs; (void)nsteps; return fail(SSFM_ERR_UNSUPPORTED, "ssfm_chirp_medium: complex64 plans only"); }
         else {
         if (!A_ || !chirp_ || !Dt_ || !hs || nsteps < 1 || nsteps > 0x7fffffff) return fail(SSFM_ERR_INVALID, "ssfm_chirp_medium: bad arguments");
-        std::vector<T> hf((size_t)nsteps), distinct;
-        for (int64_t s = 0; s < nsteps; ++s) {
-            if (!(hs[s] > 0) || !std::isfinite(hs[s])) return fail(SSFM_ERR_INVALID, "ssfm_chirp_medium: step %lld is %g km (must be finite and > 0)", (long long)s, hs[s]);
-            hf[(size_t)s] = (T)hs[s];
-            bool seen = false;
-            for (const T d : distinct) seen = seen || std::memcmp(&d, &hf[(size_t)s], sizeof(T)) == 0;
-            if (!seen) distinct.push_back(hf[(size_t)s]);
-            if (distinct.size() > (size_t)kMaxTables) return fail(SSFM_ERR_UNSUPPORTED, "ssfm_chirp_medium: more than %d distinct step sizes", kMaxTables);
-        }
+        // (the sizes are narrowed first: two float64 sizes that round to one float32 size share a table.  Too many sizes among the steps ahead of a bad one is
+        // what the caller hears of, as when the steps were looked at one by one)
+        const Schedule<T> sch(hs, nsteps, kMaxTables);
+        if (!sch.fits_tables()) return fail(SSFM_ERR_UNSUPPORTED, "ssfm_chirp_medium: more than %d distinct step sizes", kMaxTables);
+        if (!sch.valid()) return fail(SSFM_ERR_INVALID, "ssfm_chirp_medium: step %lld is %g km (must be finite and > 0)", (long long)sch.first_bad, hs[sch.first_bad]);
+        const std::vector<T>& distinct = sch.distinct;
         last_launches = 0;
         if (int rc = chirp_medium_tables(nn)) return rc;
         const long long blocks = (long long)(N2 / cols_per_tile<T>()) * batch;
@@ -2850,33 +2751,12 @@ template <typename T> struct PlanT : PlanBase {
             a.mul[i] = mulbase + i * (size_t)n;
             ++last_launches;
         }
-        const size_t hb = sizeof(T) * (size_t)nsteps, need = hb + (size_t)nsteps;
-        if (d_hs_cap < need) {
-            HIP_TRY(hipStreamSynchronize(stream));
-            (void)hipFree(d_hs); d_hs = nullptr; d_hs_cap = 0;
-            HIP_TRY(hipMalloc(&d_hs, need + need / 2));
-            d_hs_cap = need + need / 2;
-        }
-        HIP_TRY(hipStreamSynchronize(stream));             // the staging vector may still feed the previous run's copy
-        h_sched.resize(need);
-        std::memcpy(h_sched.data(), hf.data(), hb);
-        for (int64_t s = 0; s < nsteps; ++s) {
-            unsigned char w = 0;
-            for (size_t i = 0; i < distinct.size(); ++i)
-                if (std::memcmp(&distinct[i], &hf[(size_t)s], sizeof(T)) == 0) w = (unsigned char)i;
-            h_sched[hb + (size_t)s] = w;
-        }
-        HIP_TRY(hipMemcpyAsync(d_hs, h_sched.data(), need, hipMemcpyHostToDevice, stream));
-        if (!medium_st) {
-            HIP_TRY(hipMalloc(&medium_st, sizeof(unsigned long long) * 2 * (kBarShards + kBarWords + 2)));
-            HIP_TRY(hipHostMalloc(&medium_err_host, 2 * sizeof(unsigned)));
-            medium_err_host[0] = medium_err_host[1] = 0u;
-        }
-        constexpr size_t kSet = kBarShards + kBarWords + 2;
+        if (int rc = upload_schedule(sch)) return rc;
+        if (int rc = ensure_medium_state()) return rc;
         HIP_TRY(hipMemsetAsync(medium_st, 0, sizeof(unsigned long long) * 2 * kSet, stream));
         a.F = F; a.Y = Y; a.P = P; a.twA = twA; a.twB = twB; a.tw1 = tw1; a.tw2 = tw2;
         a.H[0] = xfer_tab[0]; a.H[1] = xfer_tab[1];
-        a.hs = d_hs; a.which = reinterpret_cast<const unsigned char*>(d_hs) + hb;
+        a.hs = d_hs; a.which = d_which(sch);
         a.bar = medium_st; a.error = reinterpret_cast<unsigned*>(medium_st + kBarShards + kBarWords); a.patience = medium_patience;
         a.xcc = (unsigned)medium_xcc;
         a.gamma = (T)gamma; a.n = (int)nn; a.nsteps = (int)nsteps; a.rows = batch; a.Qf = N2 / Ef;
@@ -2915,21 +2795,12 @@ template <typename T> struct PlanT : PlanBase {
         if (int rc = chirp_medium_tables(nn)) return rc;
         cx<T>* A = static_cast<cx<T>*>(A_);
         const cx<T>* chirp = static_cast<const cx<T>*>(chirp_);
-        if (zlog_cap < max_steps + 1) {
-            HIP_TRY(hipStreamSynchronize(stream));
-            (void)hipFree(zlog); zlog = nullptr; zlog_cap = 0;
-            HIP_TRY(hipMalloc(&zlog, sizeof(T) * (max_steps + 1)));
-            zlog_cap = max_steps + 1;
-        }
+        if (int rc = ensure_zlog(max_steps)) return rc;
         if (int rc = upload_adapt_state((T)gamma_d, (T)length, (T)phi_max, (int)max_steps)) return rc;
         hipLaunchKernelGGL(k_absmax<T>, dim3(256), dim3(256), 0, stream, (const cx<T>*)A, (long long)nn * batch, st);
         hipLaunchKernelGGL(k_step_control<T>, dim3(1), dim3(64), 0, stream, st, zlog, 0, 0, 0);
-        if (!medium_st) {
-            HIP_TRY(hipMalloc(&medium_st, sizeof(unsigned long long) * 2 * (kBarShards + kBarWords + 2)));
-            HIP_TRY(hipHostMalloc(&medium_err_host, 2 * sizeof(unsigned)));
-            medium_err_host[0] = medium_err_host[1] = 0u;
-        }
-        HIP_TRY(hipMemsetAsync(medium_st, 0, sizeof(unsigned long long) * (kBarShards + kBarWords + 2), stream));
+        if (int rc = ensure_medium_state()) return rc;
+        HIP_TRY(hipMemsetAsync(medium_st, 0, sizeof(unsigned long long) * kSet, stream));
         MediumChirpAdaptArgs<T> a;
         std::memset(&a, 0, sizeof(a));
         a.F = F; a.Y = Y; a.P = P; a.twA = twA; a.twB = twB; a.tw1 = tw1; a.tw2 = tw2;
@@ -2945,8 +2816,8 @@ template <typename T> struct PlanT : PlanBase {
         unsigned gave_up[2] = {0u, 0u};
         StepState<T> fin = {};
         HIP_TRY(hipMemcpyAsync(&gave_up[0], a.error, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipMemcpyAsync(&gave_up[1], reinterpret_cast<const char*>(st) + offsetof(AdaptState<T>, error), sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipMemcpyAsync(&fin, reinterpret_cast<const char*>(st) + offsetof(AdaptState<T>, cur), sizeof(fin), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(&gave_up[1], reinterpret_cast<const char*>(st.get()) + offsetof(AdaptState<T>, error), sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(&fin, reinterpret_cast<const char*>(st.get()) + offsetof(AdaptState<T>, cur), sizeof(fin), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
         last_launches += 5;
         last_engine = SSFM_ENGINE_CHIRP_MEDIUM_ADAPT;
@@ -2975,7 +2846,7 @@ template <typename T> struct PlanT : PlanBase {
         if (int rc = no_split("ssfm_table_from_field")) return rc;
         if (slot < 0 || slot > 1) return fail(SSFM_ERR_INVALID, "ssfm_table_from_field: slot %d", slot);
         if (int rc = use_device()) return rc;
-        if (!xfer_tab[slot]) HIP_TRY(hipMalloc(&xfer_tab[slot], sizeof(cx<T>) * n));
+        if (int rc = ensure_xfer(slot)) return rc;
         tags[1 + slot] = 0;
         if (int rc = field_spectrum()) return rc;
         hipLaunchKernelGGL((k_make_freq_table<T, 1>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
@@ -2986,7 +2857,7 @@ template <typename T> struct PlanT : PlanBase {
     }
     // scratch <- fft(field) of every row, natural frequency order (the field is consumed)
     int field_spectrum() {
-        if (!scratch) HIP_TRY(hipMalloc(&scratch, sizeof(cx<T>) * n * batch));
+        if (int rc = ensure_scratch()) return rc;
         HIP_TRY((launch_time<T, TM_BEGIN>(N1, batch, stream, targs(0, 0, 0, nullptr), E)));
         HIP_TRY((launch_freq<T, FM_FWD_ONLY>(N2, N1 * batch, stream, fargs(dperm, 0, nullptr), Ef)));
         const long long total = (long long)n * batch;
@@ -3010,7 +2881,7 @@ template <typename T> struct PlanT : PlanBase {
         if (int rc = no_split("ssfm_debug")) return rc;
         if (int rc = use_device()) return rc;
         const int nrows = N1 * batch;
-        if (!scratch) HIP_TRY(hipMalloc(&scratch, sizeof(cx<T>) * n * batch));
+        if (int rc = ensure_scratch()) return rc;
         HIP_TRY((launch_time<T, TM_BEGIN>(N1, batch, stream, targs(0, 0, 0, nullptr), E)));
         HIP_TRY((launch_freq<T, FM_FWD_ONLY>(N2, nrows, stream, fargs(dperm, 0, nullptr), Ef)));
         const long long total = (long long)n * batch;

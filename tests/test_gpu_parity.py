@@ -2483,6 +2483,111 @@ def test_repeated_calls_do_not_leak_device_memory():
     assert free0 - free1 < 256 * 2 ** 20, (free0, free1, pooled0, pooled1)
 
 
+def test_plan_cycles_leak_nothing_and_change_nothing(monkeypatch):
+    """Plans made, run and destroyed over and over: every resource a plan makes on first use -- the schedule on the device, operator tables, the one-launch
+    engines' barrier words and pinned error words, the backup of the field, the z log, the capture's ring, input copy, scalar log, stream, events and
+    helper thread, the scratch field, the transfer slots, the chirp line's tables and workspaces -- is made and given back in every cycle.  After three
+    warm-up cycles, twenty more: free device memory does not drift, and every run's output, engine, fall-back flag and launch count are the first
+    cycle's, bit for bit and count for count.
+
+    The bound on the drift is the allocator's granularity and nothing else: the runtime hands device memory out in 2 MiB pieces.  Measured before the
+    plan's members owned their buffers: a drift of 0 bytes over the twenty cycles; the bound is 2 MiB = 2097152 bytes above that."""
+    import gc
+    for k in ("SSFM_MEDIUM", "SSFM_MEDIUM_ADAPT", "SSFM_MEDIUM_SPLIT", "SSFM_ADAPT_FUSED", "SSFM_SMALL", "SSFM_CHIRP_SMALL", "SSFM_CHIRP_LOOP", "SSFM_FUSED_PATIENCE_TICKS",
+              "SSFM_E", "SSFM_EF", "SSFM_EF_FLY", "SSFM_LANES", "SSFM_FORCE_FLY", "SSFM_PHASE_TABLE"):
+        monkeypatch.delenv(k, raising=False)
+    oa.devices.release_plans()
+    gv(**workloads.BENCH_GV)
+    parent_drift, granularity = 0, 2 << 20
+    field = workloads.qpsk_field(1 << 14, seed=5, power_w=4e-3, n_pol=2).astype(np.complex64)
+    sched = np.array([0.5] * 7 + [0.25], dtype=np.float32)
+    ops = {n: np.asarray(oa.devices.linear_operator(n, gv.dt, 0.2, -21.7, 0.13, _lib.C64), dtype=np.complex64) for n in (1 << 10, 1 << 12, 1 << 13, 1 << 14)}
+    H = np.exp(-np.square(np.fft.fftfreq(1 << 12) * 8.0)).astype(np.complex64)              # an LPF-like transfer function
+    chirps = {n: (_lib.chirp_device(n, False, 0).astype(np.complex64),
+                  _lib.DeviceArray.from_host(np.asarray(oa.devices.linear_operator(n, gv.dt, 0.2, -21.7, 0.13, _lib.C64), dtype=np.complex64), np.complex64, 0))
+              for n in (1001, 5001)}
+    hs64 = np.array([0.5] * 7 + [0.25], dtype=np.float64)
+    op128 = np.asarray(oa.devices.linear_operator(1 << 14, gv.dt, 0.2, -21.7, 0.13, _lib.C128), dtype=np.complex128)
+
+    def on_plan(n, batch, body, prec=_lib.C64):
+        p = _lib.Plan(n, batch, prec)
+        try:
+            out = body(p)
+            info = p.last_run_info()
+            return [np.array(o, copy=True) for o in out], (info["engine"], info["fell_back"], p.last_propagate_ms()[1])
+        finally:
+            p.close()
+
+    def fixed(n, batch):
+        def body(p):
+            p.set_linear_operator(ops[n]); p.set_field(field[:batch, :n]); p.propagate_fixed(1.3, sched)
+            return [p.get_field()]
+        return on_plan(n, batch, body)
+
+    def fixed_capture(p):          # (a complex128 plan transforms its field in place: the capture keeps a copy of the input as well)
+        p.set_linear_operator(op128); p.set_field(field)
+        c = p.propagate_fixed_capture(1.3, hs64, every=2, scalars=True)
+        return [c["steps"], c["fields"], c["power"], c["peak"], p.get_field()]
+
+    def adaptive(p):
+        p.set_linear_operator(ops[1 << 14]); p.set_field(field)
+        steps, z, _ = p.propagate_adaptive(1.3, 4.0, 0.004, False)
+        return [np.int64(steps), z, p.get_field()]
+
+    def adaptive_capture(p):
+        p.set_linear_operator(ops[1 << 14]); p.set_field(field)
+        steps, z, taken, fields = p.propagate_adaptive_capture(1.3, 4.0, 0.004, every=2, capacity=64)
+        return [np.int64(steps), z, taken, fields, p.get_field()]
+
+    def transfers(p):
+        p.set_field(field[:, : 1 << 12])
+        Hd = p.apply_dispersion(gv.dt, 3.4e-23, want_H=True)          # DM: the scratch field
+        a = p.get_field()
+        p.apply_transfer(H)
+        b = p.get_field()
+        p.transfer_table(H, 0); p.transfer_table(np.conj(H), 1)        # the resident slots
+        p.apply_table(0); p.apply_table(1)
+        return [Hd, a, b, p.get_field()]
+
+    def chirp(n):
+        def body(p):
+            A = _lib.DeviceArray.from_host(field[:, :n], np.complex64, 0)
+            assert p.chirp_propagate_c64(A, chirps[n][0], chirps[n][1], 1.3, hs64) is True
+            p.synchronize()                                     # (the small line's fixed-step run is asynchronous, A is not the plan's field)
+            return [A.to_host()]
+        return body
+
+    def cycle():
+        got = [fixed(1 << 10, 1), fixed(1 << 13, 2), on_plan(1 << 14, 2, fixed_capture, _lib.C128), on_plan(1 << 14, 2, adaptive), on_plan(1 << 14, 2, adaptive_capture),
+               on_plan(1 << 12, 2, transfers), on_plan(1 << 11, 2, chirp(1001)), on_plan(1 << 14, 2, chirp(5001))]
+        oa.devices.release_plans()
+        return got
+
+    first = cycle()
+    print("engines of a cycle:", [info for _, info in first])
+    assert [info[0] for _, info in first[:2]] == ["small", "medium"], first[0][1:]             # the engines the sizes were chosen for
+    assert [info[0] for _, info in first[6:]] == ["chirp_small", "chirp_medium"]
+    assert not any(info[1] for _, info in first)
+
+    def same_as_first(got, i):
+        for k, ((outs, info), (outs0, info0)) in enumerate(zip(got, first)):
+            assert info == info0, (i, k, info, info0)
+            assert len(outs) == len(outs0)
+            for a, b in zip(outs, outs0):
+                assert a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes(), (i, k, info)
+
+    for i in range(2):
+        same_as_first(cycle(), i + 1)
+    gc.collect()
+    free0, _, pooled0 = _lib.device_mem_info()
+    for i in range(20):
+        same_as_first(cycle(), i + 3)
+    gc.collect()
+    free1, _, pooled1 = _lib.device_mem_info()
+    print(f"free device memory after the warm-up {free0}, after twenty cycles {free1}: drift {free0 - free1} bytes (pooled {pooled0} -> {pooled1})")
+    assert abs(free0 - free1) <= parent_drift + granularity, (free0, free1, pooled0, pooled1)
+
+
 def test_c_abi_from_plain_c(tmp_path):
     """examples/c_abi_demo.c: the shared library used from C with nothing but include/ssfm_amd.h."""
     import subprocess
