@@ -468,6 +468,21 @@ def axpb_device(a: DeviceArray, alpha: float, beta: float) -> DeviceArray:
     return out
 
 
+def check_every(every) -> int:
+    """``every`` as an int; a stride below 1 is rejected."""
+    every = int(every)
+    if every < 1:
+        raise ValueError(f"every = {every}")
+    return every
+
+
+def every_index(steps: int, every) -> list:
+    """Indices of the snapshots ``every`` keeps of a run of ``steps`` steps: 0 (the input), every ``every``-th step, the last one (None: all of them)."""
+    if every is None:
+        return list(range(steps + 1))
+    return list(range(0, steps, check_every(every))) + [steps]
+
+
 def chirp_device(n: int, conj: bool, device: int = 0) -> DeviceArray:
     """``exp(-i pi m^2 / n)`` (or its conjugate), m < n, complex128, generated on the device."""
     out = DeviceArray((int(n),), np.complex128, device)
@@ -717,10 +732,8 @@ class Plan:
             raise ValueError("the schedule is empty")
         out, cap = {}, Capture(0, None, None)
         if every is not None:
-            every = int(every)
-            if every < 1:
-                raise ValueError(f"every = {every}")
-            idx = list(range(0, hs.size, every)) + [hs.size]
+            every = check_every(every)
+            idx = every_index(hs.size, every)
             out["steps"] = np.asarray(idx, dtype=np.int64)
             # (page-locked up to 8 GiB: the transfers of a strided capture run beside the kernels only into page-locked memory)
             out["fields"] = host_empty((len(idx), self.batch, self.n), self.cdtype, limit=8 << 30)
@@ -774,10 +787,7 @@ class Plan:
                 raise ValueError("`steps` is empty")
             capacity = want.size if capacity is None else int(capacity)
         else:
-            every = int(every)
-            if every < 1:
-                raise ValueError(f"every = {every}")
-            want = None
+            every, want = check_every(every), None
             if capacity is None:
                 raise ValueError("a strided capture of an adaptive run needs a `capacity` (snapshots): the run's length in steps is its own")
         capacity = max(1, int(capacity))
@@ -865,18 +875,17 @@ class Plan:
                         phi_max: float = 0.0, f32: bool = True, max_steps: int = 1 << 20):
         """A whole chirp-z run from C (ssfm_chirp_propagate).  ``hs``: float64 host array of step sizes (fixed step) or None (adaptive);
         returns (steps, z) with z = positions after every step (adaptive) or None (fixed)."""
-        steps = _I64(0)
+        steps, z = _I64(0), None
         if hs is not None:
             hs = np.ascontiguousarray(hs, dtype=np.float64)
             if hs.size == 0:                       # (length 0: the reference's loop does not run, devices.py:1172)
                 return 0, None
-            api.ssfm_chirp_propagate(self._h, self.n, self.batch, A, P, chirp, Dt, A.shape[-1], float(gamma),
-                                     hs.ctypes.data_as(C.POINTER(_D)), hs.size, 0.0, 0.0, 1 if f32 else 0, 1, None, C.byref(steps))
-            return int(steps.value), None
-        z = np.zeros(int(max_steps) + 1, dtype=np.float64)
-        api.ssfm_chirp_propagate(self._h, self.n, self.batch, A, P, chirp, Dt, A.shape[-1], float(gamma),
-                                 None, 0, float(length), float(phi_max), 1 if f32 else 0, int(max_steps), z.ctypes.data_as(C.POINTER(_D)), C.byref(steps))
-        return int(steps.value), z[: int(steps.value) + 1]
+            run = (hs.ctypes.data_as(C.POINTER(_D)), hs.size, 0.0, 0.0, 1 if f32 else 0, 1, None)
+        else:
+            z = np.zeros(int(max_steps) + 1, dtype=np.float64)
+            run = (None, 0, float(length), float(phi_max), 1 if f32 else 0, int(max_steps), z.ctypes.data_as(C.POINTER(_D)))
+        api.ssfm_chirp_propagate(self._h, self.n, self.batch, A, P, chirp, Dt, A.shape[-1], float(gamma), *run, C.byref(steps))
+        return int(steps.value), (None if z is None else z[: int(steps.value) + 1])
 
     def chirp_propagate_c64(self, A: "DeviceArray", chirp: "DeviceArray", Dt: "DeviceArray", gamma: float, hs=None, *, length: float = 0.0, phi_max: float = 0.0,
                             max_steps: int = 1 << 17):
@@ -884,25 +893,21 @@ class Plan:
         workgroup per row up to 4096 points of line, the one-XCD engine above.  ``hs``: float64 host array of step sizes (fixed step; a step of length zero is
         the identity) -> True, or None for the adaptive rule over ``length`` -> (steps, z).  False / None: the plan has no such engine or schedule, or the
         launch's workgroups did not meet -- ``A`` is then as it was."""
-        steps = _I64(0)
+        steps, z = _I64(0), None
         if hs is not None:
             hs = np.ascontiguousarray(hs, dtype=np.float64)
             hs = hs[hs != 0.0]
             if hs.size == 0:
                 return True
-            rc = load().ssfm_chirp_propagate_c64(self._h, A, chirp, Dt, A.shape[-1], float(gamma), hs.ctypes.data_as(C.POINTER(_D)), hs.size,
-                                                 0.0, 0.0, 1, None, C.byref(steps))
-            if rc == 2:
-                return False
-            _check(rc, "ssfm_chirp_propagate_c64")
-            return True
-        z = np.zeros(int(max_steps) + 1, np.float64)
-        rc = load().ssfm_chirp_propagate_c64(self._h, A, chirp, Dt, A.shape[-1], float(gamma), None, 0, float(length), float(phi_max),
-                                             int(max_steps), z.ctypes.data_as(C.POINTER(_D)), C.byref(steps))
+            run = (hs.ctypes.data_as(C.POINTER(_D)), hs.size, 0.0, 0.0, 1, None)
+        else:
+            z = np.zeros(int(max_steps) + 1, np.float64)
+            run = (None, 0, float(length), float(phi_max), int(max_steps), z.ctypes.data_as(C.POINTER(_D)))
+        rc = load().ssfm_chirp_propagate_c64(self._h, A, chirp, Dt, A.shape[-1], float(gamma), *run, C.byref(steps))
         if rc == 2:
-            return None
+            return False if z is None else None
         _check(rc, "ssfm_chirp_propagate_c64")
-        return int(steps.value), z[: int(steps.value) + 1]
+        return True if z is None else (int(steps.value), z[: int(steps.value) + 1])
 
     def debug_fft(self) -> np.ndarray:
         out = host_empty((self.batch, self.n), self.cdtype)

@@ -17,7 +17,7 @@ import threading
 import functools
 import time
 import warnings
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 import numpy as np
 
@@ -292,6 +292,26 @@ def step_schedule(length, h, precision=_lib.C64):
 
 # ------------------------------------------------------------------ chirp-z engine (any length)
 _CHIRPS: "OrderedDict[tuple, tuple]" = OrderedDict()      # (device, n) -> (c, conj c) on the device; content-addressed, never stale
+_CHIRPS32: "OrderedDict[tuple, object]" = OrderedDict()   # (device, n) -> c in complex64, for the one-launch lines
+
+
+def _cached(cache: OrderedDict, key, make):
+    """``cache[key]``, made by ``make()`` when it is not there; a cache keeps its four newest entries."""
+    with _CACHE_LOCK:
+        if key not in cache:
+            cache[key] = make()
+            while len(cache) > 4:
+                cache.pop(next(iter(cache)))
+        return cache[key]
+
+
+def _chirp32(dev: int, n: int) -> "_lib.DeviceArray":
+    return _cached(_CHIRPS32, (dev, n), lambda: _lib.chirp_device(n, False, dev).astype(np.complex64))
+
+
+def _rows(shape):
+    """``(n, batch)`` of a field of ``shape`` ``(n,)`` or ``(batch, n)``."""
+    return shape[-1], (1 if len(shape) == 1 else shape[0])
 
 
 class _ChirpZ:
@@ -306,13 +326,7 @@ class _ChirpZ:
         self.plan = get_plan(M, batch, _lib.C128, dev)
         with self.plan.lock:
             self._ensure_tables()
-        key = (dev, n)
-        with _CACHE_LOCK:
-            if key not in _CHIRPS:
-                _CHIRPS[key] = (_lib.chirp_device(n, False, dev), _lib.chirp_device(n, True, dev))
-                while len(_CHIRPS) > 4:
-                    _CHIRPS.pop(next(iter(_CHIRPS)))
-            self.chirp, self.chirp_conj = _CHIRPS[key]
+        self.chirp, self.chirp_conj = _cached(_CHIRPS, (dev, n), lambda: (_lib.chirp_device(n, False, dev), _lib.chirp_device(n, True, dev)))
 
     def _ensure_tables(self):
         want = _tag("chirp", self.n)
@@ -364,8 +378,7 @@ def _fourier(obj, domain, shift=False):
     dev = default_device()
     raws = [obj._raw("signal")] + ([] if obj._raw("noise") is NULL else [obj._raw("noise")])
     shape = tuple(raws[0].shape)
-    n = shape[-1]
-    rows = 1 if len(shape) == 1 else shape[0]
+    n, rows = _rows(shape)
     _, hi = _lib.supported_log2n(_lib.C128, direct=True)
     if n < 2 or 2 * n - 1 > (1 << hi):
         raise ValueError(f"the device transform takes 2 ... 2^{hi - 1} samples per row, got {n} (there is no CPU fallback)")
@@ -394,27 +407,52 @@ def _fourier(obj, domain, shift=False):
     return _wrap_out(type(obj), outs[0], outs[1] if len(outs) > 1 else NULL, **kw)
 
 
-def _fiber_chirpz(A_dev, shape, dt, length, alpha, beta_2, beta_3, gamma, phi_max, h, return_steps, prec, dev, bar):
+class _Fibre(namedtuple("_Fibre", "length alpha beta_2 beta_3 gamma phi_max h dt prec rt L g single")):
+    """The fibre of one ``FIBER`` call as the caller gave it (``prec``: the plan's precision code) and, worked out once by :meth:`of`, what every engine
+    derives from it in the caller's arithmetic ``rt`` (float32 in complex64 mode: reference devices.py:1137-1161): ``L`` and ``g`` are length and gamma
+    in it, ``single`` says that the adaptive rule (``h`` is None) has nothing to adapt to -- one step of the whole length (reference devices.py:1163-1170)."""
+    __slots__ = ()
+
+    @classmethod
+    def of(cls, length, alpha, beta_2, beta_3, gamma, phi_max, h, dt, prec):
+        rt = _F32 if prec == _lib.C64 else np.float64
+        single = False
+        if h is None:
+            b2, b3 = rt(beta_2), rt(beta_3)
+            single = bool((b2 == 0 and b3 == 0) or rt(gamma) == 0)
+        return cls(length, alpha, beta_2, beta_3, gamma, phi_max, h, dt, prec, rt, rt(length), float(rt(gamma)), single)
+
+    def schedule(self):
+        return step_schedule(self.length, self.h, self.prec)
+
+    def known_run(self):
+        """``(hs float64, zs)`` of a run whose steps are known beforehand -- a fixed ``h``, or one step of the whole length -- and None for one
+        that the adaptive rule steps through."""
+        if self.h is None:
+            return (np.array([float(self.L)]), [self.rt(0), self.L]) if self.single else None
+        hs, z = step_schedule(self.length, self.h, self.prec)
+        return np.asarray(hs, dtype=np.float64), list(z)
+
+    def operator(self, n: int):
+        return linear_operator(n, self.dt, self.alpha, self.beta_2, self.beta_3, self.prec)
+
+
+def _fiber_chirpz(fibre, A_dev, n, batch, return_steps, dev, bar):
     """FIBER for a length that is not a power of two (same semantics as the fused engine: float32 coefficients
     and step arithmetic in complex64 mode, reference devices.py:1137-1161, 1172-1196)."""
-    n = shape[-1]
-    batch = 1 if len(shape) == 1 else shape[0]
-    rt = _F32 if prec == _lib.C64 else np.float64
-    if prec == _lib.C64 and n <= 2048 and not return_steps and bar is None and os.environ.get("SSFM_CHIRP_LOOP", "c") != "python" \
+    if fibre.prec == _lib.C64 and n <= 2048 and not return_steps and bar is None and os.environ.get("SSFM_CHIRP_LOOP", "c") != "python" \
             and os.environ.get("SSFM_CHIRP_SMALL", "1") != "0" and batch <= 16:
-        got = _fiber_chirpz_small_c64(A_dev, shape, dt, length, alpha, beta_2, beta_3, gamma, phi_max, h, dev)
+        got = _fiber_chirpz_small_c64(fibre, A_dev, n, batch, dev)
         if got is not None:
             return got + ("chirp_small_c64",)
-    if prec == _lib.C64 and 2048 < n <= 65536 and not return_steps and bar is None and os.environ.get("SSFM_CHIRP_LOOP", "c") != "python" \
+    if fibre.prec == _lib.C64 and 2048 < n <= 65536 and not return_steps and bar is None and os.environ.get("SSFM_CHIRP_LOOP", "c") != "python" \
             and os.environ.get("SSFM_MEDIUM", "1") != "0":
-        got = _fiber_chirpz_medium_c64(A_dev, shape, dt, length, alpha, beta_2, beta_3, gamma, phi_max, h, dev)
+        got = _fiber_chirpz_medium_c64(fibre, A_dev, n, batch, dev)
         if got is not None:
             return got + ("chirp_medium_c64",)
     with _ChirpZ(n, batch, dev) as eng:
-        return _fiber_chirpz_locked(eng, A_dev, shape, dt, length, alpha, beta_2, beta_3, gamma, phi_max, h, return_steps, prec, dev, bar) + ("chirp_line_c128",)
+        return _fiber_chirpz_locked(eng, fibre, A_dev, n, batch, return_steps, dev, bar) + ("chirp_line_c128",)
 
-
-_CHIRPS32: "OrderedDict[tuple, object]" = OrderedDict()
 
 # Accuracy margin of the one-launch complex64 chirp-z line (2048 < n <= 65536; profiles/r05_chirp_margin.txt).  A step of that line is four
 # padded complex64 transforms of 2-4 x the field's length where the reference's pocketfft makes two of the length itself: measured over 242 random
@@ -428,200 +466,178 @@ _c64_line_has_margin = accuracy.c64_line_has_margin
 _C64_LINE_NO_MARGIN = accuracy.c64_line_window()          # (first, last) step count without margin: (27, 1031)
 
 
-def _fiber_chirpz_small_c64(A_dev, shape, dt, length, alpha, beta_2, beta_3, gamma, phi_max, h, dev):
-    """``precision="complex64"`` at up to 2048 samples that are not a power of two: the whole run in ONE launch on a complex64 line of M >= 2n - 1 <= 4096 points
-    (k_small_chirp / k_small_chirp_adapt instantiated for float; round 4).  The reference itself transforms such a length in single precision (pocketfft's Bluestein,
-    devices.py:1178-1180), so this is its arithmetic class: 2e-6 ... 7e-6 from the float64 solution after 100 steps (profiles/r04_chirpz_c64_error.txt) where the
-    complex128 line of the general path sits at 1e-13 -- and a step takes half the time (one CU does the four line transforms of a step; float64 was its bound).
-    ``precision="complex128"`` keeps the complex128 line.  None: the plan has no such engine, or its rows' workgroups did not meet: the general path runs."""
-    n = shape[-1]
-    batch = 1 if len(shape) == 1 else shape[0]
-    M = 1 << max(8, (2 * n - 2).bit_length())
-    plan = get_plan(M, batch, _lib.C64, dev)
-    L = _F32(length)
-    if not float(L) > 0:
-        A = A_dev if A_dev.dtype == np.complex64 else A_dev.astype(np.complex64)
-        return (A.copy() if A is A_dev else A), [_F32(0)], None
-    with plan.lock:
-        key = (dev, n)
-        with _CACHE_LOCK:
-            if key not in _CHIRPS32:
-                _CHIRPS32[key] = _lib.chirp_device(n, False, dev).astype(np.complex64)
-                while len(_CHIRPS32) > 4:
-                    _CHIRPS32.pop(next(iter(_CHIRPS32)))
-            chirp = _CHIRPS32[key]
-        A = A_dev.astype(np.complex64) if A_dev.dtype != np.complex64 else A_dev.copy()          # the caller's array is never modified
-        A.shape = (batch, n)
-        Dt = _lib.DeviceArray.from_host(np.asarray(linear_operator(n, dt, alpha, beta_2, beta_3, _lib.C64), dtype=np.complex64), np.complex64, dev)
-        g = float(_F32(gamma))
-        if h is None:
-            b2, b3 = _F32(beta_2), _F32(beta_3)
-            if bool((b2 == 0 and b3 == 0) or _F32(gamma) == 0):                  # one step of the whole length (reference devices.py:1163-1170)
-                if not plan.chirp_propagate_c64(A, chirp, Dt, g, np.array([float(L)])):
-                    return None
-                zs = [_F32(0), L]
-            else:
-                zs, z0, max_steps = [_F32(0)], _F32(0), 1 << 17
-                while True:
-                    got = plan.chirp_propagate_c64(A, chirp, Dt, g, None, length=float(_F32(L - z0)), phi_max=float(_F32(phi_max)), max_steps=max_steps)
-                    if got is None:
-                        return None if z0 == 0 else _raise_chirp_midway()
-                    steps, z = got
-                    zs += [_F32(z0 + _F32(v)) for v in z[1:]]
-                    if steps < max_steps or not (zs[-1] < L):
-                        break
-                    z0 = zs[-1]
-        else:
-            hs, z_all = step_schedule(length, h, _lib.C64)
-            if not plan.chirp_propagate_c64(A, chirp, Dt, g, np.asarray(hs, dtype=np.float64)):
-                return None
-            zs = list(z_all)
-        plan.synchronize()
-        return A, zs, None
+def _prepare_c64(fibre, A_dev, n, batch, dev):
+    """What a one-launch complex64 line works on: ``(A, chirp, Dt, g)`` -- the field as a new (batch, n) complex64 array, the line's chirp, the
+    operator on the device, gamma in the caller's arithmetic."""
+    chirp = _chirp32(dev, n)
+    A = A_dev.astype(np.complex64)                          # (a copy when it has the type already: the caller's array is never modified)
+    A.shape = (batch, n)
+    Dt = _lib.DeviceArray.from_host(np.asarray(fibre.operator(n), dtype=np.complex64), np.complex64, dev)
+    return A, chirp, Dt, fibre.g
 
 
-def _fiber_chirpz_medium_c64(A_dev, shape, dt, length, alpha, beta_2, beta_3, gamma, phi_max, h, dev):
-    """``precision="complex64"``, 2048 < n <= 65536 samples that are not a power of two: the whole run in one launch on one XCD on a complex64 line of
-    M >= 2n - 1 points, 2^13 ... 2^17 (k_medium_chirp / k_medium_chirp_adapt: four passes per step instead of five / seven launches; round 4).  The arithmetic
-    class of ``_fiber_chirpz_small_c64``.  None: a plan whose rows do not fit the one-XCD engine (2^17 points in all), more than four step sizes, or a launch
-    whose workgroups did not meet: the general path runs."""
-    n = shape[-1]
-    batch = 1 if len(shape) == 1 else shape[0]
-    M = 1 << (2 * n - 2).bit_length()
-    L = _F32(length)
-    if M * batch > (1 << 17) or not float(L) > 0:
-        return None
-    adaptive = False
-    if h is None:
-        b2, b3 = _F32(beta_2), _F32(beta_3)
-        adaptive = not bool((b2 == 0 and b3 == 0) or _F32(gamma) == 0)
-        hs, zs = np.array([float(L)]), [_F32(0), L]                             # one step of the whole length (reference devices.py:1163-1170)
-        if adaptive and os.environ.get("SSFM_MEDIUM_ADAPT", "1") == "0":
-            return None
-    else:
-        hs, z_all = step_schedule(length, h, _lib.C64)
-        hs, zs = np.asarray(hs, dtype=np.float64), list(z_all)
-    if len(set(hs.tolist())) > 4 or not _c64_line_has_margin(len(hs)):
-        return None
-    plan = get_plan(M, batch, _lib.C64, dev)
-    with plan.lock:
-        key = (dev, n)
-        with _CACHE_LOCK:
-            if key not in _CHIRPS32:
-                _CHIRPS32[key] = _lib.chirp_device(n, False, dev).astype(np.complex64)
-                while len(_CHIRPS32) > 4:
-                    _CHIRPS32.pop(next(iter(_CHIRPS32)))
-            chirp = _CHIRPS32[key]
-        A = A_dev.astype(np.complex64) if A_dev.dtype != np.complex64 else A_dev.copy()          # the caller's array is never modified
-        A.shape = (batch, n)
-        Dt = _lib.DeviceArray.from_host(np.asarray(linear_operator(n, dt, alpha, beta_2, beta_3, _lib.C64), dtype=np.complex64), np.complex64, dev)
-        g = float(_F32(gamma))
-        if not adaptive:
-            if not plan.chirp_propagate_c64(A, chirp, Dt, g, hs):
-                return None
-            return A, zs, None
-        # adaptive: the step count is the run's own.  One step on a copy gives the first step size; the run's length in steps follows from it
-        # (h grows as the power falls: steps ~ L_eff / h0) -- a run that will end inside the window without margin goes to the complex128 line at once
-        probe = A.copy()
-        got = plan.chirp_propagate_c64(probe, chirp, Dt, g, None, length=float(L), phi_max=float(_F32(phi_max)), max_steps=1)
-        if got is None:
-            return None
-        h0 = float(got[1][1]) if got[0] >= 1 else float(L)
-        a_lin = float(_F32(alpha / 4.343))
-        x = a_lin * float(L)
-        l_eff = float(L) if abs(x) < 1e-6 else float(L) * (1.0 - np.exp(-x)) / x
-        est = l_eff / h0 if h0 > 0 else 1.0
-        if 0.85 * _C64_LINE_NO_MARGIN[0] <= est <= 1.15 * _C64_LINE_NO_MARGIN[1]:
-            return None
-        zs, z0, max_steps = [_F32(0)], _F32(0), 1 << 17
-        while True:
-            got = plan.chirp_propagate_c64(A, chirp, Dt, g, None, length=float(_F32(L - z0)), phi_max=float(_F32(phi_max)), max_steps=max_steps)
-            if got is None:
-                return None if z0 == 0 else _raise_chirp_midway()
-            steps, z = got
-            zs += [_F32(z0 + _F32(v)) for v in z[1:]]
-            if steps < max_steps or not (zs[-1] < L):
-                break
-            z0 = zs[-1]
-        if not _c64_line_has_margin(len(zs) - 1):              # (the estimate was off: the run is repeated on the complex128 line)
-            return None
-        return A, zs, None
+def _prepare_c128(fibre, A_dev, n, batch, dev):
+    """The same for the complex128 line: ``(A, P, Dt, g)``, ``P`` its (batch, n) buffer of powers."""
+    A = A_dev.astype(np.complex128)                         # (a copy when it has the type already: the caller's array is never modified)
+    A.shape = (batch, n)
+    P = _lib.DeviceArray((batch, n), np.float64, dev)
+    Dt = _lib.DeviceArray.from_host(np.asarray(fibre.operator(n), dtype=np.complex128), np.complex128, dev)
+    return A, P, Dt, fibre.g
 
 
 def _raise_chirp_midway():
     raise _lib.SsfmError("the one-launch chirp-z engine lost its workgroups in the middle of a run of more than 131072 steps")
 
 
-def _fiber_chirpz_locked(eng, A_dev, shape, dt, length, alpha, beta_2, beta_3, gamma, phi_max, h, return_steps, prec, dev, bar):
-    n = shape[-1]
-    batch = 1 if len(shape) == 1 else shape[0]
-    rt = _F32 if prec == _lib.C64 else np.float64
-    A = A_dev if A_dev.dtype == np.complex128 else A_dev.astype(np.complex128)
-    if A is A_dev:
-        A = A.copy()                                            # the caller's array is never modified
-    A.shape = (batch, n)
-    P = _lib.DeviceArray((batch, n), np.float64, dev)
-    Dt = _lib.DeviceArray.from_host(np.asarray(linear_operator(n, dt, alpha, beta_2, beta_3, prec), dtype=np.complex128), np.complex128, dev)
-    g = float(rt(gamma))
-    L = rt(length)
-    zs, snaps = [rt(0)], ([A.copy()] if return_steps else None)
-    steps = 0
-    if not return_steps and bar is None and os.environ.get("SSFM_CHIRP_LOOP", "c") != "python":
-        # the whole run from C (ssfm_chirp_propagate): no host call per kernel, the adaptive step rule on the device
-        if h is None:
-            b2, b3 = rt(beta_2), rt(beta_3)
-            if bool((b2 == 0 and b3 == 0) or rt(gamma) == 0):                  # one step of the whole length (reference devices.py:1163-1170)
-                eng.plan.chirp_propagate(A, P, eng.chirp, Dt, g, np.array([float(L)]), f32=(prec == _lib.C64))
-                zs = [rt(0), L]
-            else:
-                if not float(L) > 0:
-                    return A, zs, snaps
-                max_steps, z0 = 1 << 17, rt(0)
-                while True:                                   # (one call unless a run needs more than 131072 steps: then it goes on from where it is)
-                    steps, z = eng.plan.chirp_propagate(A, P, eng.chirp, Dt, g, None, length=float(rt(L - z0)), phi_max=float(rt(phi_max)),
-                                                        f32=(prec == _lib.C64), max_steps=max_steps)
-                    zs += [rt(z0 + rt(v)) for v in z[1:]]
-                    if steps < max_steps or not (zs[-1] < L):
-                        break
-                    z0 = zs[-1]
+def _adaptive_run(run, L, rt, max_steps=1 << 17, after=None):
+    """An adaptive run over the length ``L`` in the arithmetic ``rt``, at most ``max_steps`` steps per call: ``run(length=left, max_steps=k)`` advances the
+    field and returns ``(steps, z)``, ``z`` counted from where it started (``after(z)`` follows it), or None when its engine could not run.  One call
+    unless a run needs more than 131072 steps: then it goes on from where it is.  Returns the positions from 0 on; None when the first call gave up."""
+    zs, z0 = [rt(0)], rt(0)
+    while True:
+        got = run(length=float(rt(L - z0)), max_steps=max_steps)
+        if got is None:
+            return None if z0 == 0 else _raise_chirp_midway()
+        steps, z = got
+        zs += [rt(z0 + rt(v)) for v in z[1:]]
+        if after is not None:
+            after(z)
+        if steps < max_steps or not (zs[-1] < L):
+            return zs
+        z0 = zs[-1]
+
+
+def _fiber_chirpz_small_c64(fibre, A_dev, n, batch, dev):
+    """``precision="complex64"`` at up to 2048 samples that are not a power of two: the whole run in ONE launch on a complex64 line of M >= 2n - 1 <= 4096 points
+    (k_small_chirp / k_small_chirp_adapt instantiated for float; round 4).  The reference itself transforms such a length in single precision (pocketfft's Bluestein,
+    devices.py:1178-1180), so this is its arithmetic class: 2e-6 ... 7e-6 from the float64 solution after 100 steps (profiles/r04_chirpz_c64_error.txt) where the
+    complex128 line of the general path sits at 1e-13 -- and a step takes half the time (one CU does the four line transforms of a step; float64 was its bound).
+    ``precision="complex128"`` keeps the complex128 line.  None: the plan has no such engine, or its rows' workgroups did not meet: the general path runs."""
+    M = 1 << max(8, (2 * n - 2).bit_length())
+    plan = get_plan(M, batch, _lib.C64, dev)
+    L = _F32(fibre.length)
+    if not float(L) > 0:
+        return A_dev.astype(np.complex64), [_F32(0)], None       # (a copy when it has the type already)
+    with plan.lock:
+        A, chirp, Dt, g = _prepare_c64(fibre, A_dev, n, batch, dev)
+        known = fibre.known_run()
+        if known is not None:
+            hs, zs = known
+            if not plan.chirp_propagate_c64(A, chirp, Dt, g, hs):
+                return None
         else:
-            hs, z_all = step_schedule(length, h, prec)
-            eng.plan.chirp_propagate(A, P, eng.chirp, Dt, g, np.asarray(hs, dtype=np.float64), f32=(prec == _lib.C64))
-            zs = list(z_all)
+            phi = float(_F32(fibre.phi_max))
+            zs = _adaptive_run(functools.partial(plan.chirp_propagate_c64, A, chirp, Dt, g, None, phi_max=phi), L, _F32)
+            if zs is None:
+                return None
+        plan.synchronize()
+        return A, zs, None
+
+
+def _fiber_chirpz_medium_c64(fibre, A_dev, n, batch, dev):
+    """``precision="complex64"``, 2048 < n <= 65536 samples that are not a power of two: the whole run in one launch on one XCD on a complex64 line of
+    M >= 2n - 1 points, 2^13 ... 2^17 (k_medium_chirp / k_medium_chirp_adapt: four passes per step instead of five / seven launches; round 4).  The arithmetic
+    class of ``_fiber_chirpz_small_c64``.  None: a plan whose rows do not fit the one-XCD engine (2^17 points in all), more than four step sizes, or a launch
+    whose workgroups did not meet: the general path runs."""
+    M = 1 << (2 * n - 2).bit_length()
+    L = _F32(fibre.length)
+    if M * batch > (1 << 17) or not float(L) > 0:
+        return None
+    known = fibre.known_run()
+    if known is None and os.environ.get("SSFM_MEDIUM_ADAPT", "1") == "0":
+        return None
+    hs, zs = known if known is not None else (np.array([float(L)]), None)    # (an adaptive run counts as one step here; its own count is judged below)
+    if len(set(hs.tolist())) > 4 or not _c64_line_has_margin(len(hs)):
+        return None
+    plan = get_plan(M, batch, _lib.C64, dev)
+    with plan.lock:
+        A, chirp, Dt, g = _prepare_c64(fibre, A_dev, n, batch, dev)
+        if known is not None:
+            if not plan.chirp_propagate_c64(A, chirp, Dt, g, hs):
+                return None
+            return A, zs, None
+        # adaptive: the step count is the run's own.  One step on a copy gives the first step size; the run's length in steps follows from it
+        # (h grows as the power falls: steps ~ L_eff / h0) -- a run that will end inside the window without margin goes to the complex128 line at once
+        phi = float(_F32(fibre.phi_max))
+        probe = A.copy()
+        got = plan.chirp_propagate_c64(probe, chirp, Dt, g, None, length=float(L), phi_max=phi, max_steps=1)
+        if got is None:
+            return None
+        h0 = float(got[1][1]) if got[0] >= 1 else float(L)
+        a_lin = float(_F32(fibre.alpha / 4.343))
+        x = a_lin * float(L)
+        l_eff = float(L) if abs(x) < 1e-6 else float(L) * (1.0 - np.exp(-x)) / x
+        est = l_eff / h0 if h0 > 0 else 1.0
+        if 0.85 * _C64_LINE_NO_MARGIN[0] <= est <= 1.15 * _C64_LINE_NO_MARGIN[1]:
+            return None
+        zs = _adaptive_run(functools.partial(plan.chirp_propagate_c64, A, chirp, Dt, g, None, phi_max=phi), L, _F32)
+        if zs is None or not _c64_line_has_margin(len(zs) - 1):              # (the estimate was off: the run is repeated on the complex128 line)
+            return None
+        return A, zs, None
+
+
+def _fiber_chirpz_locked(eng, fibre, A_dev, n, batch, return_steps, dev, bar):
+    """The complex128 line (the caller holds the engine's plan): the whole run from C (ssfm_chirp_propagate: no host call per kernel, the adaptive step
+    rule on the device).  A caller that wants the field after every step (return_steps), a progress bar, or SSFM_CHIRP_LOOP=python gets the same entry
+    point a step at a time (one step size, or -- adaptive -- max_steps = 1 over what is left of the length: the step rule is evaluated on the device in
+    the caller's arithmetic either way, so the schedule is the whole run's bit for bit)."""
+    rt, L = fibre.rt, fibre.L
+    f32 = fibre.prec == _lib.C64
+    A, P, Dt, g = _prepare_c128(fibre, A_dev, n, batch, dev)
+    zs = [rt(0)]
+    snaps = [A.copy()] if return_steps else None
+
+    def fixed(hs):
+        eng.plan.chirp_propagate(A, P, eng.chirp, Dt, g, hs, f32=f32)
+
+    # over what is left of the length, at most max_steps steps: adaptive(length=..., max_steps=...) -> (steps, z)
+    adaptive = functools.partial(eng.plan.chirp_propagate, A, P, eng.chirp, Dt, g, None, phi_max=float(rt(fibre.phi_max)), f32=f32)
+
+    known = fibre.known_run()
+    if not return_steps and bar is None and os.environ.get("SSFM_CHIRP_LOOP", "c") != "python":
+        if known is not None:
+            fixed(known[0])
+            zs = known[1]
+        elif float(L) > 0:
+            zs = _adaptive_run(adaptive, L, rt)           # (this line always runs: never None)
         return A, zs, snaps
-    # A caller that wants the field after every step (return_steps), a progress bar, or SSFM_CHIRP_LOOP=python: the same C entry point a step at a time
-    # (ssfm_chirp_propagate with one step size, or -- adaptive -- with max_steps = 1 over what is left of the length: the step rule is evaluated on the
-    # device in the caller's arithmetic either way, so the schedule is the whole run's bit for bit)
+
+    steps = 0
+
     def after_step(hk):
+        nonlocal steps
+        steps += 1
         if return_steps:
             snaps.append(A.copy())
         if bar is not None:
             bar.update(min(100.0 * float(hk) / float(L), max(0.0, 100.0 - bar.n)))
             bar.set_postfix(FFTs=2 * steps)
-    if h is None:
-        b2, b3 = rt(beta_2), rt(beta_3)
-        single = bool((b2 == 0 and b3 == 0) or rt(gamma) == 0)
-        z = rt(0)
-        while z < L:
-            if single:
-                eng.plan.chirp_propagate(A, P, eng.chirp, Dt, g, np.array([float(L)]), f32=(prec == _lib.C64))
-                hk = L
-            else:
-                _, zz = eng.plan.chirp_propagate(A, P, eng.chirp, Dt, g, None, length=float(rt(L - z)), phi_max=float(rt(phi_max)), f32=(prec == _lib.C64), max_steps=1)
-                hk = rt(zz[1])
-            z = rt(z + hk)
-            steps += 1
-            zs.append(z)
+
+    if fibre.h is not None:
+        for hk in known[0]:
+            fixed(np.array([float(hk)]))
             after_step(hk)
-    else:
-        hs, z_all = step_schedule(length, h, prec)
-        for k, hk in enumerate(hs):
-            eng.plan.chirp_propagate(A, P, eng.chirp, Dt, g, np.array([float(hk)]), f32=(prec == _lib.C64))
-            steps += 1
-            after_step(hk)
-        zs = list(z_all)
+        zs = known[1]
+    elif float(L) > 0:                                      # (the reference's loop, `while z < length`, takes no step of a length <= 0)
+        if known is not None:
+            fixed(known[0])
+            after_step(L)
+            zs = known[1]
+        else:
+            zs = _adaptive_run(adaptive, L, rt, 1, lambda z: after_step(rt(z[1])))
     eng.plan.synchronize()
     return A, zs, snaps
+
+
+def _progress_bar(show_progress):
+    """The reference's tqdm bar, or None: not asked for, or tqdm is not installed."""
+    if not show_progress:
+        return None
+    try:
+        from tqdm.auto import tqdm
+    except ImportError:
+        return None
+    return tqdm(total=100, desc="Propagating", bar_format="{l_bar}{bar}|[{elapsed}{postfix}]", postfix={"FFTs": 0})
 
 
 # ------------------------------------------------------------------ FIBER / DBP
@@ -665,7 +681,6 @@ def FIBER(input: optical_signal,
         raise TypeError("`input` must be of type 'optical_signal'.")
     prec = _precision_code(precision)
     plan_dtype = np.complex64 if prec == _lib.C64 else np.complex128
-    rt = _F32 if prec == _lib.C64 else np.float64
 
     raw_s, raw_n = input._raw("signal"), input._raw("noise")
     dev = default_device() if device is None else int(device)
@@ -682,10 +697,12 @@ def FIBER(input: optical_signal,
     else:
         A = np.asarray(input.to_numpy())
         shape = A.shape
-    n = shape[-1]
-    batch = 1 if len(shape) == 1 else shape[0]
-    _check_size(n, prec)
-    if A is not None and _is_fast_size(n, prec):
+    n, batch = _rows(shape)
+    fast = _is_fast_size(n, prec)
+    if not fast:
+        _check_size(n, prec)
+    fibre = _Fibre.of(length, alpha, beta_2, beta_3, gamma, phi_max, h, float(grid.dt), prec)
+    if A is not None and fast:
         if A.dtype == np.complex128 and plan_dtype == np.complex64 and A.flags.c_contiguous:
             # the usual case (NumPy signals are complex128): upload as it lies and round to complex64 on the
             # device -- the same round-to-nearest cast, without a 32 -> 16 MiB conversion pass on the host
@@ -693,25 +710,18 @@ def FIBER(input: optical_signal,
         else:
             A = np.ascontiguousarray(A, dtype=plan_dtype)
 
-    if not _is_fast_size(n, prec):
+    if not fast:
         # any other length: chirp-z path on a power-of-two plan of >= 2n - 1 points (complex128 arithmetic; complex64 for complex64 callers of up to 2048 samples)
-        bar = None
-        if show_progress:
-            try:
-                from tqdm.auto import tqdm
-                bar = tqdm(total=100, desc="Propagating", bar_format="{l_bar}{bar}|[{elapsed}{postfix}]", postfix={"FFTs": 0})
-            except ImportError:
-                bar = None
+        bar = _progress_bar(show_progress)
         if A_dev is None:
             A_dev = _lib.DeviceArray.from_host(np.ascontiguousarray(A, dtype=np.complex128), np.complex128, dev)
-        out, zs, snaps, engine = _fiber_chirpz(A_dev, shape, float(grid.dt), length, alpha, beta_2, beta_3, gamma, phi_max, h, return_steps, prec, dev, bar)
+        out, zs, snaps, engine = _fiber_chirpz(fibre, A_dev, n, batch, return_steps, dev, bar)
         if bar is not None:
             bar.close()
         if return_steps:
-            keep = _every_index(len(snaps) - 1, every)
-            if z_list is not None:                      # the first step that reaches each position (0: the input; the last: the end field)
-                zs64 = np.asarray(zs, dtype=np.float64)
-                keep = [int(min(np.searchsorted(zs64, v, side="left"), len(snaps) - 1)) for v in np.asarray(z_list, dtype=np.float64).ravel()]
+            if every is not None:
+                _lib.check_every(every)                  # (rejected on this path even where `z_list` decides)
+            keep = _keep_indices(zs, len(snaps), every, z_list)
             A_z = np.stack([snaps[k].to_host() for k in keep]).astype(plan_dtype).reshape((len(keep),) + tuple(shape))
             return np.asarray(zs, dtype=np.float64)[keep], A_z
         res = out if out.dtype == plan_dtype else out.astype(plan_dtype)
@@ -721,42 +731,39 @@ def FIBER(input: optical_signal,
         output.engine = engine                                # which chirp-z line ran: "chirp_small_c64", "chirp_medium_c64" (one launch, complex64) or "chirp_line_c128"
         return back(output)
 
-    L = rt(length)
     plan = get_plan(n, batch, prec, dev)
     with plan.lock:
-        return back(_fiber_on_plan(plan, A, A_dev, shape, float(grid.dt), L, length, alpha, beta_2, beta_3, gamma, phi_max, h,
-                                   show_progress, return_steps, prec, plan_dtype, rt, dev, t0, every, z_list))
+        output = _fiber_on_plan(plan, fibre, A if A_dev is None else A_dev, shape, show_progress, return_steps, every, z_list)
+        if not return_steps:
+            output.execution_time = time.time() - t0
+        return back(output)
 
 
-def _every_index(steps: int, every):
-    """Indices of the snapshots ``every`` keeps of a run of ``steps`` steps: 0 (the input), every ``every``-th step, the last one."""
-    if every is None:
-        return list(range(steps + 1))
-    every = int(every)
-    if every < 1:
-        raise ValueError(f"every = {every}")
-    return list(range(0, steps, every)) + [steps]
+def _keep_indices(z, n_snaps: int, every, z_list):
+    """Which of the ``n_snaps`` snapshots of a run (the input, then one per step, at the positions ``z``) a caller keeps: with ``z_list``, for each
+    position the first step that reaches it (0: the input; the last: the end field); else what ``every`` keeps."""
+    if z_list is None:
+        return _lib.every_index(n_snaps - 1, every)
+    z = np.asarray(z, dtype=np.float64)
+    return [int(min(np.searchsorted(z, v, side="left"), n_snaps - 1)) for v in np.asarray(z_list, dtype=np.float64).ravel()]
 
 
-def _adaptive_capture(plan, gamma, length, phi_max, every, z_list, batch, n):
+def _adaptive_capture(plan, fibre, every, z_list):
     """``FIBER(h=None, return_steps=True, every=k | z_list=[...])`` on a power-of-two plan: the run once for its z log, the input restored, the run again
     with the capture at the step numbers that follow (``Plan.propagate_adaptive_capture``).  Returns (z of the kept snapshots, snapshots)."""
+    n, batch, run = plan.n, plan.batch, (fibre.gamma, fibre.length, fibre.phi_max)
     x0 = _lib.DeviceArray((batch, n), plan.cdtype, plan.device)
     plan.get_field_device(x0.ptr)
     first = plan.get_field().reshape(1, batch, n)
     # (the first pass on the engine the capture will run on: a capture that never fires -- the one-launch engines of the small plans find their
     # step sizes in another order of operations, and their z log differs from the launch-per-pass engines' in the last bits)
-    steps, z, _, _ = plan.propagate_adaptive_capture(gamma, length, phi_max, steps=np.array([1 << 40], dtype=np.int64))
-    if z_list is not None:
-        zl = np.asarray(z_list, dtype=np.float64).ravel()
-        keep = [int(min(np.searchsorted(z, rt_z, side="left"), steps)) for rt_z in zl]          # the first step with z_step >= z (0: the input; steps: the end)
-    else:
-        keep = _every_index(steps, every)
+    steps, z, _, _ = plan.propagate_adaptive_capture(*run, steps=np.array([1 << 40], dtype=np.int64))
+    keep = _keep_indices(z, steps + 1, every, z_list)
     want = sorted({k for k in keep if 0 < k < steps})
     got = {0: first[0]}
     if want:
         plan.set_field_device(x0.ptr)
-        steps2, z2, taken, fields = plan.propagate_adaptive_capture(gamma, length, phi_max, steps=np.asarray(want, dtype=np.int64))
+        steps2, z2, taken, fields = plan.propagate_adaptive_capture(*run, steps=np.asarray(want, dtype=np.int64))
         if steps2 != steps or not np.array_equal(z2, z) or list(taken) != want:
             raise _lib.SsfmError(f"the adaptive run did not repeat ({steps} / {steps2} steps, {len(taken)} of {len(want)} snapshots)")
         for k, f in zip(want, fields):
@@ -765,47 +772,35 @@ def _adaptive_capture(plan, gamma, length, phi_max, every, z_list, batch, n):
     return np.asarray(z)[keep], np.stack([got[k] for k in keep])
 
 
-def _fiber_on_plan(plan, A, A_dev, shape, dt, L, length, alpha, beta_2, beta_3, gamma, phi_max, h, show_progress, return_steps,
-                   prec, plan_dtype, rt, dev, t0, every=None, z_list=None):
-    """The fused two-kernel engine behind ``FIBER`` (the caller holds the plan's lock for the whole sequence)."""
-    n = shape[-1]
-    batch = 1 if len(shape) == 1 else shape[0]
-    op_tag = _tag("fibre", dt, float(alpha), float(beta_2), float(beta_3))
+def _fiber_on_plan(plan, fibre, field, shape, show_progress, return_steps, every=None, z_list=None):
+    """The fused two-kernel engine behind ``FIBER`` (the caller holds the plan's lock for the whole sequence).  ``field``: the input, a host array
+    or a device array of the plan's type."""
+    n, batch = plan.n, plan.batch
+    gamma, L = fibre.gamma, fibre.L
+    op_tag = _tag("fibre", fibre.dt, float(fibre.alpha), float(fibre.beta_2), float(fibre.beta_3))
     if plan.tag(0) != op_tag:                             # D~ is O(N) host work + an upload: reuse it while the plan still holds it
-        plan.set_linear_operator(linear_operator(n, dt, alpha, beta_2, beta_3, prec))
+        plan.set_linear_operator(fibre.operator(n))
         plan.set_tag(0, op_tag)
-    if A_dev is not None:
-        plan.set_field_device(A_dev.ptr)
+    if _on_device(field):
+        plan.set_field_device(field.ptr)
     else:
-        plan.set_field(A)
+        plan.set_field(field)
 
-    bar = None
-    if show_progress:
-        try:
-            from tqdm.auto import tqdm
-            bar = tqdm(total=100, desc="Propagating", bar_format="{l_bar}{bar}|[{elapsed}{postfix}]", postfix={"FFTs": 0})
-        except ImportError:
-            bar = None
-
-    if h is None:
-        b2, b3, g = rt(beta_2), rt(beta_3), rt(gamma)
-        single = bool((b2 == 0 and b3 == 0) or g == 0)
-        if return_steps and (every is not None or z_list is not None) and not single and n <= (1 << _lib.DIRECT_LOG2_MAX) and float(L) > 0:
-            z, snaps = _adaptive_capture(plan, gamma, length, phi_max, every, z_list, batch, n)
+    bar = _progress_bar(show_progress)
+    if fibre.h is None:
+        if return_steps and (every is not None or z_list is not None) and not fibre.single and n <= (1 << _lib.DIRECT_LOG2_MAX) and float(L) > 0:
+            z, snaps = _adaptive_capture(plan, fibre, every, z_list)
             steps, every, z_list = len(z) - 1, None, None                         # (thinned already)
-        else:
-            steps, z, snaps = plan.propagate_adaptive(gamma, length, phi_max, single, snapshots=return_steps)
-            if return_steps and z_list is not None:                              # (a single step, a split plan: every snapshot was taken; picked here)
-                zl = np.asarray(z_list, dtype=np.float64).ravel()
-                keep = [int(min(np.searchsorted(np.asarray(z, dtype=np.float64), v, side="left"), len(z) - 1)) for v in zl]
-                snaps, z, every = snaps[keep], np.asarray(z)[keep], None
+        else:                                                                    # (a single step, a split plan: every snapshot is taken; picked below)
+            steps, z, snaps = plan.propagate_adaptive(gamma, fibre.length, fibre.phi_max, fibre.single, snapshots=return_steps)
     else:
-        hs, z = step_schedule(length, h, prec)
+        hs, z = fibre.schedule()
         steps = hs.size
         snaps = None
+        z_list = None                                     # a fixed step ignores `z_list`: ADVICE.md's second finding, left as it is here
         if return_steps and every is not None and steps and n > (1 << _lib.DIRECT_LOG2_MAX):
             # a split plan (more than 2^22 samples per row) has no capture beside the run: `every` steps per call, the field read back in between
-            k = _every_index(steps, every)
+            k = _lib.every_index(steps, every)
             fields = [plan.get_field()]
             for a0, a1 in zip(k[:-1], k[1:]):
                 plan.propagate_fixed(gamma, hs[a0:a1])
@@ -827,24 +822,23 @@ def _fiber_on_plan(plan, A, A_dev, shape, dt, L, length, alpha, beta_2, beta_3, 
         elif steps:
             plan.propagate_fixed(gamma, hs)
     if bar is not None:
-        if h is None or return_steps:
+        if fibre.h is None or return_steps:
             bar.update(100)
             bar.set_postfix(FFTs=2 * int(steps))
         bar.close()
 
     if return_steps:
-        if every is not None and snaps.shape[0] == len(z):         # (the adaptive run, or a run of no steps: every snapshot was taken; thinned here)
-            keep = _every_index(snaps.shape[0] - 1, every)
+        if (every is not None or z_list is not None) and snaps.shape[0] == len(z):      # (every snapshot was taken: the adaptive run, a run of no steps; thinned here)
+            keep = _keep_indices(z, snaps.shape[0], every, z_list)
             snaps, z = snaps[keep], np.asarray(z)[keep]
         A_z = snaps.reshape((snaps.shape[0],) + shape)
         return np.asarray(z, dtype=np.float64), A_z
     if KEEP_ON_DEVICE:
-        out = _lib.DeviceArray(shape, plan_dtype, dev)
+        out = _lib.DeviceArray(shape, plan.cdtype, plan.device)
         plan.get_field_device(out.ptr)
         output = optical_signal.from_device(out)
     else:
         output = optical_signal(plan.get_field().reshape(shape))
-    output.execution_time = time.time() - t0
     # beside the reference's execution_time: which engine ran ("two_kernel", "medium", "adaptive_fused" ..., _lib.ENGINES) and whether a one-launch
     # engine had to give way to its fallback -- a shared GPU or a profiler turns the fast engines off without any other sign
     info = plan.last_run_info()
@@ -887,8 +881,7 @@ def DM(input: optical_signal, D: float, retH: bool = False, *, device=None):
     raw_s, raw_n = input._raw("signal"), input._raw("noise")
     dev = default_device() if device is None else int(device)
     shape = tuple(raw_s.shape)
-    n = shape[-1]
-    rows = 1 if len(shape) == 1 else shape[0]
+    n, rows = _rows(shape)
     _check_size(n, _lib.C128)
     has_noise = raw_n is not NULL
     if not _is_fast_size(n, _lib.C128):
@@ -1699,8 +1692,7 @@ def PM(op_input: optical_signal, el_input, Vpi: float = 5.0, *, device=None) -> 
     raw_v, raw_vn = el_input._raw("signal"), el_input._raw("noise")
     dev = default_device() if device is None else int(device)
     shape = tuple(raw_s.shape)
-    n = shape[-1]
-    n_pol = 1 if len(shape) == 1 else shape[0]
+    n, n_pol = _rows(shape)
     cplx = any(a is not NULL and a.dtype.kind == "c" for a in (raw_v, raw_vn))
     vdt = np.complex128 if cplx else np.float64
 

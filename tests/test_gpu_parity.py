@@ -507,6 +507,73 @@ def test_any_length_with_nothing_to_propagate_is_the_identity():
         np.testing.assert_array_equal(y, a.astype(np.complex64))
 
 
+# The three chirp-z lines at their smallest lengths: (samples, precision, engine).  1000 samples: a line of 2048 points, the small complex64 line;
+# 2049: a line of 8192, the first length of the medium line; complex128 callers: the complex128 line.  Dual polarisation, a fixed step that gives
+# 5 steps and an adaptive bound that gives 16 or 17 / 14 steps (the tests assert 10 ... 40; the medium line runs below its window without margin, 27 steps).
+_CHIRP_LINES = [(1000, "complex64", "chirp_small_c64"), (2049, "complex64", "chirp_medium_c64"), (1000, "complex128", "chirp_line_c128")]
+_CHIRP_RUNS = {"fixed": dict(length=5, h=1.0, **workloads.SMF), "adaptive": dict(length=5, phi_max=0.004, **workloads.SMF)}
+
+
+def _chirp_line_field(n):
+    gv(**workloads.BENCH_GV)
+    return workloads.qpsk_field(1 << 12, seed=21, power_w=5e-3)[:, :n]
+
+
+@pytest.mark.parametrize("mode", ["fixed", "adaptive"])
+@pytest.mark.parametrize("n,precision,engine", _CHIRP_LINES)
+def test_any_length_return_steps_with_a_stride_and_with_positions(n, precision, engine, mode):
+    """``return_steps`` on the chirp-z path (a step per call on the complex128 line), fixed and adaptive: ``every=3`` keeps rows 0, 3, ..., last of the plain
+    ``return_steps`` call and ``z_list`` the first step that reaches each position -- below 0 (the input), between two steps, exactly on a step's z, beyond the
+    length (the end field).  An adaptive run repeats bit for bit, so the bound is equality, ``z`` included."""
+    x = optical_signal(_chirp_line_field(n))
+    kw = dict(_CHIRP_RUNS[mode], precision=precision)
+    z_all, A_all = oa.FIBER(x, return_steps=True, **kw)
+    S = len(z_all) - 1
+    assert (S == 5) if mode == "fixed" else (10 <= S <= 40), S
+    assert A_all.shape == (S + 1, 2, n) and A_all.dtype == np.dtype(precision)
+    keep = list(range(0, S, 3)) + [S]
+    z3, A3 = oa.FIBER(x, return_steps=True, every=3, **kw)
+    np.testing.assert_array_equal(z3, z_all[keep])
+    np.testing.assert_array_equal(A3, A_all[keep])
+    zl = [-1.0, 0.5 * (float(z_all[2]) + float(z_all[3])), float(z_all[4]), 7.0]
+    idx = [next((k for k in range(S + 1) if z_all[k] >= v), S) for v in zl]
+    assert idx == [0, 3, 4, S]
+    zp, Ap = oa.FIBER(x, return_steps=True, z_list=zl, **kw)
+    np.testing.assert_array_equal(zp, z_all[idx])
+    np.testing.assert_array_equal(Ap, A_all[idx])
+
+
+@pytest.mark.parametrize("mode", ["fixed", "adaptive"])
+@pytest.mark.parametrize("n,precision,engine", _CHIRP_LINES)
+def test_any_length_leaves_a_device_resident_input_as_it_was(n, precision, engine, mode):
+    """The caller's array is never modified: a device-resident input reads back byte for byte the same after ``FIBER`` on each chirp-z line, given in the
+    line's own type (the line works on a copy) and in the other one (on a cast)."""
+    a = _chirp_line_field(n)
+    for dtype in (np.complex64, np.complex128):
+        x = _lib.DeviceArray.from_host(a.astype(dtype), dtype)
+        before = x.to_host().tobytes()
+        out = oa.FIBER(optical_signal.from_device(x), precision=precision, **_CHIRP_RUNS[mode])
+        assert out.signal.shape == a.shape and np.isfinite(out.signal).all() and not np.array_equal(out.signal, a.astype(out.signal.dtype))
+        assert x.to_host().tobytes() == before, (dtype, out.engine)
+
+
+@pytest.mark.parametrize("mode", ["fixed", "adaptive"])
+@pytest.mark.parametrize("n,precision,engine", _CHIRP_LINES)
+def test_any_length_names_the_chirp_line_that_ran(n, precision, engine, mode):
+    """``FIBER(...).engine`` on the three routes of the chirp-z path.  A one-launch route is skipped only where the environment sets a knob that governs
+    it to the value that switches it off (the knob suite); every route it leaves on is still checked."""
+    off = {"SSFM_CHIRP_LOOP": "python", "SSFM_FUSED_PATIENCE_TICKS": "-1"}
+    if engine == "chirp_small_c64":
+        off.update(SSFM_CHIRP_SMALL="0", SSFM_SMALL="0")
+    elif engine == "chirp_medium_c64":
+        off.update(SSFM_MEDIUM="0", **({"SSFM_MEDIUM_ADAPT": "0"} if mode == "adaptive" else {}))
+    hit = {k: v for k, v in off.items() if os.environ.get(k) == v}
+    if hit and engine != "chirp_line_c128":
+        pytest.skip(f"the environment switches this one-launch engine off: {hit}")
+    out = oa.FIBER(optical_signal(_chirp_line_field(n)), precision=precision, **_CHIRP_RUNS[mode])
+    assert out.engine == engine, (out.engine, mode)
+
+
 def test_lengths_beyond_the_range_are_rejected():
     gv(sps=16, R=10e9)
     with pytest.raises(ValueError, match="samples per polarisation"):
