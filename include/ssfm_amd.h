@@ -367,6 +367,22 @@ SSFM_API int ssfm_chirp_propagate(ssfm_plan* plan, int64_t plan_n, int batch, vo
  * arithmetic class; its accuracy margin and when a caller should prefer the complex128 line: opticomlib_amd/devices.py _c64_line_has_margin.) */
 SSFM_API int ssfm_chirp_propagate_c64(ssfm_plan* plan, void* A, const void* chirp, const void* Dt, int64_t n, double gamma, const double* hs, int64_t nsteps,
                              double length, double phi_max, int64_t max_steps, double* z_out, int64_t* steps_out);
+/* FIBER / DBP of a dual-polarisation field with MANAKOV coupling: the nonlinear phase of both polarisations follows the power in both,
+ *     P = |A_x|^2 + |A_y|^2,   A <- A exp(i g P h/2);  A <- ifft(fft(A) exp(D~ h));  A <- A exp(i g P h/2)        (P of the step's start, as the
+ * reference keeps its N^ over a step, devices.py:1175-1181), where the scalar run of ssfm_propagate_* rotates each row by its own |A|^2.
+ * The plan: batch 2, not a split plan, either precision; its field (ssfm_set_field) is advanced in place, its linear operator
+ * (ssfm_set_linear_operator) is D~; g = gamma * kappa in the caller's arithmetic (kappa = 8/9 for the Manakov equation).  All step arithmetic is the
+ * plan's real type (float32 on a complex64 plan).  hs != NULL: fixed step, `nsteps` sizes (HOST; positive and finite); asynchronous on the plan's
+ * stream.  hs == NULL: the adaptive rule h = phi_max / (|g| max P), clamped to the rest of `length`, evaluated on the device, at most max_steps
+ * steps; z_out (HOST, nullable, max_steps + 1 doubles) receives z after every step; synchronous.  *steps_out: the steps taken.
+ * snaps (DEVICE, nullable; snap_capacity fields of 2 x n): the field after every snap_every-th step and after the last one, in order -- step s
+ * (from 1) goes to slot ceil(s / snap_every) - 1.  chunk: adaptive steps queued between two looks at the device's step control (0: chosen from
+ * the step size); steps queued behind the end of the run leave the field bit for bit as it is, so the result does not depend on it.
+ * A step is a pointwise launch (the closing half rotation of one step and the opening one of the next in one pass over both rows) and the
+ * three launches of ssfm_apply_table; an adaptive step adds the maximum of P, the one-thread step control and the table exp(D~ h) / n.  The
+ * table slots of ssfm_transfer_table are overwritten (their tags cleared); the linear operator stays. */
+SSFM_API int ssfm_manakov_propagate(ssfm_plan* plan, double g, const double* hs, int64_t nsteps, double length, double phi_max, int64_t max_steps,
+                           void* snaps, int64_t snap_every, int64_t snap_capacity, int64_t chunk, double* z_out, int64_t* steps_out);
 /* x <- ifft_n(fft_n(x) * tab) (exponent = 0: DM's H for any length, devices.py:1019-1035) or * exp(tab) (exponent != 0) for every row of the DEVICE array
  * A (batch x n complex128, in place); tab: n complex128, DEVICE.  Plan as for ssfm_chirp_propagate.  Asynchronous on the plan's stream. */
 SSFM_API int ssfm_chirp_transfer(ssfm_plan* plan, int64_t plan_n, int batch, void* A, const void* chirp, const void* tab, int64_t n, int exponent);
@@ -434,7 +450,8 @@ enum ssfm_engine {
     SSFM_ENGINE_CHIRP_MEDIUM = 11,     /* any length, 2048 < n <= 65536, complex64: fixed step, one launch per run on one XCD */
     SSFM_ENGINE_CHIRP_MEDIUM_ADAPT = 12, /* ... adaptive */
     SSFM_ENGINE_SPLIT = 13,            /* more than 2^22 samples per row, fixed step: four launches per step (csrc/ssfm_split.hpp) */
-    SSFM_ENGINE_SPLIT_ADAPT = 14       /* ... adaptive: five launches per step */
+    SSFM_ENGINE_SPLIT_ADAPT = 14,      /* ... adaptive: five launches per step */
+    SSFM_ENGINE_MANAKOV_LINE = 15      /* Manakov-coupled polarisations (ssfm_manakov_propagate): four launches per fixed step, seven adaptive */
 };
 typedef struct ssfm_run_info {
     int engine;

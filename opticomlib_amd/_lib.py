@@ -78,6 +78,7 @@ SYMBOLS = {
     "ssfm_device_chirp": (_I, [_I, _VP, _I64, _I]),
     "ssfm_chirp_setup": (_I, [_VP, _I64, _I64]),
     "ssfm_chirp_propagate_c64": (_I, [_VP, _VP, _VP, _VP, _I64, _D, C.POINTER(_D), _I64, _D, _D, _I64, C.POINTER(_D), C.POINTER(_I64)]),
+    "ssfm_manakov_propagate": (_I, [_VP, _D, C.POINTER(_D), _I64, _D, _D, _I64, _VP, _I64, _I64, _I64, C.POINTER(_D), C.POINTER(_I64)]),
     "ssfm_chirp_transfer": (_I, [_VP, _I64, _I, _VP, _VP, _VP, _I64, _I]),
     "ssfm_chirp_fourier": (_I, [_VP, _I64, _I, _VP, _VP, _VP, _I64, _I]),
     "ssfm_device_reduce": (_I, [_I, _I, _VP, _VP, _I, _I64, _I, C.POINTER(_D)]),
@@ -134,7 +135,7 @@ SYMBOLS = {
 
 # enum ssfm_engine of include/ssfm_amd.h, by value
 ENGINES = ("none", "two_kernel", "small", "medium", "adaptive_3_launches", "adaptive_fused", "small_adaptive", "medium_adaptive",
-           "chirp_small", "chirp_small_adaptive", "chirp_steps", "chirp_medium", "chirp_medium_adaptive", "split", "split_adaptive")
+           "chirp_small", "chirp_small_adaptive", "chirp_steps", "chirp_medium", "chirp_medium_adaptive", "split", "split_adaptive", "manakov_line")
 DIRECT_LOG2_MAX = 22      # rows of more than 2^22 samples are split plans (csrc/ssfm_split.hpp): propagation, DM and field transfers -- no tables, chirp-z or strided capture
 
 
@@ -908,6 +909,25 @@ class Plan:
             return False if z is None else None
         _check(rc, "ssfm_chirp_propagate_c64")
         return True if z is None else (int(steps.value), z[: int(steps.value) + 1])
+
+    def manakov_propagate(self, g: float, hs=None, *, length: float = 0.0, phi_max: float = 0.0, max_steps: int = 1 << 17, snaps: "DeviceArray" = None,
+                          every: int = 1, chunk: int = 0):
+        """A Manakov-coupled run of this two-row plan's field on its linear operator (``ssfm_manakov_propagate``); ``g`` = gamma * kappa in the caller's
+        arithmetic.  ``hs``: host array of step sizes (fixed step; asynchronous) or None for the adaptive rule over ``length`` (synchronous).  ``snaps``:
+        device array of at least ``ceil(steps / every)`` fields for the field after every ``every``-th step and the last one.  ``chunk``: adaptive steps
+        queued per look at the device's step control (0: chosen from the step size; the result does not depend on it).  Returns ``(steps, z)``, ``z`` =
+        positions after every step (adaptive) or None (fixed)."""
+        steps, z = _I64(0), None
+        cap = 0 if snaps is None else snaps.nbytes // (2 * self.n * np.dtype(self.cdtype).itemsize)
+        if hs is not None:
+            hs = np.ascontiguousarray(hs, dtype=np.float64)
+            run = (hs.ctypes.data_as(C.POINTER(_D)), hs.size, 0.0, 0.0, 1)
+        else:
+            z = np.zeros(int(max_steps) + 1, dtype=np.float64)
+            run = (None, 0, float(length), float(phi_max), int(max_steps))
+        api.ssfm_manakov_propagate(self._h, float(g), *run, snaps, check_every(every), cap, int(chunk),
+                                   None if z is None else z.ctypes.data_as(C.POINTER(_D)), C.byref(steps))
+        return int(steps.value), (None if z is None else z[: int(steps.value) + 1])
 
     def debug_fft(self) -> np.ndarray:
         out = host_empty((self.batch, self.n), self.cdtype)

@@ -60,6 +60,20 @@ SSFM_INTERNAL int64_t plan_length(ssfm_plan* plan, int* batch, int* precision);
 // hipMalloc / hipFree pair per call -- hipFree waits for the whole device and stalls the streams of every other plan
 SSFM_INTERNAL int plan_workspace(ssfm_plan* plan, int slot, size_t bytes, void** out);
 
+// What the Manakov line (manakov.hip) works on: the field, D~ in the order of the plan's transfer tables (element i of a table is a function of element i of
+// it), the two table slots of ssfm_apply_table (made if need be; their tags are cleared: the caller overwrites them).  The run is recorded as the plan's last
+// (SSFM_ENGINE_MANAKOV_LINE).  SSFM_ERR_STATE without a linear operator, SSFM_ERR_UNSUPPORTED for split plans.
+struct ManakovPlan {
+    void* F;
+    const void* D;
+    void* tab[2];
+    void* stream;
+    int64_t n;
+    int batch, precision;
+};
+SSFM_INTERNAL int plan_manakov_begin(ssfm_plan* plan, ManakovPlan* out);
+SSFM_INTERNAL void plan_count_launches(ssfm_plan* plan, int64_t launches);     // (ssfm_last_propagate_ms's count)
+
 // Philox4x32-10 (Salmon et al., SC'11): ten rounds on the counter `c` under the key (k0, k1) -- the documented device generator of
 // ssfm_device_randn (device_mem.hip) and of the PPM tie-breaking with rng="device" (ppm.hip).
 __device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, unsigned k1) {

@@ -3172,6 +3172,30 @@ int64_t plan_length(ssfm_plan* plan, int* batch, int* precision) {
     return P_->n_full;
 }
 int plan_workspace(ssfm_plan* plan, int slot, size_t bytes, void** out) { WITH_PLAN(plan, P_->workspace(slot, bytes, out)); }
+namespace {
+template <typename PT> static int manakov_begin_impl(PT* P_, ManakovPlan* out) {
+    if (int rc = P_->no_split("ssfm_manakov_propagate")) return rc;
+    if (int rc = P_->use_device()) return rc;
+    if (!P_->have_op) return fail(SSFM_ERR_STATE, "ssfm_manakov_propagate: the plan has no linear operator (ssfm_set_linear_operator)");
+    for (int slot = 0; slot < 2; ++slot) {
+        if (int rc = P_->ensure_xfer(slot)) return rc;
+        P_->tags[1 + slot] = 0;
+        out->tab[slot] = P_->xfer_tab[slot];
+    }
+    out->F = P_->F; out->D = P_->dperm; out->stream = P_->stream; out->n = P_->n; out->batch = P_->batch; out->precision = P_->precision;
+    P_->last_engine = SSFM_ENGINE_MANAKOV_LINE; P_->last_fell_back = 0; P_->last_launches = 0; P_->timed = false;
+    return SSFM_OK;
+}
+}  // namespace
+int plan_manakov_begin(ssfm_plan* plan, ManakovPlan* out) {
+    if (!out) return fail(SSFM_ERR_INVALID, "ssfm_manakov_propagate: NULL plan description");
+    WITH_PLAN(plan, manakov_begin_impl(P_, out));
+}
+void plan_count_launches(ssfm_plan* plan, int64_t launches) {
+    if (!plan || !plan->impl) return;
+    if (plan->impl->precision == SSFM_C64) static_cast<PlanT<float>*>(plan->impl)->last_launches += launches;
+    else static_cast<PlanT<double>*>(plan->impl)->last_launches += launches;
+}
 int plan_chirp_step(ssfm_plan* plan, const void* mul_dev, const ChirpStepIO* io) {
     if (!io) return fail(SSFM_ERR_INVALID, "chirp step: NULL field description");
     WITH_PLAN(plan, P_->apply_tables_mul(mul_dev, io));

@@ -655,7 +655,9 @@ def FIBER(input: optical_signal,
           precision="complex64",
           device=None,
           every: int = None,
-          z_list=None):
+          z_list=None,
+          coupling: str = None,
+          kappa: float = None):
     """Optical fibre: symmetric split-step Fourier solution of the scalar NLSE per polarisation.
 
     Parameters as the reference (``devices.py:1038-1083``): ``length`` [km], ``alpha`` [dB/km],
@@ -674,8 +676,19 @@ def FIBER(input: optical_signal,
     ``z_list`` (round 6) keep the run's own engine as well (``ssfm_adaptive_set_capture``): ``z_list`` = positions [km] -- for each
     the field after the first step that reaches it (the input for z <= 0, the end field beyond the length).  The run is
     made twice: once for its z log (an adaptive run repeats bit for bit), once with the capture at the steps that follow from it.
+
+    ``coupling`` (keyword-only): ``None`` -- the reference's behaviour: the two polarisations of a ``(2, N)`` field are two scalar fibres that share
+    only the adaptive step size -- or ``"manakov"``: the nonlinear phase of BOTH polarisations follows the power in both,
+    ``exp(1j * gamma * kappa * (|A_x|^2 + |A_y|^2) * h / 2)`` per half step, the Manakov equation of a fibre whose birefringence scrambles the
+    polarisation state (``kappa`` defaults to 8/9; ``kappa=1`` is the coupled equation without the averaging).  Everything else -- the stale power
+    over a step, the coefficient rounding, the step rule ``h = phi_max / max(|gamma kappa| P)`` -- is the reference's loop.  For ``(2, N)`` fields
+    of a power-of-two length up to 2^22 (:func:`_fiber_manakov`).
     """
     t0 = time.time()
+    if coupling is not None and coupling != "manakov":
+        raise ValueError(f"coupling must be None (per polarisation) or 'manakov', got {coupling!r}")
+    if coupling is None and kappa is not None:
+        raise ValueError("kappa belongs to coupling='manakov'")
     input, grid, back = _adopt(input, "optical_signal")
     if not isinstance(input, optical_signal):
         raise TypeError("`input` must be of type 'optical_signal'.")
@@ -698,6 +711,8 @@ def FIBER(input: optical_signal,
         A = np.asarray(input.to_numpy())
         shape = A.shape
     n, batch = _rows(shape)
+    if coupling is not None:
+        kappa = _check_manakov(shape, prec, kappa)
     fast = _is_fast_size(n, prec)
     if not fast:
         _check_size(n, prec)
@@ -733,10 +748,100 @@ def FIBER(input: optical_signal,
 
     plan = get_plan(n, batch, prec, dev)
     with plan.lock:
-        output = _fiber_on_plan(plan, fibre, A if A_dev is None else A_dev, shape, show_progress, return_steps, every, z_list)
+        if coupling is not None:
+            output = _fiber_manakov(plan, fibre, kappa, A if A_dev is None else A_dev, shape, show_progress, return_steps, every, z_list)
+        else:
+            output = _fiber_on_plan(plan, fibre, A if A_dev is None else A_dev, shape, show_progress, return_steps, every, z_list)
         if not return_steps:
             output.execution_time = time.time() - t0
         return back(output)
+
+
+MANAKOV_KAPPA = 8.0 / 9.0
+_MANAKOV_LOG2_MAX = _lib.DIRECT_LOG2_MAX          # no split plans
+
+
+def _check_manakov(shape, prec: int, kappa) -> float:
+    """What ``coupling="manakov"`` takes, checked before anything touches the GPU; returns kappa (8/9 when None)."""
+    n = int(shape[-1])
+    if len(shape) != 2 or shape[0] != 2:
+        raise ValueError(f"coupling='manakov' is not supported for a field of shape {tuple(shape)}: it couples the two polarisations of a (2, N) field "
+                         f"(batches of coupled fields are not supported either)")
+    if not _is_fast_size(n, prec) or n > (1 << _MANAKOV_LOG2_MAX):
+        raise ValueError(f"coupling='manakov' is not supported for {n} samples per polarisation: a power of two from 2^8 to 2^{_MANAKOV_LOG2_MAX} is needed")
+    kappa = MANAKOV_KAPPA if kappa is None else float(kappa)
+    if not np.isfinite(kappa) or kappa <= 0:
+        raise ValueError(f"coupling='manakov' is not supported for kappa = {kappa!r}: a finite positive factor is needed")
+    return kappa
+
+
+def _fiber_manakov(plan, fibre, kappa: float, field, shape, show_progress, return_steps, every=None, z_list=None):
+    """``FIBER(coupling="manakov")`` on a power-of-two plan of two rows (the caller holds its lock): the Manakov line of csrc/manakov.hip -- a pointwise
+    launch over both rows and the plan's table transform per step, the adaptive step rule on the device.  ``field``: the input, a host array or a
+    device array of the plan's type.  Snapshots (``return_steps``) are taken on the device beside the run: every ``every``-th step, or every step
+    when ``z_list`` picks among them."""
+    n, batch, rt, L = plan.n, plan.batch, fibre.rt, fibre.L
+    g = float(rt(rt(fibre.gamma) * rt(kappa)))
+    op_tag = _tag("fibre", fibre.dt, float(fibre.alpha), float(fibre.beta_2), float(fibre.beta_3))
+    if plan.tag(0) != op_tag:
+        plan.set_linear_operator(fibre.operator(n))
+        plan.set_tag(0, op_tag)
+    if _on_device(field):
+        plan.set_field_device(field.ptr)
+    else:
+        plan.set_field(field)
+    bar = _progress_bar(show_progress)
+    if every is not None:
+        every = _lib.check_every(every)
+    stride = every if (every is not None and z_list is None) else 1
+    first = plan.get_field().reshape(1, batch, n) if return_steps else None
+
+    def snapshots(steps_at_most):
+        return _lib.DeviceArray((max(1, -(-steps_at_most // stride)), batch, n), plan.cdtype, plan.device) if return_steps else None
+
+    known = fibre.known_run()
+    if fibre.h is None and not fibre.single and g == 0.0:
+        known = (np.array([float(L)]), [rt(0), L])            # (kappa rounds gamma away: nothing to adapt to, one step as for gamma == 0)
+    snaps = None
+    if not float(L) > 0:                                       # (the reference's loop, `while z < length`, takes no step)
+        steps, z = 0, [rt(0)]
+    elif known is not None:
+        hs, z = known
+        steps = len(hs)
+        snaps = snapshots(steps)
+        plan.manakov_propagate(g, hs, snaps=snaps, every=stride)
+    else:
+        max_steps = 1 << 17
+        if return_steps:
+            # (the snapshot buffer follows the steps the run takes: the run once for its count -- an adaptive run repeats bit for bit --, the input restored)
+            x0 = _lib.DeviceArray((batch, n), plan.cdtype, plan.device)
+            plan.get_field_device(x0.ptr)
+            max_steps, _ = plan.manakov_propagate(g, None, length=fibre.length, phi_max=fibre.phi_max, max_steps=max_steps)
+            plan.set_field_device(x0.ptr)
+            snaps = snapshots(max_steps)
+        steps, z = plan.manakov_propagate(g, None, length=fibre.length, phi_max=fibre.phi_max, max_steps=max_steps, snaps=snaps, every=stride)
+    if bar is not None:
+        bar.update(100)
+        bar.set_postfix(FFTs=2 * int(steps))
+        bar.close()
+
+    if return_steps:
+        plan.synchronize()
+        kept = _lib.every_index(steps, stride if stride > 1 else None)
+        fields = np.concatenate([first, snaps.to_host()[: len(kept) - 1]]) if steps else first
+        z = np.asarray(z, dtype=np.float64)[kept]
+        if z_list is not None:
+            keep = _keep_indices(z, fields.shape[0], None, z_list)
+            fields, z = fields[keep], z[keep]
+        return z, fields.reshape((fields.shape[0],) + tuple(shape))
+    if KEEP_ON_DEVICE:
+        out = _lib.DeviceArray(shape, plan.cdtype, plan.device)
+        plan.get_field_device(out.ptr)
+        output = optical_signal.from_device(out)
+    else:
+        output = optical_signal(plan.get_field().reshape(shape))
+    output.engine = plan.last_run_info()["engine"]
+    return output
 
 
 def _keep_indices(z, n_snaps: int, every, z_list):
@@ -860,11 +965,13 @@ def DBP(input: optical_signal,
         precision="complex64",
         device=None,
         every: int = None,
-        z_list=None):
-    """Digital back-propagation = ``FIBER`` with every operator negated (``devices.py:1280-1283``)."""
+        z_list=None,
+        coupling: str = None,
+        kappa: float = None):
+    """Digital back-propagation = ``FIBER`` with every operator negated (``devices.py:1280-1283``); ``coupling`` / ``kappa`` as ``FIBER``'s."""
     return FIBER(input, length=length, alpha=-alpha, beta_2=-beta_2, beta_3=-beta_3, gamma=-gamma,
                  phi_max=phi_max, h=h, show_progress=show_progress, return_steps=return_steps,
-                 precision=precision, device=device, every=every, z_list=z_list)
+                 precision=precision, device=device, every=every, z_list=z_list, coupling=coupling, kappa=kappa)
 
 
 # ------------------------------------------------------------------ DM

@@ -281,6 +281,10 @@ def propagate_channels(fields, dt: float, to_all: bool = True, dbp: bool = False
     from .typing import optical_signal
 
     kw = dict(fiber_kw)
+    if kw.get("coupling") is not None or kw.get("kappa") is not None:
+        raise ValueError("propagate_channels does not support coupling=...: batches of Manakov-coupled fields are not supported (call FIBER per field)")
+    kw.pop("coupling", None)
+    kw.pop("kappa", None)
     prec = _precision_code(kw.get("precision", "complex64"))
     cdt = np.dtype(np.complex64 if prec == _lib.C64 else np.complex128)
     dev = default_device() if kw.get("device") is None else int(kw["device"])
