@@ -18,11 +18,13 @@
 #include <new>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "ssfm_amd.h"
 #include "ssfm_common.hpp"
 #include "ssfm_kernels.hpp"
+#include "ssfm_launch.hpp"
 #include "ssfm_medium.hpp"
 #include "ssfm_owned.hpp"
 #include "ssfm_schedule.hpp"
@@ -42,11 +44,6 @@ constexpr int kMaxTables = 4;
 // rows per k_freq workgroup: at least 64 threads where the row count allows (N1 >= 16 rows per batch entry)
 constexpr int freq_rows(int n2, int e) { return (n2 / e) >= 64 ? 1 : ((64 * e / n2) > 16 ? 16 : (64 * e / n2)); }
 
-template <typename K> hipError_t allow_lds(K kernel, size_t bytes) {
-    if (bytes <= 48 * 1024) return hipSuccess;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
-}
-
 // ----------------------------------------------------------------------------- launchers
 // E = points per thread: 16 (default) or 8 (twice the waves, half the registers, one more LDS exchange).
 template <typename T, int MODE, int N1, int E>
@@ -57,20 +54,12 @@ hipError_t launch_time_n1(dim3 grid, hipStream_t s, const TimeArgs<T>& a) {
     else if constexpr (U16 && MODE == TM_MID_L) return hipErrorInvalidValue;                    // (as a launch of its own: plans in the plain layout)
     else if constexpr (MODE == TM_MID_A && N1 != 128 && N1 != 256) return hipErrorInvalidValue;   // (the fused adaptive kernel: plans of 2^14 ... 2^18 samples)
     else {
-    constexpr size_t lds = (fft_nstages(N1, E) > 1 ? (size_t)N1 * C * sizeof(cx<T>) : 0) + (size_t)E * C * sizeof(cx<T>)
-                         + (size_t)fft_tw_lds_entries(N1, E) * sizeof(cx<T>);
+    constexpr size_t lds = col_pass_lds<T>(N1, C, E);
     if constexpr (MODE == TM_BEGIN || MODE == TM_MID || MODE == TM_END) {
-        if (a.scal != nullptr) {             // a capture run with the scalar log: the instantiation that keeps it (ssfm_kernels.hpp time_body, LOG)
-            static hipError_t attr_log = allow_lds(k_time<T, N1, C, E, MODE, U16, true>, lds);
-            if (attr_log != hipSuccess) return attr_log;
-            hipLaunchKernelGGL((k_time<T, N1, C, E, MODE, U16, true>), grid, dim3(N1 * C / E), lds, s, SSFM_TIME_KERNEL_ARGS(a));
-            return hipGetLastError();
-        }
+        if (a.scal != nullptr)               // a capture run with the scalar log: the instantiation that keeps it (ssfm_kernels.hpp time_body, LOG)
+            return launch_kernel<k_time<T, N1, C, E, MODE, U16, true>, lds>(grid, dim3(N1 * C / E), s, SSFM_TIME_KERNEL_ARGS(a));
     }
-    static hipError_t attr = allow_lds(k_time<T, N1, C, E, MODE, U16>, lds);
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL((k_time<T, N1, C, E, MODE, U16>), grid, dim3(N1 * C / E), lds, s, SSFM_TIME_KERNEL_ARGS(a));
-    return hipGetLastError();
+    return launch_kernel<k_time<T, N1, C, E, MODE, U16>, lds>(grid, dim3(N1 * C / E), s, SSFM_TIME_KERNEL_ARGS(a));
     }
 }
 template <typename T, int MODE, int E>
@@ -95,19 +84,11 @@ hipError_t launch_time(int N1, int batch, hipStream_t s, TimeArgs<T> a, int E) {
 template <typename T, int MODE, int N2, int E, bool U16>
 hipError_t launch_freq_u(int nrows, hipStream_t s, const FreqArgs<T>& a) {
     constexpr int ROWS = freq_rows(N2, E);
-    constexpr size_t lds = (fft_nstages(N2, E) > 1 ? (size_t)ROWS * row_lds_elems(N2, E) * sizeof(cx<T>) : 0)
-                         + (size_t)fft_tw_lds_entries(N2, E) * sizeof(cx<T>);
-    if constexpr (MODE == FM_FWD_ONLY || MODE == FM_INV_ONLY) {
-        static hipError_t attr_h = allow_lds(k_freq_half<T, N2, ROWS, E, MODE, U16>, lds);
-        if (attr_h != hipSuccess) return attr_h;
-        hipLaunchKernelGGL((k_freq_half<T, N2, ROWS, E, MODE, U16>), dim3(nrows / ROWS), dim3(ROWS * N2 / E), lds, s, SSFM_FREQ_KERNEL_ARGS(a));
-        return hipGetLastError();
-    } else {
-    static hipError_t attr = allow_lds(k_freq<T, N2, ROWS, E, MODE, U16>, lds);
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL((k_freq<T, N2, ROWS, E, MODE, U16>), dim3(nrows / ROWS), dim3(ROWS * N2 / E), lds, s, SSFM_FREQ_KERNEL_ARGS(a));
-    return hipGetLastError();
-    }
+    constexpr size_t lds = row_pass_lds<T>(N2, E, ROWS);
+    if constexpr (MODE == FM_FWD_ONLY || MODE == FM_INV_ONLY)
+        return launch_kernel<k_freq_half<T, N2, ROWS, E, MODE, U16>, lds>(dim3(nrows / ROWS), dim3(ROWS * N2 / E), s, SSFM_FREQ_KERNEL_ARGS(a));
+    else
+        return launch_kernel<k_freq<T, N2, ROWS, E, MODE, U16>, lds>(dim3(nrows / ROWS), dim3(ROWS * N2 / E), s, SSFM_FREQ_KERNEL_ARGS(a));
 }
 template <typename T, int MODE, int N2, int E>
 hipError_t launch_freq_n2(int nrows, hipStream_t s, const FreqArgs<T>& a) {
@@ -152,12 +133,7 @@ hipError_t launch_freq(int N2, int nrows, hipStream_t s, FreqArgs<T> a, int E) {
 template <int MODE, int N1, int E>
 hipError_t launch_time_h_n1(dim3 grid, hipStream_t s, const TimeArgs<double>& a) {
     constexpr int C = cols_per_tile<double>();
-    constexpr size_t lds = (fft_nstages(N1, E) > 1 ? (size_t)N1 * C * sizeof(cx<double>) : 0) + (size_t)E * C * sizeof(cx<double>)
-                         + (size_t)fft_tw_lds_entries(N1, E) * sizeof(cx<double>);
-    static hipError_t attr = allow_lds(k_time_h<double, N1, C, E, MODE>, lds);
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL((k_time_h<double, N1, C, E, MODE>), grid, dim3(N1 * C / E), lds, s, SSFM_TIME_KERNEL_ARGS(a));
-    return hipGetLastError();
+    return launch_kernel<k_time_h<double, N1, C, E, MODE>, col_pass_lds<double>(N1, C, E)>(grid, dim3(N1 * C / E), s, SSFM_TIME_KERNEL_ARGS(a));
 }
 constexpr bool line_half_shape(int N1, int N2, int E, int Ef) { return ((N1 == 256 && E == 8) || (N1 == 512 && E == 16)) && Ef == 16 && N2 >= 1024 && N2 <= 8192; }
 template <int MODE>
@@ -171,16 +147,14 @@ hipError_t launch_time_h(int N1, int batch, hipStream_t s, TimeArgs<double> a, i
 template <int N2>
 hipError_t launch_freq_h_n2(int nrows, hipStream_t s, const FreqArgs<double>& a, const int* done) {
     constexpr int E = 16, ROWS = freq_rows(N2, E);
-    constexpr size_t lds = (fft_nstages(N2, E) > 1 ? (size_t)ROWS * row_lds_elems(N2, E) * sizeof(cx<double>) : 0) + (size_t)fft_tw_lds_entries(N2, E) * sizeof(cx<double>);
-    static hipError_t attr = allow_lds(k_freq_h<double, N2, ROWS, E, FM_TABLE>, lds);
-    if (attr != hipSuccess) return attr;
+    constexpr auto kernel = &k_freq_h<double, N2, ROWS, E, FM_TABLE>;
+    constexpr size_t lds = row_pass_lds<double>(N2, E, ROWS);
+    const dim3 grid(nrows / ROWS), block(ROWS * N2 / E);
 #if SSFM_TRACE
-    hipLaunchKernelGGL((k_freq_h<double, N2, ROWS, E, FM_TABLE>), dim3(nrows / ROWS), dim3(ROWS * N2 / E), lds, s, a.F, a.tab, a.tw2, a.st, a.h, a.amp, a.inv_n, a.step, a.N1, a.rows, a.u16, done,
-                       a.trace, a.trace_slot);
+    return launch_kernel<kernel, lds>(grid, block, s, a.F, a.tab, a.tw2, a.st, a.h, a.amp, a.inv_n, a.step, a.N1, a.rows, a.u16, done, a.trace, a.trace_slot);
 #else
-    hipLaunchKernelGGL((k_freq_h<double, N2, ROWS, E, FM_TABLE>), dim3(nrows / ROWS), dim3(ROWS * N2 / E), lds, s, a.F, a.tab, a.tw2, a.st, a.h, a.amp, a.inv_n, a.step, a.N1, a.rows, a.u16, done);
+    return launch_kernel<kernel, lds>(grid, block, s, a.F, a.tab, a.tw2, a.st, a.h, a.amp, a.inv_n, a.step, a.N1, a.rows, a.u16, done);
 #endif
-    return hipGetLastError();
 }
 inline hipError_t launch_freq_h(int N2, int nrows, hipStream_t s, FreqArgs<double> a, const int* done = nullptr) {
     a.rows = nrows / a.N1;
@@ -231,26 +205,25 @@ template <typename T> constexpr bool small_supported(int n) {
     return n >= 256 && n <= (sizeof(T) == 4 ? 8192 : 4096) && (n & (n - 1)) == 0;
 }
 static_assert(kSmallTabs == kMaxTables, "k_small takes one table per cached step size");
-template <typename T, int N>
-hipError_t launch_small_n(int rows, hipStream_t s, const SmallArgs<T>& a) {
-    constexpr int E = small_points<T>(N);
-    constexpr size_t lds = (fft_nstages(N, E) > 1 ? (size_t)row_lds_elems(N, E) * sizeof(cx<T>) : 0) + (size_t)fft_tw_lds_entries(N, E) * sizeof(cx<T>);
-    static hipError_t attr = allow_lds(k_small<T, N, E>, lds);
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL((k_small<T, N, E>), dim3(rows), dim3(N / E), lds, s, a);
-    return hipGetLastError();
+// The line lengths of the one-workgroup engines, 256 ... MAXN: f(std::integral_constant<int, n>) for the one that n is
+template <int MAXN, typename F>
+hipError_t small_size(int n, F&& f) {
+    switch (n) {
+        case 256:  return f(std::integral_constant<int, 256>());
+        case 512:  return f(std::integral_constant<int, 512>());
+        case 1024: return f(std::integral_constant<int, 1024>());
+        case 2048: return f(std::integral_constant<int, 2048>());
+        case 4096: return f(std::integral_constant<int, 4096>());
+        case 8192: if constexpr (MAXN >= 8192) return f(std::integral_constant<int, 8192>()); else break;      // (complex64 k_small only)
+    }
+    return hipErrorInvalidValue;
 }
 template <typename T>
 hipError_t launch_small(int n, int rows, hipStream_t s, const SmallArgs<T>& a) {
-    switch (n) {
-        case 256:  return launch_small_n<T, 256>(rows, s, a);
-        case 512:  return launch_small_n<T, 512>(rows, s, a);
-        case 1024: return launch_small_n<T, 1024>(rows, s, a);
-        case 2048: return launch_small_n<T, 2048>(rows, s, a);
-        case 4096: return launch_small_n<T, 4096>(rows, s, a);
-        case 8192: if constexpr (sizeof(T) == 4) return launch_small_n<T, 8192>(rows, s, a); else break;
-    }
-    return hipErrorInvalidValue;
+    return small_size<(sizeof(T) == 4 ? 8192 : 4096)>(n, [&](auto size) {
+        constexpr int N = decltype(size)::value, E = small_points<T>(N);
+        return launch_kernel<k_small<T, N, E>, row_pass_lds<T>(N, E, 1)>(dim3(rows), dim3(N / E), s, a);
+    });
 }
 
 // ---- kernels around k_medium_chirp (chirp_medium below): a complex64 line, the chirp's phase reduced exactly in integers as in chirpz.hip
@@ -311,48 +284,23 @@ template <typename T> __global__ __launch_bounds__(256) void k_cm_post(cx<T>* __
 // but four wavefronts per workgroup hide less: fixed step 12.6 us per step at n = 2032 either way, adaptive 23.3 against 16.7 (eight exp(D~ h) per
 // thread and step instead of four).  So 8.
 template <typename T> constexpr int chirp_points(int n) { return small_points<T>(n); }
-template <typename T, int N>
-hipError_t launch_small_chirp_n(int rows, hipStream_t s, const SmallChirpArgs<T>& a) {
-    constexpr int E = chirp_points<T>(N);
-    constexpr size_t lds = (fft_nstages(N, E) > 1 ? (size_t)row_lds_elems(N, E) * sizeof(cx<T>) : 0) + (size_t)fft_tw_lds_entries(N, E) * sizeof(cx<T>) + (size_t)N * sizeof(cx<T>);
-    static_assert(lds <= 160 * 1024, "k_small_chirp: the line, its twiddles and H must fit the LDS");
-    static hipError_t attr = allow_lds(k_small_chirp<T, N, E>, lds);
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL((k_small_chirp<T, N, E>), dim3(rows), dim3(N / E), lds, s, a);
-    return hipGetLastError();
-}
 template <typename T>
 hipError_t launch_small_chirp(int n, int rows, hipStream_t s, const SmallChirpArgs<T>& a) {
-    switch (n) {
-        case 256:  return launch_small_chirp_n<T, 256>(rows, s, a);
-        case 512:  return launch_small_chirp_n<T, 512>(rows, s, a);
-        case 1024: return launch_small_chirp_n<T, 1024>(rows, s, a);
-        case 2048: return launch_small_chirp_n<T, 2048>(rows, s, a);
-        case 4096: return launch_small_chirp_n<T, 4096>(rows, s, a);
-    }
-    return hipErrorInvalidValue;
-}
-
-template <typename T, int N>
-hipError_t launch_small_chirp_adapt_n(int rows, hipStream_t s, const SmallChirpAdaptArgs<T>& a) {
-    constexpr int E = chirp_points<T>(N);
-    constexpr size_t lds = (fft_nstages(N, E) > 1 ? (size_t)row_lds_elems(N, E) * sizeof(cx<T>) : 0) + (size_t)fft_tw_lds_entries(N, E) * sizeof(cx<T>) + (size_t)N * sizeof(cx<T>);
-    static_assert(lds + 256 <= 160 * 1024, "k_small_chirp_adapt: the line, its twiddles and H must fit the LDS");
-    static hipError_t attr = allow_lds(k_small_chirp_adapt<T, N, E>, lds);
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL((k_small_chirp_adapt<T, N, E>), dim3(rows), dim3(N / E), lds, s, a);
-    return hipGetLastError();
+    return small_size<4096>(n, [&](auto size) {
+        constexpr int N = decltype(size)::value, E = chirp_points<T>(N);
+        constexpr size_t lds = row_pass_lds<T>(N, E, 1, N);
+        static_assert(lds <= 160 * 1024, "k_small_chirp: the line, its twiddles and H must fit the LDS");
+        return launch_kernel<k_small_chirp<T, N, E>, lds>(dim3(rows), dim3(N / E), s, a);
+    });
 }
 template <typename T>
 hipError_t launch_small_chirp_adapt(int n, int rows, hipStream_t s, const SmallChirpAdaptArgs<T>& a) {
-    switch (n) {
-        case 256:  return launch_small_chirp_adapt_n<T, 256>(rows, s, a);
-        case 512:  return launch_small_chirp_adapt_n<T, 512>(rows, s, a);
-        case 1024: return launch_small_chirp_adapt_n<T, 1024>(rows, s, a);
-        case 2048: return launch_small_chirp_adapt_n<T, 2048>(rows, s, a);
-        case 4096: return launch_small_chirp_adapt_n<T, 4096>(rows, s, a);
-    }
-    return hipErrorInvalidValue;
+    return small_size<4096>(n, [&](auto size) {
+        constexpr int N = decltype(size)::value, E = chirp_points<T>(N);
+        constexpr size_t lds = row_pass_lds<T>(N, E, 1, N);
+        static_assert(lds + 256 <= 160 * 1024, "k_small_chirp_adapt: the line, its twiddles and H must fit the LDS");
+        return launch_kernel<k_small_chirp_adapt<T, N, E>, lds>(dim3(rows), dim3(N / E), s, a);
+    });
 }
 
 // k_small_adapt: all rows of the plan in ONE workgroup (they share the step size); at most 512 threads, so that a thread
@@ -363,30 +311,15 @@ template <typename T> constexpr bool small_adapt_supported(int n, int rows) {
 template <typename T, int N, int ROWS>
 hipError_t launch_small_adapt_nr(hipStream_t s, const SmallAdaptArgs<T>& a) {
     constexpr int E = small_points<T>(N);
-    if constexpr (ROWS * N / E <= 512) {
-        constexpr size_t lds = (fft_nstages(N, E) > 1 ? (size_t)ROWS * row_lds_elems(N, E) * sizeof(cx<T>) : 0) + (size_t)fft_tw_lds_entries(N, E) * sizeof(cx<T>);
-        static hipError_t attr = allow_lds(k_small_adapt<T, N, E, ROWS>, lds);
-        if (attr != hipSuccess) return attr;
-        hipLaunchKernelGGL((k_small_adapt<T, N, E, ROWS>), dim3(1), dim3(ROWS * N / E), lds, s, a);
-        return hipGetLastError();
-    } else {
-        return hipErrorInvalidValue;
-    }
-}
-template <typename T, int N>
-hipError_t launch_small_adapt_n(int rows, hipStream_t s, const SmallAdaptArgs<T>& a) {
-    return rows == 1 ? launch_small_adapt_nr<T, N, 1>(s, a) : launch_small_adapt_nr<T, N, 2>(s, a);
+    if constexpr (ROWS * N / E <= 512) return launch_kernel<k_small_adapt<T, N, E, ROWS>, row_pass_lds<T>(N, E, ROWS)>(dim3(1), dim3(ROWS * N / E), s, a);
+    else return hipErrorInvalidValue;
 }
 template <typename T>
 hipError_t launch_small_adapt(int n, int rows, hipStream_t s, const SmallAdaptArgs<T>& a) {
-    switch (n) {
-        case 256:  return launch_small_adapt_n<T, 256>(rows, s, a);
-        case 512:  return launch_small_adapt_n<T, 512>(rows, s, a);
-        case 1024: return launch_small_adapt_n<T, 1024>(rows, s, a);
-        case 2048: return launch_small_adapt_n<T, 2048>(rows, s, a);
-        case 4096: return launch_small_adapt_n<T, 4096>(rows, s, a);
-    }
-    return hipErrorInvalidValue;
+    return small_size<4096>(n, [&](auto size) {
+        constexpr int N = decltype(size)::value;
+        return rows == 1 ? launch_small_adapt_nr<T, N, 1>(s, a) : launch_small_adapt_nr<T, N, 2>(s, a);
+    });
 }
 
 // A host thread that enqueues ONE lane's launches.  The host issues a launch per ~3.1 us, a 2^20 x 2 step is four launches per
@@ -1313,13 +1246,12 @@ template <typename T> struct PlanT : PlanBase {
         HIP_TRY(hipStreamSynchronize(stream));
         if (medium_err_host[0] == 0u && medium_err_host[1] == 0u) return SSFM_OK;
         medium_err_host[0] = medium_err_host[1] = 0u;
-        medium_ok = false;
-        ++fallbacks;
+        medium_gave_up(medium_ok);                 // (ahead of the repeat: it must not choose this engine again)
         HIP_TRY(hipMemcpyAsync(F, fused_backup, sizeof(cx<T>) * n * batch, hipMemcpyDeviceToDevice, stream));
         const std::vector<T> sched = medium_sched;
         if (int rc = propagate_fixed(medium_gamma, sched.data(), (int64_t)sched.size(), nullptr)) return rc;
         HIP_TRY(hipStreamSynchronize(stream));
-        last_fell_back = 1;
+        last_fell_back = 1;                        // (again: the repeat is a run of its own and cleared it)
         return SSFM_OK;
     }
     // the XCDs a launch's workgroups are dealt to (probe launch, once per device), and this plan's among them: plans take turns
@@ -1333,6 +1265,49 @@ template <typename T> struct PlanT : PlanBase {
         for (int b = 0; b < 32; ++b)
             if ((mask >> b) & 1u) { if (k == 0) { medium_xcc = b; break; } --k; }
         return SSFM_OK;
+    }
+    // ---- the host side of a launch on one XCD, for the four engines that are one (k_medium, k_medium_adapt, k_medium_chirp, k_medium_chirp_adapt)
+    // Ahead of the launch: `sets` of the two sets of meeting words zeroed on the plan's stream (a launch meets in one set), the plan's XCD, and what
+    // the four argument structs share filled in: the plan's fields and twiddles, where and how long the workgroups of `rows` rows meet.
+    template <typename Args>
+    int medium_prepare(Args& a, int rows, int sets) {
+        if (int rc = ensure_medium_state()) return rc;
+        HIP_TRY(hipMemsetAsync(medium_st, 0, sizeof(unsigned long long) * sets * kSet, stream));
+        if (int rc = pick_xcc()) return rc;
+        a.F = F; a.Y = Y; a.P = P; a.twA = twA; a.twB = twB; a.tw1 = tw1; a.tw2 = tw2;
+        medium_meet_in(a, 0);
+        a.patience = medium_patience;
+        a.xcc = (unsigned)medium_xcc;
+        a.rows = rows; a.nblk = (unsigned)((N2 / cols_per_tile<T>()) * rows); a.Qf = N2 / Ef;
+        return SSFM_OK;
+    }
+    // a launch's set of meeting words: the shards and flag words, then the error word, then the ticket counter
+    template <typename Args>
+    void medium_meet_in(Args& a, int set) {
+        a.bar = medium_st + set * kSet;
+        a.error = reinterpret_cast<unsigned*>(a.bar + kBarShards + kBarWords);
+    }
+    // Behind the launch, on stream `s`: its error word (not zero: its workgroups did not meet within the patience) ...
+    template <typename Args>
+    int medium_verdict(const Args& a, unsigned* gave_up, hipStream_t s) {
+        HIP_TRY(hipMemcpyAsync(gave_up, a.error, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        return SSFM_OK;
+    }
+    // ... and of an adaptive run also the step state's error word (the hand-over of the maxima) and where the run stands; waits for all three
+    template <typename Args>
+    int medium_adapt_verdict(const Args& a, unsigned gave_up[2], StepState<T>* now) {
+        const char* state = reinterpret_cast<const char*>(st.get());
+        if (int rc = medium_verdict(a, &gave_up[0], stream)) return rc;
+        HIP_TRY(hipMemcpyAsync(&gave_up[1], state + offsetof(AdaptState<T>, error), sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipMemcpyAsync(now, state + offsetof(AdaptState<T>, cur), sizeof(*now), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        return SSFM_OK;
+    }
+    // A run whose workgroups did not meet: the plan keeps off that engine from here on (`engine_ok`: medium_ok or medium_adapt_ok) and says so
+    void medium_gave_up(bool& engine_ok) {
+        engine_ok = false;
+        ++fallbacks;
+        last_fell_back = 1;
     }
     // fixed-step runs of a dual-polarisation plan of long rows: one launch per row (see run_medium)
     bool medium_rows_split() const { return medium_split_ok && batch == 2 && n >= (1ll << 16); }
@@ -1348,19 +1323,12 @@ template <typename T> struct PlanT : PlanBase {
         for (size_t i = 0; i < distinct.size(); ++i) { const T xr = op_re0 * distinct[i]; a.amp[i] = (T)std::exp((double)xr) * inv_n(); }
         if (int rc = upload_schedule(sch)) return rc;
         if (int rc = backup_field()) return rc;                  // for a repeat on the two-kernel engine
-        if (int rc = ensure_medium_state()) return rc;
-        HIP_TRY(hipMemsetAsync(medium_st, 0, sizeof(unsigned long long) * 2 * kSet, stream));
-        a.F = F; a.Y = Y; a.P = P; a.twA = twA; a.twB = twB; a.tw1 = tw1; a.tw2 = tw2;
-        a.hs = d_hs; a.which = d_which(sch);
-        a.bar = medium_st; a.error = reinterpret_cast<unsigned*>(medium_st + kBarShards + kBarWords); a.patience = medium_patience;
-        if (int rc = pick_xcc()) return rc;
-        a.xcc = (unsigned)medium_xcc;
-        a.gamma = gamma; a.inv_n = inv_n(); a.nsteps = (int)nsteps; a.Qf = N2 / Ef;
         // The rows of a fixed-step run share nothing: a dual-polarisation plan of long rows (2^16 samples and more) runs them as TWO launches, each
         // on an XCD and a stream of its own (2^16 x 2: 8.3 against 9.25 us per step in one launch; 2^17 x 2 only fits this way)
         const bool two = medium_rows_split();
-        a.rows = two ? 1 : batch;
-        a.nblk = (unsigned)((N2 / cols_per_tile<T>()) * a.rows);
+        if (int rc = medium_prepare(a, two ? 1 : batch, 2)) return rc;        // (both sets of meeting words: the second launch has its own)
+        a.hs = d_hs; a.which = d_which(sch);
+        a.gamma = gamma; a.inv_n = inv_n(); a.nsteps = (int)nsteps;
         if (two) {
             if (!medium_stream2) {
                 HIP_TRY(hipStreamCreateWithFlags(medium_stream2.out(), hipStreamNonBlocking));
@@ -1371,12 +1339,13 @@ template <typename T> struct PlanT : PlanBase {
         }
         ++last_launches;
         HIP_TRY(launch_medium(N1, N2, phase, (int)a.nblk, medium_xccs, stream, a));
-        HIP_TRY(hipMemcpyAsync(medium_err_host, a.error, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+        // (the run is asynchronous: the words land in pinned memory and finish_medium looks at them when the plan is next used)
+        if (int rc = medium_verdict(a, medium_err_host, stream)) return rc;
         medium_err_host[1] = 0u;
         if (two) {
             MediumArgs<T> b = a;
             b.F = F + n; b.Y = Y + n; b.P = P + n;
-            b.bar = medium_st + kSet; b.error = reinterpret_cast<unsigned*>(medium_st + kSet + kBarShards + kBarWords);
+            medium_meet_in(b, 1);
             // the next XCD of the device's set
             const unsigned mask = xcc_mask(device);
             unsigned nx = (unsigned)medium_xcc;
@@ -1384,7 +1353,7 @@ template <typename T> struct PlanT : PlanBase {
             b.xcc = medium_xccs > 1 ? nx : (unsigned)medium_xcc;
             ++last_launches;
             HIP_TRY(launch_medium(N1, N2, phase, (int)b.nblk, medium_xccs, medium_stream2, b));
-            HIP_TRY(hipMemcpyAsync(medium_err_host + 1, b.error, sizeof(unsigned), hipMemcpyDeviceToHost, medium_stream2));
+            if (int rc = medium_verdict(b, medium_err_host + 1, medium_stream2)) return rc;
             HIP_TRY(hipEventRecord(medium_ev2, medium_stream2));
             HIP_TRY(hipStreamWaitEvent(stream, medium_ev2, 0));
         }
@@ -2144,22 +2113,15 @@ template <typename T> struct PlanT : PlanBase {
                     hipLaunchKernelGGL(k_absmax<T>, dim3(1024), dim3(256), 0, stream, (const cx<T>*)F, (long long)n * batch, st);
                     hipLaunchKernelGGL(k_step_control<T>, dim3(1), dim3(64), 0, stream, st, zlog, 0, 0, 0);
                     last_launches += 2;
-                    if (int rc = ensure_medium_state()) return rc;
-                    HIP_TRY(hipMemsetAsync(medium_st, 0, sizeof(unsigned long long) * kSet, stream));
-                    if (int rc = pick_xcc()) return rc;
-                    MediumAdaptArgs<T> ma;
-                    ma.F = F; ma.Y = Y; ma.P = P; ma.twA = twA; ma.twB = twB; ma.tw1 = tw1; ma.tw2 = tw2; ma.D = dperm; ma.st = st; ma.zlog = zlog;
-                    ma.bar = medium_st; ma.error = reinterpret_cast<unsigned*>(medium_st + kBarShards + kBarWords); ma.patience = medium_patience;
-                    ma.xcc = (unsigned)medium_xcc; ma.nblk = (unsigned)((N2 / cols_per_tile<T>()) * batch);
-                    ma.gamma = keep.gamma; ma.inv_n = inv_n(); ma.rows = batch; ma.Qf = N2 / Ef;
+                    MediumAdaptArgs<T> ma;                              // (no memset: the struct has no padding and every member is assigned)
+                    if (int rc = medium_prepare(ma, batch, 1)) return rc;        // (one launch for all rows: the first set of meeting words)
+                    ma.D = dperm; ma.st = st; ma.zlog = zlog;
+                    ma.gamma = keep.gamma; ma.inv_n = inv_n();
                     ++last_launches;
                     HIP_TRY(launch_medium_adapt(N1, N2, (int)ma.nblk, medium_xccs, stream, ma));
-                    unsigned gave_up = 0, gave_up2 = 0;
-                    HIP_TRY(hipMemcpyAsync(&gave_up, ma.error, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-                    HIP_TRY(hipMemcpyAsync(&gave_up2, reinterpret_cast<const char*>(st.get()) + offsetof(AdaptState<T>, error), sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-                    HIP_TRY(hipMemcpyAsync(&ar.now, reinterpret_cast<const char*>(st.get()) + offsetof(AdaptState<T>, cur), sizeof(ar.now), hipMemcpyDeviceToHost, stream));
-                    HIP_TRY(hipStreamSynchronize(stream));
-                    if (!gave_up && !gave_up2) {
+                    unsigned gave_up[2] = {0u, 0u};
+                    if (int rc = medium_adapt_verdict(ma, gave_up, &ar.now)) return rc;
+                    if (!gave_up[0] && !gave_up[1]) {
                         ar.deferred = false;
                         last_engine = SSFM_ENGINE_MEDIUM_ADAPT;
                         if (steps_total) *steps_total = ar.now.steps;
@@ -2167,9 +2129,7 @@ template <typename T> struct PlanT : PlanBase {
                         return SSFM_OK;
                     }
                     // part of the grid never ran beside the rest: the same run on the chunked engine, which this plan then keeps to
-                    medium_adapt_ok = false;
-                    last_fell_back = 1;
-                    ++fallbacks;
+                    medium_gave_up(medium_adapt_ok);
                     HIP_TRY(hipMemcpyAsync(F, fused_backup, fb, hipMemcpyDeviceToDevice, stream));
                 }
             } else if (keep.medium) {
@@ -2737,7 +2697,6 @@ template <typename T> struct PlanT : PlanBase {
         const std::vector<T>& distinct = sch.distinct;
         last_launches = 0;
         if (int rc = chirp_medium_tables(nn)) return rc;
-        const long long blocks = (long long)(N2 / cols_per_tile<T>()) * batch;
         cx<T>* A = static_cast<cx<T>*>(A_);
         const cx<T>* chirp = static_cast<const cx<T>*>(chirp_);
         const cx<T>* Dt = static_cast<const cx<T>*>(Dt_);
@@ -2752,30 +2711,25 @@ template <typename T> struct PlanT : PlanBase {
             ++last_launches;
         }
         if (int rc = upload_schedule(sch)) return rc;
-        if (int rc = ensure_medium_state()) return rc;
-        HIP_TRY(hipMemsetAsync(medium_st, 0, sizeof(unsigned long long) * 2 * kSet, stream));
-        a.F = F; a.Y = Y; a.P = P; a.twA = twA; a.twB = twB; a.tw1 = tw1; a.tw2 = tw2;
+        // (both sets of meeting words, though the launch meets in the first only: one would do, but the size of the fill shows in a trace of the run
+        // and stays as it was.  The plan's XCD is picked already, chirp_medium_tables asks for it: pick_xcc in there returns at once)
+        if (int rc = medium_prepare(a, batch, 2)) return rc;
         a.H[0] = xfer_tab[0]; a.H[1] = xfer_tab[1];
         a.hs = d_hs; a.which = d_which(sch);
-        a.bar = medium_st; a.error = reinterpret_cast<unsigned*>(medium_st + kBarShards + kBarWords); a.patience = medium_patience;
-        a.xcc = (unsigned)medium_xcc;
-        a.gamma = (T)gamma; a.n = (int)nn; a.nsteps = (int)nsteps; a.rows = batch; a.Qf = N2 / Ef;
-        a.nblk = (unsigned)blocks;
+        a.gamma = (T)gamma; a.n = (int)nn; a.nsteps = (int)nsteps;
         const unsigned gA = (unsigned)std::min<long long>((n * batch + 255) / 256, 4096);
         hipLaunchKernelGGL(k_cm_pre<T>, dim3(gA), dim3(256), 0, stream, (const cx<T>*)A, chirp, F, (long long)nn, (long long)n, batch);
         HIP_TRY(launch_medium_chirp(N1, N2, (int)a.nblk, medium_xccs, stream, a));
         hipLaunchKernelGGL(k_cm_post<T>, dim3(gA), dim3(256), 0, stream, A, chirp, (const cx<T>*)F, (long long)nn, (long long)n, batch, (const unsigned*)a.error);
         HIP_TRY(hipGetLastError());
         last_launches += 3;
-        HIP_TRY(hipMemcpyAsync(medium_err_host, a.error, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
+        if (int rc = medium_verdict(a, medium_err_host, stream)) return rc;
+        HIP_TRY(hipStreamSynchronize(stream));           // (a synchronous call: the verdict is read here, not in finish_medium)
         last_engine = SSFM_ENGINE_CHIRP_MEDIUM;
         last_fell_back = 0;
         if (medium_err_host[0] != 0u) {
             medium_err_host[0] = 0u;
-            medium_ok = false;
-            ++fallbacks;
-            last_fell_back = 1;
+            medium_gave_up(medium_ok);                   // (the fixed-step engine's flag: k_medium_chirp is k_medium's schedule around other row passes)
             return fail(SSFM_ERR_UNSUPPORTED, "ssfm_chirp_medium: the launch's workgroups did not meet within the patience; the field is unchanged");
         }
         return SSFM_OK;
@@ -2799,15 +2753,11 @@ template <typename T> struct PlanT : PlanBase {
         if (int rc = upload_adapt_state((T)gamma_d, (T)length, (T)phi_max, (int)max_steps)) return rc;
         hipLaunchKernelGGL(k_absmax<T>, dim3(256), dim3(256), 0, stream, (const cx<T>*)A, (long long)nn * batch, st);
         hipLaunchKernelGGL(k_step_control<T>, dim3(1), dim3(64), 0, stream, st, zlog, 0, 0, 0);
-        if (int rc = ensure_medium_state()) return rc;
-        HIP_TRY(hipMemsetAsync(medium_st, 0, sizeof(unsigned long long) * kSet, stream));
         MediumChirpAdaptArgs<T> a;
         std::memset(&a, 0, sizeof(a));
-        a.F = F; a.Y = Y; a.P = P; a.twA = twA; a.twB = twB; a.tw1 = tw1; a.tw2 = tw2;
+        if (int rc = medium_prepare(a, batch, 1)) return rc;             // (as adaptive_run; the plan's XCD is picked already: chirp_medium_tables asks for it)
         a.H[0] = xfer_tab[0]; a.H[1] = xfer_tab[1]; a.Dt = static_cast<const cx<T>*>(Dt_); a.st = st; a.zlog = zlog;
-        a.bar = medium_st; a.error = reinterpret_cast<unsigned*>(medium_st + kBarShards + kBarWords); a.patience = medium_patience;
-        a.xcc = (unsigned)medium_xcc; a.nblk = (unsigned)blocks;
-        a.gamma = (T)gamma_d; a.inv_len = (T)(1.0 / (double)nn); a.n = (int)nn; a.rows = batch; a.Qf = N2 / Ef;
+        a.gamma = (T)gamma_d; a.inv_len = (T)(1.0 / (double)nn); a.n = (int)nn;
         const unsigned gA = (unsigned)std::min<long long>((n * batch + 255) / 256, 4096);
         hipLaunchKernelGGL(k_cm_pre<T>, dim3(gA), dim3(256), 0, stream, (const cx<T>*)A, chirp, F, (long long)nn, (long long)n, batch);
         HIP_TRY(launch_medium_chirp_adapt(N1, N2, (int)a.nblk, medium_xccs, stream, a));
@@ -2815,17 +2765,12 @@ template <typename T> struct PlanT : PlanBase {
         // -- the post kernel -- only when both are clear and the run is done)
         unsigned gave_up[2] = {0u, 0u};
         StepState<T> fin = {};
-        HIP_TRY(hipMemcpyAsync(&gave_up[0], a.error, sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipMemcpyAsync(&gave_up[1], reinterpret_cast<const char*>(st.get()) + offsetof(AdaptState<T>, error), sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipMemcpyAsync(&fin, reinterpret_cast<const char*>(st.get()) + offsetof(AdaptState<T>, cur), sizeof(fin), hipMemcpyDeviceToHost, stream));
-        HIP_TRY(hipStreamSynchronize(stream));
+        if (int rc = medium_adapt_verdict(a, gave_up, &fin)) return rc;
         last_launches += 5;
         last_engine = SSFM_ENGINE_CHIRP_MEDIUM_ADAPT;
         last_fell_back = 0;
         if (gave_up[0] != 0u || gave_up[1] != 0u || !fin.done) {
-            medium_adapt_ok = false;
-            ++fallbacks;
-            last_fell_back = 1;
+            medium_gave_up(medium_adapt_ok);
             return fail(SSFM_ERR_UNSUPPORTED, "ssfm_chirp_medium_adapt: the launch's workgroups did not meet within the patience; the field is unchanged");
         }
         hipLaunchKernelGGL(k_cm_post<T>, dim3(gA), dim3(256), 0, stream, A, chirp, (const cx<T>*)F, (long long)nn, (long long)n, batch, (const unsigned*)a.error);

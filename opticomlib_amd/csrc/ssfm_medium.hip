@@ -2,124 +2,59 @@
 // translation unit of its own (its four shapes x two operator-table kinds are a minute of compile time).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <mutex>
 
 #include "ssfm_kernels.hpp"
+#include "ssfm_launch.hpp"
 #include "ssfm_medium.hpp"
 
 namespace ssfm {
 namespace {
-template <int N1, int N2, int FMODE>
-hipError_t launch_shape(int nblk, int xccs, hipStream_t s, const MediumArgs<float>& a) {
-    using T = float;
-    constexpr int E = 8, C = 16, ROWS = N1 * C / N2;
-    constexpr size_t lds_t = (fft_nstages(N1, E) > 1 ? (size_t)N1 * C * sizeof(cx<T>) : 0) + (size_t)E * C * sizeof(cx<T>)
-                           + (size_t)fft_tw_lds_entries(N1, E) * sizeof(cx<T>);
-    constexpr size_t lds_f = (fft_nstages(N2, E) > 1 ? (size_t)ROWS * row_lds_elems(N2, E) * sizeof(cx<T>) : 0)
-                           + (size_t)fft_tw_lds_entries(N2, E) * sizeof(cx<T>);
-    constexpr size_t lds = lds_t > lds_f ? lds_t : lds_f;
-    static hipError_t attr = lds <= 48 * 1024 ? hipSuccess
-        : hipFuncSetAttribute(reinterpret_cast<const void*>(k_medium<T, N1, N2, E, FMODE>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL((k_medium<T, N1, N2, E, FMODE>), dim3(xccs * nblk), dim3(N1 * C / E), lds, s, a);
-    return hipGetLastError();
-}
-template <int FMODE> hipError_t launch_mode(int N1, int N2, int nblk, int xccs, hipStream_t s, const MediumArgs<float>& a) {
-    if (N1 == 64 && N2 == 64) return launch_shape<64, 64, FMODE>(nblk, xccs, s, a);
-    if (N1 == 64 && N2 == 128) return launch_shape<64, 128, FMODE>(nblk, xccs, s, a);
-    if (N1 == 128 && N2 == 128) return launch_shape<128, 128, FMODE>(nblk, xccs, s, a);
-    if (N1 == 128 && N2 == 256) return launch_shape<128, 256, FMODE>(nblk, xccs, s, a);
-    if (N1 == 256 && N2 == 256) return launch_shape<256, 256, FMODE>(nblk, xccs, s, a);
-    if (N1 == 256 && N2 == 512) return launch_shape<256, 512, FMODE>(nblk, xccs, s, a);
-    return hipErrorInvalidValue;
+// The four kernels: what each takes and its instantiation for a shape
+template <int FMODE> struct Fixed {
+    using Args = MediumArgs<float>;
+    template <int N1, int N2> static constexpr auto kernel = &k_medium<float, N1, N2, 8, FMODE>;
+};
+struct Adapt {
+    using Args = MediumAdaptArgs<float>;
+    template <int N1, int N2> static constexpr auto kernel = &k_medium_adapt<float, N1, N2, 8>;
+};
+struct Chirp {
+    using Args = MediumChirpArgs<float>;
+    template <int N1, int N2> static constexpr auto kernel = &k_medium_chirp<float, N1, N2, 8>;
+};
+struct ChirpAdapt {
+    using Args = MediumChirpAdaptArgs<float>;
+    template <int N1, int N2> static constexpr auto kernel = &k_medium_chirp_adapt<float, N1, N2, 8>;
+};
+
+// N1 column points x N2 row points, 8 points per thread, 16 columns per tile: a workgroup does column passes and row passes in the same LDS
+constexpr int kShapes[6][2] = {{64, 64}, {64, 128}, {128, 128}, {128, 256}, {256, 256}, {256, 512}};
+
+template <typename K, size_t I = 0>
+hipError_t launch_shape(int N1, int N2, int nblk, int xccs, hipStream_t s, const typename K::Args& a) {
+    if constexpr (I == sizeof(kShapes) / sizeof(kShapes[0])) return hipErrorInvalidValue;
+    else {
+        constexpr int S1 = kShapes[I][0], S2 = kShapes[I][1], E = 8, C = 16, ROWS = S1 * C / S2;
+        constexpr size_t lds = std::max(col_pass_lds<float>(S1, C, E), row_pass_lds<float>(S2, E, ROWS));
+        if (N1 == S1 && N2 == S2) return launch_kernel<K::template kernel<S1, S2>, lds>(dim3(xccs * nblk), dim3(S1 * C / E), s, a);
+        return launch_shape<K, I + 1>(N1, N2, nblk, xccs, s, a);
+    }
 }
 }  // namespace
 
-namespace {
-template <int N1, int N2>
-hipError_t launch_adapt_shape(int nblk, int xccs, hipStream_t s, const MediumAdaptArgs<float>& a) {
-    using T = float;
-    constexpr int E = 8, C = 16, ROWS = N1 * C / N2;
-    constexpr size_t lds_t = (fft_nstages(N1, E) > 1 ? (size_t)N1 * C * sizeof(cx<T>) : 0) + (size_t)E * C * sizeof(cx<T>)
-                           + (size_t)fft_tw_lds_entries(N1, E) * sizeof(cx<T>);
-    constexpr size_t lds_f = (fft_nstages(N2, E) > 1 ? (size_t)ROWS * row_lds_elems(N2, E) * sizeof(cx<T>) : 0)
-                           + (size_t)fft_tw_lds_entries(N2, E) * sizeof(cx<T>);
-    constexpr size_t lds = lds_t > lds_f ? lds_t : lds_f;
-    static hipError_t attr = lds <= 48 * 1024 ? hipSuccess
-        : hipFuncSetAttribute(reinterpret_cast<const void*>(k_medium_adapt<T, N1, N2, E>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL((k_medium_adapt<T, N1, N2, E>), dim3(xccs * nblk), dim3(N1 * C / E), lds, s, a);
-    return hipGetLastError();
+bool medium_shape(int N1, int N2) {
+    for (const auto& sh : kShapes)
+        if (N1 == sh[0] && N2 == sh[1]) return true;
+    return false;
 }
-}  // namespace
-hipError_t launch_medium_adapt(int N1, int N2, int nblk, int xccs, hipStream_t s, const MediumAdaptArgs<float>& a) {
-    if (N1 == 64 && N2 == 64) return launch_adapt_shape<64, 64>(nblk, xccs, s, a);
-    if (N1 == 64 && N2 == 128) return launch_adapt_shape<64, 128>(nblk, xccs, s, a);
-    if (N1 == 128 && N2 == 128) return launch_adapt_shape<128, 128>(nblk, xccs, s, a);
-    if (N1 == 128 && N2 == 256) return launch_adapt_shape<128, 256>(nblk, xccs, s, a);
-    if (N1 == 256 && N2 == 256) return launch_adapt_shape<256, 256>(nblk, xccs, s, a);
-    if (N1 == 256 && N2 == 512) return launch_adapt_shape<256, 512>(nblk, xccs, s, a);
-    return hipErrorInvalidValue;
-}
-
-namespace {
-template <int N1, int N2>
-hipError_t launch_chirp_shape(int nblk, int xccs, hipStream_t s, const MediumChirpArgs<float>& a) {
-    using T = float;
-    constexpr int E = 8, C = 16, ROWS = N1 * C / N2;
-    constexpr size_t lds_t = (fft_nstages(N1, E) > 1 ? (size_t)N1 * C * sizeof(cx<T>) : 0) + (size_t)E * C * sizeof(cx<T>)
-                           + (size_t)fft_tw_lds_entries(N1, E) * sizeof(cx<T>);
-    constexpr size_t lds_f = (fft_nstages(N2, E) > 1 ? (size_t)ROWS * row_lds_elems(N2, E) * sizeof(cx<T>) : 0)
-                           + (size_t)fft_tw_lds_entries(N2, E) * sizeof(cx<T>);
-    constexpr size_t lds = lds_t > lds_f ? lds_t : lds_f;
-    static hipError_t attr = lds <= 48 * 1024 ? hipSuccess
-        : hipFuncSetAttribute(reinterpret_cast<const void*>(k_medium_chirp<T, N1, N2, E>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL((k_medium_chirp<T, N1, N2, E>), dim3(xccs * nblk), dim3(N1 * C / E), lds, s, a);
-    return hipGetLastError();
-}
-}  // namespace
-hipError_t launch_medium_chirp(int N1, int N2, int nblk, int xccs, hipStream_t s, const MediumChirpArgs<float>& a) {
-    if (N1 == 64 && N2 == 64) return launch_chirp_shape<64, 64>(nblk, xccs, s, a);
-    if (N1 == 64 && N2 == 128) return launch_chirp_shape<64, 128>(nblk, xccs, s, a);
-    if (N1 == 128 && N2 == 128) return launch_chirp_shape<128, 128>(nblk, xccs, s, a);
-    if (N1 == 128 && N2 == 256) return launch_chirp_shape<128, 256>(nblk, xccs, s, a);
-    if (N1 == 256 && N2 == 256) return launch_chirp_shape<256, 256>(nblk, xccs, s, a);
-    if (N1 == 256 && N2 == 512) return launch_chirp_shape<256, 512>(nblk, xccs, s, a);
-    return hipErrorInvalidValue;
-}
-
-namespace {
-template <int N1, int N2>
-hipError_t launch_chirp_adapt_shape(int nblk, int xccs, hipStream_t s, const MediumChirpAdaptArgs<float>& a) {
-    using T = float;
-    constexpr int E = 8, C = 16, ROWS = N1 * C / N2;
-    constexpr size_t lds_t = (fft_nstages(N1, E) > 1 ? (size_t)N1 * C * sizeof(cx<T>) : 0) + (size_t)E * C * sizeof(cx<T>)
-                           + (size_t)fft_tw_lds_entries(N1, E) * sizeof(cx<T>);
-    constexpr size_t lds_f = (fft_nstages(N2, E) > 1 ? (size_t)ROWS * row_lds_elems(N2, E) * sizeof(cx<T>) : 0)
-                           + (size_t)fft_tw_lds_entries(N2, E) * sizeof(cx<T>);
-    constexpr size_t lds = lds_t > lds_f ? lds_t : lds_f;
-    static hipError_t attr = lds <= 48 * 1024 ? hipSuccess
-        : hipFuncSetAttribute(reinterpret_cast<const void*>(k_medium_chirp_adapt<T, N1, N2, E>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (attr != hipSuccess) return attr;
-    hipLaunchKernelGGL((k_medium_chirp_adapt<T, N1, N2, E>), dim3(xccs * nblk), dim3(N1 * C / E), lds, s, a);
-    return hipGetLastError();
-}
-}  // namespace
-hipError_t launch_medium_chirp_adapt(int N1, int N2, int nblk, int xccs, hipStream_t s, const MediumChirpAdaptArgs<float>& a) {
-    if (N1 == 64 && N2 == 64) return launch_chirp_adapt_shape<64, 64>(nblk, xccs, s, a);
-    if (N1 == 64 && N2 == 128) return launch_chirp_adapt_shape<64, 128>(nblk, xccs, s, a);
-    if (N1 == 128 && N2 == 128) return launch_chirp_adapt_shape<128, 128>(nblk, xccs, s, a);
-    if (N1 == 128 && N2 == 256) return launch_chirp_adapt_shape<128, 256>(nblk, xccs, s, a);
-    if (N1 == 256 && N2 == 256) return launch_chirp_adapt_shape<256, 256>(nblk, xccs, s, a);
-    if (N1 == 256 && N2 == 512) return launch_chirp_adapt_shape<256, 512>(nblk, xccs, s, a);
-    return hipErrorInvalidValue;
-}
-
-bool medium_shape(int N1, int N2) { return (N1 == 64 && (N2 == 64 || N2 == 128)) || (N1 == 128 && (N2 == 128 || N2 == 256)) || (N1 == 256 && (N2 == 256 || N2 == 512)); }
-
+// (the kernels stand in the code object in the order in which these name them)
+hipError_t launch_medium_adapt(int N1, int N2, int nblk, int xccs, hipStream_t s, const MediumAdaptArgs<float>& a) { return launch_shape<Adapt>(N1, N2, nblk, xccs, s, a); }
+hipError_t launch_medium_chirp(int N1, int N2, int nblk, int xccs, hipStream_t s, const MediumChirpArgs<float>& a) { return launch_shape<Chirp>(N1, N2, nblk, xccs, s, a); }
+hipError_t launch_medium_chirp_adapt(int N1, int N2, int nblk, int xccs, hipStream_t s, const MediumChirpAdaptArgs<float>& a) { return launch_shape<ChirpAdapt>(N1, N2, nblk, xccs, s, a); }
 hipError_t launch_medium(int N1, int N2, bool phase_tables, int nblk, int xccs, hipStream_t s, const MediumArgs<float>& a) {
-    return phase_tables ? launch_mode<FM_PHASE>(N1, N2, nblk, xccs, s, a) : launch_mode<FM_TABLE>(N1, N2, nblk, xccs, s, a);
+    return phase_tables ? launch_shape<Fixed<FM_PHASE>>(N1, N2, nblk, xccs, s, a) : launch_shape<Fixed<FM_TABLE>>(N1, N2, nblk, xccs, s, a);
 }
 
 namespace {

@@ -333,6 +333,29 @@ def test_any_length_run_driven_from_c_against_the_host_loop(n, monkeypatch):
     assert within(oa.FIBER(x1, **kw).signal, ref, 1e-8)  # (the complex128 line queued from C)
 
 
+@pytest.mark.parametrize("precision", ["complex64", "complex128"])
+@pytest.mark.parametrize("n", [100, 200, 500, 1016, 2032])
+def test_any_length_one_launch_line_of_every_length_against_oracle(n, precision, monkeypatch):
+    """The one-workgroup chirp-z kernels (k_small_chirp, k_small_chirp_adapt) on every line length they are built for -- 256, 512, 1024, 2048, 4096 points for
+    100, 200, 500, 1016, 2032 samples -- in both precisions: two rows, a fixed run of 12 steps and an adaptive run of 15 to 19, against the float64 restatement
+    of the same call at the bound of the run's step count.  The plan of the line says which engine ran: a run that took another one fails here."""
+    for k in ("SSFM_SMALL", "SSFM_CHIRP_SMALL", "SSFM_CHIRP_LOOP", "SSFM_FUSED_PATIENCE_TICKS", "SSFM_E", "SSFM_EF"):
+        monkeypatch.delenv(k, raising=False)
+    oa.devices.release_plans()                  # (a plan reads its knobs when it is made)
+    gv(**workloads.BENCH_GV)
+    a = workloads.qpsk_field(1 << 12, seed=5, power_w=8e-3)[:, :n]
+    x = optical_signal(a)
+    M = 1 << (2 * n - 2).bit_length()
+    for kw, engine in ((dict(length=6.0, h=0.5, **workloads.SMF), "chirp_small"), (dict(length=3.0, phi_max=0.004, **workloads.SMF), "chirp_small_adaptive")):
+        y = oa.FIBER(x, precision=precision, **kw).signal
+        info = oa.devices.get_plan(M, 2, _lib.C64 if precision == "complex64" else _lib.C128, 0).last_run_info()
+        assert info["engine"] == engine and not info["fell_back"], (info, kw)
+        assert y.dtype == np.dtype(precision) and y.shape == a.shape
+        ns = len(orc.fiber_c64(a, gv.dt, return_steps=True, **kw)[0]) - 1
+        assert 10 <= ns <= 20, ns
+        assert within(y, orc.fiber_c128(a, gv.dt, **kw), steps=ns, what=f"float64 restatement, line of {M} points ({engine})")
+
+
 @pytest.mark.parametrize("n,npol", [(3000, 2), (8176, 2), (8176, 1), (15060, 2), (32752, 2), (40000, 1), (65533, 1)])
 def test_any_length_medium_line_in_one_launch_against_oracle(n, npol, monkeypatch):
     """complex64 callers, fixed steps, 2048 < n <= 65536 (the reference's own generators: PRBS-9 / -11 words at 16 samples per bit are 8176 / 32752 samples):
@@ -967,6 +990,29 @@ def test_single_launch_adaptive_run_against_the_chunked_engine(log2n, rows, prec
 
 
 @pytest.mark.parametrize("prec", [_lib.C64, _lib.C128])
+@pytest.mark.parametrize("log2n, rows", [(9, 1), (9, 2), (10, 1), (11, 1)])
+def test_single_launch_adaptive_run_at_the_other_sizes_against_oracle(log2n, rows, prec, monkeypatch):
+    """k_small_adapt at the sizes and row counts the test above leaves out -- 512 samples with one row and with two, 1024 and 2048 with one: the whole run in
+    one launch, named by the plan, against the float64 restatement of the run at the bound of its step count."""
+    n = 1 << log2n
+    gv(**workloads.BENCH_GV)
+    a = workloads.qpsk_field(n, seed=40 + log2n, power_w=10e-3)[:rows]
+    monkeypatch.setenv("SSFM_SMALL", "1")
+    p = _lib.Plan(n, rows, prec)
+    try:
+        p.set_linear_operator(oa.devices.linear_operator(n, gv.dt, 0.2, -21.7, 0.13, prec))
+        p.set_field(a)
+        steps, z, _ = p.propagate_adaptive(1.3, 6.0, 0.008, False)
+        f, info, launches = p.get_field(), p.last_run_info(), p.last_propagate_ms()[1]
+    finally:
+        p.close()
+    assert info["engine"] == "small_adaptive" and not info["fell_back"] and launches == 1, (info, launches)
+    assert 10 <= steps <= 20 and abs(z[-1] - 6.0) < 1e-5, steps
+    ref = orc.fiber_c128(a if rows > 1 else a[0], gv.dt, 6.0, 0.2, -21.7, 0.13, 1.3, phi_max=0.008)
+    assert within(f if rows > 1 else f[0], ref, steps=steps, what=f"float64 restatement, adaptive ({steps} steps)")
+
+
+@pytest.mark.parametrize("prec", [_lib.C64, _lib.C128])
 def test_single_launch_capture_against_the_two_kernel_engine(prec, monkeypatch):
     """return_steps on a small plan: the single launch writes the field after every step between its two half rotations
     (what k_time<END> hands to the capture of the two-kernel engine)."""
@@ -1042,6 +1088,38 @@ def test_medium_single_launch_engine_against_the_two_kernel_engine(log2n, rows, 
     for h_ in hs:
         A = orc.ssfm_step_c64(A, orc.linear_operator_c64(n, gv.dt, 0.2, -21.7, 0.13), np.float32(1.3), h_)
     assert within(got["1"][0][0], A, steps=hs.size, what="oracle, step by step")
+
+
+@pytest.mark.parametrize("log2n, rows, phase", [(12, 2, "1"), (12, 2, "0"), (13, 1, "0"), (14, 1, "0"), (15, 1, "0"), (16, 1, "0"), (17, 1, "0")])
+def test_medium_single_launch_engine_on_its_smallest_shape_and_with_value_tables_against_oracle(log2n, rows, phase, monkeypatch):
+    """k_medium where the tests above do not take it: the 64 x 64 shape (2^12 samples x 2 rows, which k_small takes unless SSFM_SMALL=0) with either kind
+    of operator table, and the five larger shapes with tables of values (SSFM_PHASE_TABLE=0; a fibre's operator gets phase tables otherwise).  Fifteen
+    steps of three sizes in one launch, named by the plan, against the float64 restatement step by step."""
+    n = 1 << log2n
+    gv(**workloads.BENCH_GV)
+    rng = np.random.default_rng(100 + log2n)
+    a = ((rng.standard_normal((rows, n)) + 1j * rng.standard_normal((rows, n))) * 0.05).astype(np.complex64)
+    hs = np.array([0.5] * 12 + [0.25, 0.5, 0.125], dtype=np.float32)
+    for k in ("SSFM_FUSED_PATIENCE_TICKS", "SSFM_FORCE_FLY", "SSFM_E", "SSFM_EF", "SSFM_MEDIUM_SPLIT"):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv("SSFM_SMALL", "0")
+    monkeypatch.setenv("SSFM_MEDIUM", "1")
+    monkeypatch.setenv("SSFM_PHASE_TABLE", phase)
+    p = _lib.Plan(n, rows, _lib.C64)
+    try:
+        p.set_linear_operator(oa.devices.linear_operator(n, gv.dt, 0.2, -21.7, 0.13))
+        p.set_field(a)
+        p.propagate_fixed(1.3, hs)
+        f, info, launches = p.get_field(), p.last_run_info(), p.last_propagate_ms()[1]
+    finally:
+        p.close()
+    assert info["engine"] == "medium" and not info["fell_back"] and launches == 1, (info, launches)
+    Dn = orc.linear_operator_c128(n, gv.dt, 0.2, -21.7, 0.13)
+    want = a.astype(np.complex128)
+    for h_ in hs.astype(np.float64):
+        N_hat = 1j * 1.3 * np.abs(want) ** 2
+        want = np.fft.ifft(np.fft.fft(want * np.exp(h_ / 2 * N_hat), axis=-1) * np.exp(Dn * h_), axis=-1) * np.exp(h_ / 2 * N_hat)
+    assert within(f, want, steps=hs.size, what="float64 restatement, step by step")
 
 
 def test_a_stream_ordered_consumer_never_sees_a_run_that_gave_up(tmp_path):
