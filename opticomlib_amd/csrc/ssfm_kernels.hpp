@@ -1392,7 +1392,6 @@ template <typename T> struct FreqArgs {
     SSFM_TRACE_ARGS
 };
 
-template <typename T> __device__ __forceinline__ T exp_acc(T x);
 template <> __device__ __forceinline__ float exp_acc<float>(float x) { return expf(x); }
 template <> __device__ __forceinline__ double exp_acc<double>(double x) { return exp(x); }
 
@@ -1760,80 +1759,137 @@ template <typename T> struct MediumArgs {
 constexpr int kBarShards = 8;
 constexpr int kBarWords = 64;          // one-XCD form: a flag word per workgroup (no atomics), behind the shards; then the error word and the ticket counter
 
-// every workgroup of the launch has passed here `epoch` times once each counter shows epoch * nblk / 8 arrivals
-__device__ __forceinline__ bool medium_barrier(unsigned long long* bar, unsigned* error, long long patience, unsigned long long& epoch,
-                                               const unsigned bid, const unsigned nblk, const int tid) {
-    __shared__ __attribute__((aligned(16))) int s_bar_ok[4];
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // every wave: its write-through stores have landed
-    __syncthreads();
-    ++epoch;
-    if (tid < 64) {
-        // every workgroup raises its own word to the epoch; a wavefront of every workgroup reads them all (one per lane).  No atomics at all: sharded
-        // L2 atomics were 0.4-0.6 us per step slower
-        if (tid == 0) st_l2_u64(&bar[kBarShards + bid], epoch);
-        const unsigned long long want = epoch * (nblk / kBarShards);
-        const long long t0 = wall_clock64();
-        int good = 0;
-        // (Two polls in flight half a round trip apart, so that the last arrival is seen sooner, changed nothing: 4.71 / 5.77 / 8.12 / 12.38 against
-        // 4.59 / 5.74 / 8.07 / 12.17 us per step at 2^13 x 2 / 2^14 / 2^16 x 2 / the 8176-sample chirp-z line -- the wait is for the slowest workgroup's
-        // stores, not for the news of them.  Round 4, tools/medium_time.py.)
-        for (;;) {
-            unsigned long long got = want;
-            if ((unsigned)tid < nblk) got = ld_l2_u64(&bar[kBarShards + tid]) >= epoch ? want : 0ull;
-            if (__all(got >= want)) { good = 1; break; }
-            if (wall_clock64() - t0 > patience) break;                  // (looking at the clock only every 16th round changes nothing here: 4.59 / 5.70 / 5.82 against
-            __builtin_amdgcn_s_sleep(1);                                //  4.61 / 5.70 / 5.81 us per step at 2^13 x 2 / 2^14 / 2^14 x 2, profiles/r05_adaptive.txt)
-        }
-        if (tid == 0) { s_bar_ok[0] = good; if (!good) atomicExch(error, 1u); }
+// The meeting of a one-XCD engine's workgroups: join() once, then meet() between two passes.
+struct Meeting {
+    unsigned long long* bar;
+    unsigned* error;
+    long long patience;
+    unsigned long long epoch;
+    unsigned bid;                      // the tile / row group this workgroup drew in join()
+    unsigned nblk;
+    int tid;
+    template <typename Args>           // (any of the four Medium*Args)
+    __device__ __forceinline__ explicit Meeting(const Args& a) : bar(a.bar), error(a.error), patience(a.patience), epoch(0), nblk(a.nblk), tid(threadIdx.x) {}
+    // The one-XCD engines are launched with 8 x nblk workgroups, dealt round robin to the XCDs: the ones on XCD `xcc` take the tiles in the order they arrive
+    // (the others leave); should fewer than nblk arrive there, the first barrier runs out of patience and the host repeats the run on the launch-per-pass engine.
+    __device__ __forceinline__ bool join(const unsigned xcc) {
+        if (xcc_id() != xcc) return false;
+        __shared__ __attribute__((aligned(16))) unsigned s_bid[4];
+        if (tid == 0) s_bid[0] = (unsigned)l2_add_u64(bar + kBarShards + kBarWords + 1, 1ull);
+        __syncthreads();
+        bid = s_bid[0];
+        return bid < nblk;
     }
-    __syncthreads();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");       // (no instruction: the loads of the next pass stay below)
-    return s_bar_ok[0] != 0;
+    // every workgroup of the launch has passed here `epoch` times once each counter shows epoch * nblk / 8 arrivals.  false: out of patience (error word set)
+    __device__ __forceinline__ bool meet() {
+        __shared__ __attribute__((aligned(16))) int s_bar_ok[4];
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");            // every wave: its write-through stores have landed
+        __syncthreads();
+        ++epoch;
+        if (tid < 64) {
+            // every workgroup raises its own word to the epoch; a wavefront of every workgroup reads them all (one per lane).  No atomics at all: sharded
+            // L2 atomics were 0.4-0.6 us per step slower
+            if (tid == 0) st_l2_u64(&bar[kBarShards + bid], epoch);
+            const unsigned long long want = epoch * (nblk / kBarShards);
+            const long long t0 = wall_clock64();
+            int good = 0;
+            // (Two polls in flight half a round trip apart, so that the last arrival is seen sooner, changed nothing: 4.71 / 5.77 / 8.12 / 12.38 against
+            // 4.59 / 5.74 / 8.07 / 12.17 us per step at 2^13 x 2 / 2^14 / 2^16 x 2 / the 8176-sample chirp-z line -- the wait is for the slowest workgroup's
+            // stores, not for the news of them.  Round 4, tools/medium_time.py.)
+            for (;;) {
+                unsigned long long got = want;
+                if ((unsigned)tid < nblk) got = ld_l2_u64(&bar[kBarShards + tid]) >= epoch ? want : 0ull;
+                if (__all(got >= want)) { good = 1; break; }
+                if (wall_clock64() - t0 > patience) break;                  // (looking at the clock only every 16th round changes nothing here: 4.59 / 5.70 / 5.82 against
+                __builtin_amdgcn_s_sleep(1);                                //  4.61 / 5.70 / 5.81 us per step at 2^13 x 2 / 2^14 / 2^14 x 2, profiles/r05_adaptive.txt)
+            }
+            if (tid == 0) { s_bar_ok[0] = good; if (!good) atomicExch(error, 1u); }
+        }
+        __syncthreads();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");       // (no instruction: the loads of the next pass stay below)
+        return s_bar_ok[0] != 0;
+    }
+};
+// The workgroup shape that the two passes of a one-XCD engine share: kMediumC columns of a tile, medium_rows() rows of a group
+constexpr int kMediumC = 16;
+template <int N1, int N2> __host__ __device__ constexpr int medium_rows() {
+    constexpr int ROWS = N1 * kMediumC / N2;
+    static_assert(ROWS >= 1 && ROWS * N2 == N1 * kMediumC, "the two passes share the workgroup shape");
+    return ROWS;
 }
-// The one-XCD engines are launched with 8 x nblk workgroups, dealt round robin to the XCDs: the ones on XCD `xcc` take the tiles in the order they arrive
-// (the others leave); should fewer than nblk arrive there, the first barrier runs out of patience and the host repeats the run on the launch-per-pass engine.
-__device__ __forceinline__ bool medium_ticket(const unsigned xcc, unsigned long long* bar, const unsigned nblk, const int tid, unsigned& bid) {
-    if (xcc_id() != xcc) return false;
-    __shared__ __attribute__((aligned(16))) unsigned s_bid[4];
-    if (tid == 0) s_bid[0] = (unsigned)l2_add_u64(bar + kBarShards + kBarWords + 1, 1ull);
-    __syncthreads();
-    bid = s_bid[0];
-    return bid < nblk;
+// What all four engines hand to time_body and freq_body alike; each sets zlog, s_in, s_out, keep, mul and inv_n, tab, amp, h itself.
+// (pk: the thread's |A|^2 between two column passes, TimeArgs::pkeep)
+template <typename T, int N1, int N2, typename Args>
+__device__ __forceinline__ void medium_pass_args(const Args& a, T* pk, TimeArgs<T>& ta, FreqArgs<T>& fa) {
+    ta.F = a.F; ta.Y = a.Y; ta.P = a.P; ta.twN = nullptr; ta.twA = a.twA; ta.twB = a.twB; ta.tw1 = a.tw1; ta.st = nullptr;
+    ta.gamma = a.gamma; ta.N2 = N2; ta.rows = a.rows; ta.Qf = a.Qf; ta.step = 0; ta.derive = 0; ta.pkeep = pk;
+    fa.F = a.Y; fa.tw2 = a.tw2; fa.st = nullptr; fa.N1 = N1; fa.rows = a.rows; fa.u16 = 1; fa.step = 0;
 }
+// The end of fixed step s: the second half rotation of the step and the first of the next in one column pass (TM_MID) and a meeting, or TM_END behind the
+// last step.  false: the meeting ran out of patience
+template <typename T, int N1, int E>
+__device__ __forceinline__ bool medium_close_step(TimeArgs<T>& ta, Meeting& mt, const T* hs, const int s, const int nsteps) {
+    const T half = (T)0.5;
+    ta.hh_prev = hs[s] * half;
+    if (s + 1 < nsteps) {
+        ta.hh_next = hs[s + 1] * half;
+        time_body<T, N1, kMediumC, E, TM_MID, true, true>(ta, mt.bid, mt.nblk);
+        if (!mt.meet()) return false;
+    } else {
+        ta.hh_next = (T)0;
+        time_body<T, N1, kMediumC, E, TM_END, true, true>(ta, mt.bid, mt.nblk);
+    }
+    return true;
+}
+// The step control of the adaptive engines: every workgroup keeps the state itself -- S in registers, and in LDS s_state[0], the step being taken, and
+// s_state[1], where TM_MID_A leaves the next one (TimeArgs::s_in, s_out).
+constexpr int kNoHandOver = -0x7fffffff;          // s_state[1].steps ahead of TM_MID_A, which leaves s_state[1] untouched if the hand-over of the maxima ran out of patience
+template <typename T, int N1, int E> struct MediumStepControl {
+    StepState<T>* s_state;
+    StepState<T> S;
+    // the first step's size is in st->cur[0] (k_absmax + k_step_control ran before the launch).  false: the run is over already
+    __device__ __forceinline__ bool begin(const AdaptState<T>* st) {
+        S = st->cur[0];
+        return !S.done;
+    }
+    // S to the workgroup ahead of TM_MID_A; a meeting follows, and its barriers also publish s_state to the workgroup
+    __device__ __forceinline__ void publish(const int tid) {
+        if (tid == 0) { s_state[0] = S; s_state[1].steps = kNoHandOver; }
+    }
+    // The end of adaptive step `step`: TM_MID_A finds the next step from the maxima of all workgroups, S takes it over.  false: error word set
+    __device__ __forceinline__ bool close_step(TimeArgs<T>& ta, const Meeting& mt, const int step) {
+        ta.step = step;
+        time_body<T, N1, kMediumC, E, TM_MID_A, true, true>(ta, mt.bid, mt.nblk);
+        __syncthreads();
+        const StepState<T> Sn = s_state[1];
+        if (Sn.steps == kNoHandOver) return false;             // the hand-over of the maxima ran out of patience (error word set)
+        S = Sn;
+        return true;
+    }
+    __device__ __forceinline__ void finish(AdaptState<T>* st, const Meeting& mt) {
+        if (mt.bid == 0 && mt.tid == 0) st->cur[0] = S;        // (the host reads cur[0])
+    }
+};
 template <typename T, int N1, int N2, int E, int FMODE>
 __global__ __launch_bounds__(N1 * 16 / E) void k_medium(const MediumArgs<T> a) {
-    constexpr int C = 16, ROWS = N1 * C / N2;
-    static_assert(ROWS >= 1 && ROWS * N2 == N1 * C, "the two passes share the workgroup shape");
-    const int tid = threadIdx.x;
-    const unsigned nblk = a.nblk;
-    unsigned bid;
-    if (!medium_ticket(a.xcc, a.bar, nblk, tid, bid)) return;
-    unsigned long long epoch = 0;
+    constexpr int C = kMediumC, ROWS = medium_rows<N1, N2>();
+    Meeting mt(a);
+    if (!mt.join(a.xcc)) return;
     T pk[E];
     TimeArgs<T> ta;
-    ta.F = a.F; ta.Y = a.Y; ta.P = a.P; ta.twN = nullptr; ta.twA = a.twA; ta.twB = a.twB; ta.tw1 = a.tw1; ta.st = nullptr; ta.zlog = nullptr;
-    ta.gamma = a.gamma; ta.N2 = N2; ta.rows = a.rows; ta.Qf = a.Qf; ta.step = 0; ta.derive = 0;
-    ta.s_in = nullptr; ta.s_out = nullptr; ta.pkeep = pk; ta.mul = nullptr;
     FreqArgs<T> fa;
-    fa.F = a.Y; fa.tw2 = a.tw2; fa.st = nullptr; fa.inv_n = a.inv_n; fa.N1 = N1; fa.rows = a.rows; fa.u16 = 1; fa.step = 0;
-    const T half = (T)0.5;
-    ta.hh_prev = (T)0; ta.hh_next = a.hs[0] * half;
-    time_body<T, N1, C, E, TM_BEGIN, true, true>(ta, bid, nblk);
-    if (!medium_barrier(a.bar, a.error, a.patience, epoch, bid, nblk, tid)) return;
+    medium_pass_args<T, N1, N2>(a, pk, ta, fa);
+    ta.zlog = nullptr; ta.s_in = nullptr; ta.s_out = nullptr; ta.mul = nullptr;
+    fa.inv_n = a.inv_n;
+    ta.hh_prev = (T)0; ta.hh_next = a.hs[0] * (T)0.5;
+    time_body<T, N1, C, E, TM_BEGIN, true, true>(ta, mt.bid, mt.nblk);
+    if (!mt.meet()) return;
     for (int s = 0; s < a.nsteps; ++s) {
         const int w = a.which[s];
         fa.tab = a.tab[w]; fa.amp = a.amp[w]; fa.h = a.hs[s];
-        freq_body<T, N2, ROWS, E, FMODE, true, true>(fa, bid);
-        if (!medium_barrier(a.bar, a.error, a.patience, epoch, bid, nblk, tid)) return;
-        ta.hh_prev = a.hs[s] * half;
-        if (s + 1 < a.nsteps) {
-            ta.hh_next = a.hs[s + 1] * half;
-            time_body<T, N1, C, E, TM_MID, true, true>(ta, bid, nblk);
-            if (!medium_barrier(a.bar, a.error, a.patience, epoch, bid, nblk, tid)) return;
-        } else {
-            ta.hh_next = (T)0;
-            time_body<T, N1, C, E, TM_END, true, true>(ta, bid, nblk);
-        }
+        freq_body<T, N2, ROWS, E, FMODE, true, true>(fa, mt.bid);
+        if (!mt.meet()) return;
+        if (!medium_close_step<T, N1, E>(ta, mt, a.hs, s, a.nsteps)) return;
     }
 }
 
@@ -1870,47 +1926,33 @@ template <typename T> struct MediumChirpArgs {
 };
 template <typename T, int N1, int N2, int E>
 __global__ __launch_bounds__(N1 * 16 / E) void k_medium_chirp(const MediumChirpArgs<T> a) {
-    constexpr int C = 16, ROWS = N1 * C / N2;
-    static_assert(ROWS >= 1 && ROWS * N2 == N1 * C, "the two passes share the workgroup shape");
-    const int tid = threadIdx.x;
-    const unsigned nblk = a.nblk;
-    unsigned bid;
-    if (!medium_ticket(a.xcc, a.bar, nblk, tid, bid)) return;
-    unsigned long long epoch = 0;
+    constexpr int C = kMediumC, ROWS = medium_rows<N1, N2>();
+    Meeting mt(a);
+    if (!mt.join(a.xcc)) return;
     T pk[E];
     TimeArgs<T> ta;
-    ta.F = a.F; ta.Y = a.Y; ta.P = a.P; ta.twN = nullptr; ta.twA = a.twA; ta.twB = a.twB; ta.tw1 = a.tw1; ta.st = nullptr; ta.zlog = nullptr;
-    ta.gamma = a.gamma; ta.N2 = N2; ta.rows = a.rows; ta.Qf = a.Qf; ta.step = 0; ta.derive = 0;
-    ta.s_in = nullptr; ta.s_out = nullptr; ta.pkeep = pk; ta.mul = nullptr; ta.keep = a.n;
+    FreqArgs<T> fa;
+    medium_pass_args<T, N1, N2>(a, pk, ta, fa);
+    ta.zlog = nullptr; ta.s_in = nullptr; ta.s_out = nullptr; ta.mul = nullptr; ta.keep = a.n;
     TimeArgs<T> tl = ta;
     tl.gamma = (T)0; tl.hh_prev = tl.hh_next = (T)0; tl.keep = 0;
-    FreqArgs<T> fa;
-    fa.F = a.Y; fa.tw2 = a.tw2; fa.st = nullptr; fa.inv_n = (T)0; fa.N1 = N1; fa.rows = a.rows; fa.u16 = 1; fa.step = 0; fa.h = (T)0; fa.amp = (T)0;
-    const T half = (T)0.5;
-    ta.hh_prev = (T)0; ta.hh_next = a.hs[0] * half;
-    time_body<T, N1, C, E, TM_BEGIN, true, true>(ta, bid, nblk);
-    if (!medium_barrier(a.bar, a.error, a.patience, epoch, bid, nblk, tid)) return;
+    fa.inv_n = (T)0; fa.h = (T)0; fa.amp = (T)0;
+    ta.hh_prev = (T)0; ta.hh_next = a.hs[0] * (T)0.5;
+    time_body<T, N1, C, E, TM_BEGIN, true, true>(ta, mt.bid, mt.nblk);
+    if (!mt.meet()) return;
     for (int s = 0; s < a.nsteps; ++s) {
         tl.mul = a.mul[a.which[s]];
 #pragma unroll 1
         for (int half_step = 0; half_step < 2; ++half_step) {
             fa.tab = a.H[half_step];
-            freq_body<T, N2, ROWS, E, FM_TABLE, true, true>(fa, bid);
-            if (!medium_barrier(a.bar, a.error, a.patience, epoch, bid, nblk, tid)) return;
+            freq_body<T, N2, ROWS, E, FM_TABLE, true, true>(fa, mt.bid);
+            if (!mt.meet()) return;
             if (half_step == 0) {
-                time_body<T, N1, C, E, TM_MID_L, true, true>(tl, bid, nblk);
-                if (!medium_barrier(a.bar, a.error, a.patience, epoch, bid, nblk, tid)) return;
+                time_body<T, N1, C, E, TM_MID_L, true, true>(tl, mt.bid, mt.nblk);
+                if (!mt.meet()) return;
             }
         }
-        ta.hh_prev = a.hs[s] * half;
-        if (s + 1 < a.nsteps) {
-            ta.hh_next = a.hs[s + 1] * half;
-            time_body<T, N1, C, E, TM_MID, true, true>(ta, bid, nblk);
-            if (!medium_barrier(a.bar, a.error, a.patience, epoch, bid, nblk, tid)) return;
-        } else {
-            ta.hh_next = (T)0;
-            time_body<T, N1, C, E, TM_END, true, true>(ta, bid, nblk);
-        }
+        if (!medium_close_step<T, N1, E>(ta, mt, a.hs, s, a.nsteps)) return;
     }
 }
 
@@ -1941,52 +1983,41 @@ template <typename T> struct MediumChirpAdaptArgs {
 };
 template <typename T, int N1, int N2, int E>
 __global__ __launch_bounds__(N1 * 16 / E) void k_medium_chirp_adapt(const MediumChirpAdaptArgs<T> a) {
-    constexpr int C = 16, ROWS = N1 * C / N2;
-    static_assert(ROWS >= 1 && ROWS * N2 == N1 * C, "the two passes share the workgroup shape");
-    const int tid = threadIdx.x;
-    const unsigned nblk = a.nblk;
-    unsigned bid;
-    if (!medium_ticket(a.xcc, a.bar, nblk, tid, bid)) return;
-    __shared__ __attribute__((aligned(16))) StepState<T> s_state[2];       // [0] the step being taken, [1] where TM_MID_A leaves the next one
-    unsigned long long epoch = 0;
-    StepState<T> S = a.st->cur[0];
-    if (S.done) return;
-    TimeArgs<T> ta;
-    ta.F = a.F; ta.Y = a.Y; ta.P = a.P; ta.twN = nullptr; ta.twA = a.twA; ta.twB = a.twB; ta.tw1 = a.tw1; ta.st = nullptr; ta.zlog = a.zlog;
-    ta.gamma = a.gamma; ta.N2 = N2; ta.rows = a.rows; ta.Qf = a.Qf; ta.step = 0; ta.derive = 0;
+    constexpr int C = kMediumC, ROWS = medium_rows<N1, N2>();
+    Meeting mt(a);
+    if (!mt.join(a.xcc)) return;
+    __shared__ __attribute__((aligned(16))) StepState<T> s_state[2];
+    MediumStepControl<T, N1, E> sc{s_state};
+    if (!sc.begin(a.st)) return;
     T pk[E];
-    ta.s_in = &s_state[0]; ta.s_out = &s_state[1]; ta.pkeep = pk; ta.mul = nullptr; ta.keep = a.n;
+    TimeArgs<T> ta;
+    FreqArgs<T> fa;
+    medium_pass_args<T, N1, N2>(a, pk, ta, fa);
+    ta.zlog = a.zlog; ta.s_in = &s_state[0]; ta.s_out = &s_state[1]; ta.mul = nullptr; ta.keep = a.n;
     TimeArgs<T> tl = ta;
     tl.gamma = (T)0; tl.hh_prev = (T)0; tl.hh_next = a.inv_len; tl.mul = a.Dt; tl.zlog = nullptr;
-    FreqArgs<T> fa;
-    fa.F = a.Y; fa.tw2 = a.tw2; fa.st = nullptr; fa.inv_n = (T)0; fa.N1 = N1; fa.rows = a.rows; fa.u16 = 1; fa.step = 0; fa.h = (T)0; fa.amp = (T)0;
-    const T half = (T)0.5;
-    ta.hh_prev = (T)0; ta.hh_next = S.h * half;
-    time_body<T, N1, C, E, TM_BEGIN, true, true>(ta, bid, nblk);
-    if (tid == 0) { s_state[0] = S; s_state[1].steps = -0x7fffffff; }
-    if (!medium_barrier(a.bar, a.error, a.patience, epoch, bid, nblk, tid)) return;           // (its barriers also publish s_state to the workgroup)
+    fa.inv_n = (T)0; fa.h = (T)0; fa.amp = (T)0;
+    ta.hh_prev = (T)0; ta.hh_next = sc.S.h * (T)0.5;
+    time_body<T, N1, C, E, TM_BEGIN, true, true>(ta, mt.bid, mt.nblk);
+    sc.publish(mt.tid);
+    if (!mt.meet()) return;
     ta.st = a.st;
     for (int step = 0;; ++step) {
         fa.tab = a.H[0];
-        freq_body<T, N2, ROWS, E, FM_TABLE, true, true>(fa, bid);
-        if (!medium_barrier(a.bar, a.error, a.patience, epoch, bid, nblk, tid)) return;
-        time_body<T, N1, C, E, TM_MID_L, true, true>(tl, bid, nblk);
-        if (!medium_barrier(a.bar, a.error, a.patience, epoch, bid, nblk, tid)) return;
+        freq_body<T, N2, ROWS, E, FM_TABLE, true, true>(fa, mt.bid);
+        if (!mt.meet()) return;
+        time_body<T, N1, C, E, TM_MID_L, true, true>(tl, mt.bid, mt.nblk);
+        if (!mt.meet()) return;
         fa.tab = a.H[1];
-        freq_body<T, N2, ROWS, E, FM_TABLE, true, true>(fa, bid);
-        if (!medium_barrier(a.bar, a.error, a.patience, epoch, bid, nblk, tid)) return;
-        ta.step = step;
-        time_body<T, N1, C, E, TM_MID_A, true, true>(ta, bid, nblk);
-        __syncthreads();
-        const StepState<T> Sn = s_state[1];
-        if (Sn.steps == -0x7fffffff) return;                   // the hand-over of the maxima ran out of patience (error word set)
-        S = Sn;
-        if (S.done) break;
-        __syncthreads();
-        if (tid == 0) { s_state[0] = S; s_state[1].steps = -0x7fffffff; }
-        if (!medium_barrier(a.bar, a.error, a.patience, epoch, bid, nblk, tid)) return;
+        freq_body<T, N2, ROWS, E, FM_TABLE, true, true>(fa, mt.bid);
+        if (!mt.meet()) return;
+        if (!sc.close_step(ta, mt, step)) return;
+        if (sc.S.done) break;
+        __syncthreads();                                       // (TM_MID_L reads the step size from s_state[0], so the state is published right behind the
+        sc.publish(mt.tid);                                    //  step: every thread has to have read s_state[1] first)
+        if (!mt.meet()) return;
     }
-    if (bid == 0 && tid == 0) a.st->cur[0] = S;                // (the host reads cur[0])
+    sc.finish(a.st, mt);
 }
 
 // ------------------------------------------------------------------------------ k_medium_adapt
@@ -2016,43 +2047,32 @@ template <typename T> struct MediumAdaptArgs {
 };
 template <typename T, int N1, int N2, int E>
 __global__ __launch_bounds__(N1 * 16 / E) void k_medium_adapt(const MediumAdaptArgs<T> a) {
-    constexpr int C = 16, ROWS = N1 * C / N2;
-    static_assert(ROWS >= 1 && ROWS * N2 == N1 * C, "the two passes share the workgroup shape");
-    const int tid = threadIdx.x;
-    const unsigned nblk = a.nblk;
-    unsigned bid;
-    if (!medium_ticket(a.xcc, a.bar, nblk, tid, bid)) return;
-    __shared__ __attribute__((aligned(16))) StepState<T> s_state[2];       // [0] the step being taken, [1] where TM_MID_A leaves the next one
-    unsigned long long epoch = 0;
-    StepState<T> S = a.st->cur[0];
-    if (S.done) return;
-    TimeArgs<T> ta;
-    ta.F = a.F; ta.Y = a.Y; ta.P = a.P; ta.twN = nullptr; ta.twA = a.twA; ta.twB = a.twB; ta.tw1 = a.tw1; ta.st = nullptr; ta.zlog = a.zlog;
-    ta.gamma = a.gamma; ta.N2 = N2; ta.rows = a.rows; ta.Qf = a.Qf; ta.step = 0; ta.derive = 0;
+    constexpr int C = kMediumC, ROWS = medium_rows<N1, N2>();
+    Meeting mt(a);
+    if (!mt.join(a.xcc)) return;
+    __shared__ __attribute__((aligned(16))) StepState<T> s_state[2];
+    MediumStepControl<T, N1, E> sc{s_state};
+    if (!sc.begin(a.st)) return;
     T pk[E];
-    ta.s_in = &s_state[0]; ta.s_out = &s_state[1]; ta.pkeep = pk; ta.mul = nullptr;
+    TimeArgs<T> ta;
     FreqArgs<T> fa;
-    fa.F = a.Y; fa.tab = a.D; fa.tw2 = a.tw2; fa.st = nullptr; fa.inv_n = a.inv_n; fa.N1 = N1; fa.rows = a.rows; fa.u16 = 1; fa.step = 0; fa.amp = (T)0;
-    const T half = (T)0.5;
-    ta.hh_prev = (T)0; ta.hh_next = S.h * half;
-    time_body<T, N1, C, E, TM_BEGIN, true, true>(ta, bid, nblk);
-    if (!medium_barrier(a.bar, a.error, a.patience, epoch, bid, nblk, tid)) return;
+    medium_pass_args<T, N1, N2>(a, pk, ta, fa);
+    ta.zlog = a.zlog; ta.s_in = &s_state[0]; ta.s_out = &s_state[1]; ta.mul = nullptr;
+    fa.inv_n = a.inv_n; fa.tab = a.D; fa.amp = (T)0;
+    ta.hh_prev = (T)0; ta.hh_next = sc.S.h * (T)0.5;
+    time_body<T, N1, C, E, TM_BEGIN, true, true>(ta, mt.bid, mt.nblk);
+    if (!mt.meet()) return;
     ta.st = a.st;
     for (int step = 0;; ++step) {
-        fa.h = S.h;
-        freq_body<T, N2, ROWS, E, FM_FLY, true, true>(fa, bid);
-        if (tid == 0) { s_state[0] = S; s_state[1].steps = -0x7fffffff; }
-        if (!medium_barrier(a.bar, a.error, a.patience, epoch, bid, nblk, tid)) return;       // (its barriers also publish s_state to the workgroup)
-        ta.step = step;
-        time_body<T, N1, C, E, TM_MID_A, true, true>(ta, bid, nblk);
-        __syncthreads();
-        const StepState<T> Sn = s_state[1];
-        if (Sn.steps == -0x7fffffff) return;                   // the hand-over of the maxima ran out of patience (error word set)
-        S = Sn;
-        if (S.done) break;
-        if (!medium_barrier(a.bar, a.error, a.patience, epoch, bid, nblk, tid)) return;
+        fa.h = sc.S.h;
+        freq_body<T, N2, ROWS, E, FM_FLY, true, true>(fa, mt.bid);
+        sc.publish(mt.tid);                                    // (a meeting lies between every thread's read of s_state[1] and this: no barrier of its own)
+        if (!mt.meet()) return;
+        if (!sc.close_step(ta, mt, step)) return;
+        if (sc.S.done) break;
+        if (!mt.meet()) return;
     }
-    if (bid == 0 && tid == 0) a.st->cur[0] = S;                // (the host reads cur[0])
+    sc.finish(a.st, mt);
 }
 
 // ------------------------------------------------------------------------------ k_small
