@@ -64,6 +64,8 @@
  *   utils.py:1593-1787 (eyediagram; also           ssfm_eye_density_range (minimum, maximum, non-finite flag of the plotted points), ssfm_eye_density
  *     electrical_signal.plot_eye,                  (np.histogram2d counts, scipy.ndimage.gaussian_filter, the plotted points' colours)
  *     typing.py:1971-2041)
+ *   typing.py:2577-2808 (eye.plot: the grid, the   ssfm_eye_fold_range (minimum, maximum, non-finite flag of a general fold's points and of those a phase mask
+ *     traces' colours, the side histogram)         passes), ssfm_eye_fold_density (ssfm_eye_density of the fold, and np.histogram of the masked points)
  *   (none: NumPy arrays are the reference's only   ssfm_device_alloc / _free / _copy / _convert / _add
  *     data format)                                 -- device-resident signals between calls
  *
@@ -738,6 +740,23 @@ SSFM_API int ssfm_eye_density_range(const double* y, const double* noise, int64_
 SSFM_API int ssfm_eye_density(const double* y, const double* noise, int64_t n, int64_t sps, int64_t n_traces, int64_t bins, const double* yedges,
                               const int32_t* xbin, const double* weights, int64_t radius, uint32_t* counts, double* grid, const int32_t* xidx,
                               double min_y, double max_y, double* points, int32_t* iy, double* colors);
+
+/* The same of a general fold, as eye.plot draws it (typing.py:2718-2788): point j < count is sample start + j of the record (DEVICE, n samples, no
+ * noise term) at phase j mod period; count need not be a multiple of the period (the last trace is partial).  Values, indices and colours come back
+ * for the first n_draw * trace points (n_draw traces of `trace` points; trace = period without resampling, n_draw <= count / trace).  A fold that
+ * does not lie within the record is SSFM_ERR_INVALID before any launch.  Everything else as above: the same kernels, the same bits on every call.
+ *   ssfm_eye_fold_range     out (HOST, 7) = minimum, maximum and flags (1 a NaN, 2 an infinity) of the count points, then the same three of the
+ *                           points whose phase p has mask[p] != 0 (HOST, period bytes; NULL: every point) and their number.
+ *   ssfm_eye_fold_density   counts, grid, xbin, xidx (period entries each), yedges, weights, min_y, max_y, points, iy, colors as in
+ *                           ssfm_eye_density, with two differences: the outputs per point hold n_draw * trace values while the colours are
+ *                           normalised over all count points, and they are NaN (0 / 0, as typing.py:2757 divides) when c_max == c_min.
+ *                           With hist (HOST, hbins uint32; nullable) also np.histogram of the masked points: the bin among hedges (HOST, hbins + 1)
+ *                           by the rule of yedges; 1 <= hbins <= 4096, mask and hedges are then required. */
+SSFM_API int ssfm_eye_fold_range(const double* y, int64_t n, int64_t start, int64_t count, int64_t period, const uint8_t* mask, double* out);
+SSFM_API int ssfm_eye_fold_density(const double* y, int64_t n, int64_t start, int64_t count, int64_t period, int64_t trace, int64_t n_draw, int64_t bins,
+                                   const double* yedges, const int32_t* xbin, const double* weights, int64_t radius, uint32_t* counts, double* grid,
+                                   const int32_t* xidx, double min_y, double max_y, double* points, int32_t* iy, double* colors, const uint8_t* mask,
+                                   int64_t hbins, const double* hedges, uint32_t* hist);
 
 #ifdef __cplusplus
 }

@@ -130,6 +130,9 @@ SYMBOLS = {
     "ssfm_bits_count": (_I, [_VP, _I64, C.POINTER(_I64)]),
     "ssfm_eye_density_range": (_I, [_VP, _VP, _I64, _I64, _I64, C.POINTER(_D)]),
     "ssfm_eye_density": (_I, [_VP, _VP, _I64, _I64, _I64, _I64, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _D, _D, _VP, _VP, _VP]),
+    "ssfm_eye_fold_range": (_I, [_VP, _I64, _I64, _I64, _I64, _VP, C.POINTER(_D)]),
+    "ssfm_eye_fold_density": (_I, [_VP, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _D, _D, _VP, _VP, _VP, _VP, _I64,
+                                   _VP, _VP]),
 }
 
 

@@ -53,3 +53,23 @@ EYE_HD inline int eye_grid_index(double v, double lo, double hi, int B) {
     const long long k = (long long)t;
     return (int)(k < 0 ? 0 : (k > B - 1 ? B - 1 : k));
 }
+
+// A general fold of the record: point j < count is sample start + j at phase j mod P; the first n_draw L points are drawn, as n_draw traces of L
+// points (values and indices come back for those; L = P without resampling).  count need not be a multiple of P or of L.  eye.plot's fold
+// (reference typing.py:2718-2764; formed by utils._eye_plot_fold) is start = sps, count = n - sps, P = 2 (sps_resamp or sps), L = 2 sps,
+// n_draw = count / L; the geometry above is start = sps / 2, count = T P, L = P, n_draw = T.
+struct EyeFold {
+    long long start, count, P, L, n_draw;
+    int err;
+};
+// a fold the caller states: 0 when it lies within an n-sample record and its drawn points within its points
+EYE_HD inline int eye_fold_check(const EyeFold& f, long long n) {
+    if (f.start < 0 || f.count < 1 || f.start > n - f.count) return 1;
+    if (f.P < 1 || f.L < 1 || f.n_draw < 0 || f.n_draw > f.count / f.L) return 2;
+    return 0;
+}
+EYE_HD inline long long eye_fold_sample(const EyeFold& f, long long j) { return f.start + j; }
+EYE_HD inline int eye_fold_phase(const EyeFold& f, long long j) { return (int)(j % f.P); }
+EYE_HD inline bool eye_fold_drawn(const EyeFold& f, long long j) { return j < f.n_draw * f.L; }
+// whether point j enters the side histogram: its phase passes the mask (P bytes); a NULL mask passes every point
+EYE_HD inline bool eye_fold_masked(const EyeFold& f, const unsigned char* mask, long long j) { return !mask || mask[j % f.P] != 0; }

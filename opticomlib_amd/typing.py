@@ -1483,6 +1483,20 @@ electrical_signal._FAMILY, electrical_signal._OPERANDS = electrical_signal, (ele
 optical_signal._FAMILY, optical_signal._OPERANDS = optical_signal, (optical_signal, electrical_signal)
 
 
+class EyeShowOptions:
+    """What ``eye.plot`` draws beside the eye itself (reference ``typing.py:2440-2457``): ``averages``, ``threshold``, ``cross_points``,
+    ``legends``, ``t_opt``, ``histogram``; an option left None takes ``all_none`` (False: a default plot draws the eye alone)."""
+
+    def __init__(self, averages: bool = None, threshold: bool = None, cross_points: bool = None, legends: bool = None, t_opt: bool = None,
+                 histogram: bool = None, all_none: bool = False):
+        self.averages = averages if averages is not None else all_none
+        self.threshold = threshold if threshold is not None else all_none
+        self.cross_points = cross_points if cross_points is not None else all_none
+        self.legends = legends if legends is not None else all_none
+        self.t_opt = t_opt if t_opt is not None else all_none
+        self.histogram = histogram if histogram is not None else all_none
+
+
 class _KnownSlots(_LazyArray):
     """``eye.ones`` / ``eye.zeros``: a lazy array that only the eye of ``lab.GET_EYE_v2`` has (an ``AttributeError`` on any other eye)."""
 
@@ -1493,7 +1507,8 @@ class _KnownSlots(_LazyArray):
 
 
 class eye:
-    """Eye-diagram parameters: what ``GET_EYE`` returns, with the reference's attribute names (``typing.py`` class ``eye``; no ``plot``).
+    """Eye-diagram parameters: what ``GET_EYE`` returns, with the reference's attribute names (``typing.py`` class ``eye``), ``plot`` and
+    ``show``.  ``plot`` computes the picture where ``y`` lies (:func:`opticomlib_amd.utils.eye_fold_density`) and does not download it.
 
     ``y`` (the possibly resampled, rolled signal) stays on the GPU until it is read; ``t``, ``y_25_75``, ``y_top`` and ``y_bot`` are
     formed from it on first access (NaN outside their masks, as in the reference).  The eye of ``lab.GET_EYE_v2`` also has ``ones`` and
@@ -1558,6 +1573,119 @@ class eye:
     @property
     def y_bot(self):
         return self._masked("y_bot", lambda y: (y < self._y_center) & (self.t_span0 < self.t) & (self.t < self.t_span1))
+
+    def plot(self, show_options: EyeShowOptions = EyeShowOptions(), hlines: list = [], vlines: list = [], style='dark', cmap='winter',
+             smooth: bool = True, title: str = '', savefig: str = None, ax=None):
+        """Plot the eye diagram (reference ``typing.py:2577-2796``), artist for artist: the blurred 350 x 350 density as an image
+        (``smooth=True``) or one ``LineCollection`` per trace coloured by it, and what ``show_options`` asks for -- the decision instant and its
+        span, the crossing points, the threshold, the means, legends, and a side panel with the density's profile at the centre (``smooth``) or
+        the step histogram of the samples within the span.  ``hlines`` / ``vlines``: further lines.  ``style``: 'dark' or 'light' (applied when
+        the axes are created here).  ``savefig``: a file name ('.png' at 300 dpi).  Returns the eye.
+
+        The grid, the colours and the histogram come from :func:`opticomlib_amd.utils.eye_fold_density`: for an eye whose ``y`` lies in GPU
+        memory they are computed there and ``y`` stays there."""
+        from .utils import EYE_PLOT_BINS, eye_fold_density
+        if self.__dict__.get("_y") is None or "t_opt" not in self.__dict__ or "sps" not in self.__dict__:
+            raise ValueError('Empty eye diagram object.')
+        if style == 'dark':
+            style_context, t_opt_color, means_color = 'dark_background', '#60FF86', 'white'
+        elif style == 'light':
+            style_context, t_opt_color, means_color = 'default', 'green', '#5A5A5A'
+        else:
+            raise TypeError("The `style` argument must be one of the following values ('dark', 'light')")
+        import matplotlib.pyplot as plt
+        from contextlib import nullcontext
+        dt = self.dt
+        with plt.style.context(style_context) if ax is None else nullcontext():
+            if show_options.histogram:
+                fig, ax = plt.subplots(1, 2, gridspec_kw={'width_ratios': [4, 1], 'wspace': 0.03}, figsize=(8, 5))
+            elif ax is None:
+                fig, ax = plt.subplots(1, 1)
+                ax = [ax, ax]
+            else:
+                ax = [ax, ax]
+            if title:
+                plt.suptitle(f'Eye diagram {title}')
+            ax[0].set_xlim(-1 - dt, 1)
+            ax[0].set_ylim(self.mu0 - 4 * self.s0, self.mu1 + 4 * self.s1)
+            ax[0].set_ylabel(r'Amplitude [V]', fontsize=12)
+            ax[0].grid(color='grey', ls='--', lw=0.5, alpha=0.5)
+            ax[0].set_xticks([-1, -0.5, 0, 0.5, 1])
+            ax[0].set_xlabel(r'Time [$t/T_{slot}$]', fontsize=12)
+            if show_options.t_opt:
+                ax[0].axvline(self.t_opt, color=t_opt_color, ls='--', alpha=0.7)
+                ax[0].axvline(self.t_span0, color=t_opt_color, ls='-', alpha=0.4)
+                ax[0].axvline(self.t_span1, color=t_opt_color, ls='-', alpha=0.4)
+            if show_options.cross_points:
+                if self.y_right and self.y_left:
+                    ax[0].plot([self.t_left, self.t_right], [self.y_left, self.y_right], 'xr')
+            if show_options.threshold:
+                ax[0].axhline(self.threshold, c='r', ls='--')
+                if show_options.histogram:
+                    ax[1].axhline(self.threshold, c='r', ls='--', label='th')
+                    if show_options.legends:
+                        ax[1].legend()
+            for hl in hlines:
+                ax[0].axhline(hl, c='y')
+                if show_options.histogram:
+                    ax[1].axhline(hl, c='y')
+            for vl in vlines:
+                ax[0].axvline(vl, c='y')
+                if show_options.histogram:
+                    ax[1].axvline(vl, c='y')
+            if show_options.legends:
+                ax[0].legend([r'$t_{opt}$'], fontsize=12, loc='upper right')
+            if show_options.averages:
+                ax[0].axhline(self.mu1, color=means_color, ls=':', alpha=0.7)
+                ax[0].axhline(self.mu0, color=means_color, ls='-.', alpha=0.7)
+                if show_options.histogram:
+                    ax[1].axhline(self.mu1, color=means_color, ls=':', alpha=0.7, label=r'$\mu_1$')
+                    ax[1].axhline(self.mu0, color=means_color, ls='-.', alpha=0.7, label=r'$\mu_0$')
+                    if show_options.legends:
+                        ax[1].legend()
+            if show_options.histogram:
+                ax[1].sharey(ax[0])
+                ax[1].tick_params(axis='x', which='both', length=0, labelbottom=False)
+                ax[1].tick_params(axis='y', which='both', length=0, labelleft=False)
+                ax[1].grid(color='grey', ls='--', lw=0.5, alpha=0.5)
+
+            # the eye itself: computed where the record lies
+            step_hist = show_options.histogram and not smooth
+            d = eye_fold_density(self, colors=not smooth,
+                                 hist=(self.t_opt - 0.05 * self.t_dist, self.t_opt + 0.05 * self.t_dist) if step_hist else None)
+            if smooth:
+                from scipy.special import expit
+                heatmap = d.counts.astype(np.float64)
+                vmin, vmax = heatmap.min(), heatmap.max()
+                alpha_values = expit((d.grid - (vmin + 0.05 * (vmax - vmin))) * 100 / (vmax - vmin)).T * 0.8
+                ax[0].imshow(d.grid.T, extent=[d.xedges[0], d.xedges[-1], d.yedges[0], d.yedges[-1]], origin='lower', aspect='auto',
+                             alpha=alpha_values, cmap=cmap, interpolation='bicubic', resample=True)
+            else:
+                from matplotlib.collections import LineCollection
+                L = 2 * self.sps
+                t = d.x[:L]
+                for c, y in zip(d.colors.reshape(-1, L), d.y.reshape(-1, L)):
+                    points = np.array([t, y]).T.reshape(-1, 1, 2)
+                    segments = np.concatenate([points[:-1], points[1:]], axis=1)
+                    ax[0].add_collection(LineCollection(segments, colors=getattr(plt.cm, cmap)(c[:-1]), linewidth=1, alpha=0.05))
+            if show_options.histogram:
+                if smooth:
+                    ax[1].plot(d.grid[170:180].sum(axis=0), np.linspace(d.extent[2], d.extent[3], EYE_PLOT_BINS), color=t_opt_color)
+                else:                                           # np.histogram's counts, drawn as the reference's ax.hist draws them
+                    ax[1].hist(d.hist_edges[:-1], bins=d.hist_edges, weights=d.hist_counts.astype(np.int64), density=True,
+                               orientation='horizontal', color=t_opt_color, alpha=0.9, histtype='step')
+            if savefig:
+                if savefig.endswith('.png'):
+                    plt.savefig(savefig, dpi=300)
+                else:
+                    plt.savefig(savefig)
+        return self
+
+    def show(self):
+        """``plt.show()`` (reference ``typing.py:2798-2808``); returns the eye."""
+        import matplotlib.pyplot as plt
+        plt.show()
+        return self
 
     def __repr__(self):
         return (f"eye(sps={self.sps}, t_opt={self.t_opt}, i={self.i}, mu0={self.mu0:.6g}, mu1={self.mu1:.6g}, s0={self.s0:.3g}, "

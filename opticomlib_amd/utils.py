@@ -550,4 +550,148 @@ def eyediagram(y, sps, n_traces=None, cmap='viridis', N_grid_bins=200, grid_sigm
     return ax
 
 
-__all__ = ["get_psd", "eye_density", "eyediagram", "EyeDensity"]
+# ----------------------------------------------------------------------------- eye.plot's fold of the record (csrc/eye_density.hip, the fold entry points)
+EYE_PLOT_BINS = 350           # reference typing.py:2721: the grid of eye.plot
+EYE_PLOT_SIGMA = 3            # typing.py:2723
+EYE_PLOT_HIST_BINS = 200      # typing.py:2782: the bins of the side histogram
+
+
+class EyeFoldDensity(EyeDensity):
+    """What :func:`eye_fold_density` returns (host arrays): the fields of :class:`EyeDensity` -- ``x``, ``y``, ``colors``, ``ix``, ``iy`` of the
+    ``n_traces * 2 sps`` drawn points -- and with ``hist=(lo, hi)`` also ``hist_counts`` (200 integers), ``hist_edges`` (201) and ``n_masked``,
+    the number of points whose abscissa lies strictly between ``lo`` and ``hi``."""
+    __slots__ = ("hist_counts", "hist_edges", "n_masked")
+
+    def __init__(self, **kw):
+        for k in EyeDensity.__slots__ + self.__slots__:
+            setattr(self, k, kw.get(k))
+
+
+def _eye_plot_fold(eye_obj):
+    """``(record, start, count, P, L, n_draw, tg)`` of the points ``eye.plot`` draws (reference ``typing.py:2718-2719`` and ``:2759-2764``):
+    ``np.roll(y, -sps // 2)[sps // 2 : -sps // 2]`` is ``y[sps:]`` and ``t[:-sps]`` has the period ``P = 2 (sps_resamp or sps)``, so point
+    ``j < count = n - sps`` is sample ``sps + j`` at phase ``j mod P``; the ``n_draw = count // (2 sps)`` drawn traces have ``L = 2 sps`` points.
+    The record is read from ``eye_obj.__dict__`` so that one in GPU memory is not downloaded."""
+    d = getattr(eye_obj, "__dict__", {})
+    y = d.get("_y")
+    if y is None or "t_opt" not in d or "sps" not in d:
+        raise ValueError('Empty eye diagram object.')
+    sps = int(d["sps"])
+    tg = eye_obj._tgrid()
+    if not _is_device(y):
+        y = np.ascontiguousarray(y, dtype=np.float64)
+    if y.ndim != 1:
+        raise ValueError(f"the eye diagram takes a 1-D record, got shape {y.shape}")
+    n = int(y.size)
+    if sps < 1 or n - sps < 1:
+        raise ValueError(f"the eye's record of {n} samples at sps={sps} leaves no point to plot")
+    count, L = n - sps, 2 * sps
+    return y, sps, count, int(tg.size), L, count // L, tg
+
+
+def _fold_tables(tg, count, lo_hi):
+    """The abscissa's share of the fold, all on the host: ``(m, xedges, xbin, xidx, mask)`` -- ``m`` phases occur among the points, the
+    histogram's x-edges span their abscissae, and every phase has its column, its colour index and (with ``lo_hi``) its pass through the window."""
+    P, B = tg.size, EYE_PLOT_BINS
+    m = min(count, P)
+    min_x, max_x = tg[:m].min(), tg[:m].max()
+    xe = _hist_edges(min_x, max_x, B)
+    xbin = np.full(P, B - 1, dtype=np.int32)                       # (phases beyond the m-th never occur: any valid column)
+    xbin[:m] = _hist_bins(xe, tg[:m])
+    xidx = np.zeros(P, dtype=np.int32)
+    xidx[:m] = _grid_index(tg[:m], min_x, max_x, B)
+    mask = None
+    if lo_hi is not None:
+        mask = np.ascontiguousarray((tg > lo_hi[0]) & (tg < lo_hi[1]), dtype=np.uint8)
+    return m, xe, xbin, xidx, mask
+
+
+def _fold_hist_edges(n_masked, lo, hi):
+    """The edges ``np.histogram(v, bins=200)`` forms for the masked points: over their range, or over (0, 1) when there is none."""
+    return _hist_edges(lo, hi, EYE_PLOT_HIST_BINS) if n_masked else np.linspace(0.0, 1.0, EYE_PLOT_HIST_BINS + 1)
+
+
+def _eye_fold_density_host(a, start, count, L, n_draw, tg, colors, hist):
+    from scipy.ndimage import gaussian_filter
+    B, P = EYE_PLOT_BINS, tg.size
+    Y = a[start:start + count]
+    X = np.tile(tg, -(-count // P))[:count]
+    with np.errstate(all="ignore"):
+        counts, xe, ye = np.histogram2d(X, Y, bins=B)
+    grid = gaussian_filter(counts, sigma=EYE_PLOT_SIGMA)
+    min_y, max_y = Y.min(), Y.max()
+    out = dict(grid=grid, counts=counts.astype(np.uint32), xedges=xe, yedges=ye, extent=(X.min(), X.max(), min_y, max_y), n_traces=n_draw)
+    if colors:
+        ix, iy = _grid_index(X, X.min(), X.max(), B), _grid_index(Y, min_y, max_y, B)
+        c = grid[ix, iy]
+        with np.errstate(all="ignore"):
+            c = (c - c.min()) / (c.max() - c.min())               # (unguarded, as the reference: NaN when every point has one colour)
+        k = n_draw * L
+        out.update(x=X[:k], y=Y[:k], ix=ix[:k], iy=iy[:k], colors=c[:k])
+    if hist is not None:
+        v = Y[(X > hist[0]) & (X < hist[1])]
+        hc, he = np.histogram(v, bins=EYE_PLOT_HIST_BINS)
+        out.update(hist_counts=hc.astype(np.uint32), hist_edges=he, n_masked=int(v.size))
+    return EyeFoldDensity(**out)
+
+
+def _eye_fold_density_device(s, start, count, L, n_draw, tg, colors, hist):
+    import ctypes as C
+    B, H, P, n = EYE_PLOT_BINS, EYE_PLOT_HIST_BINS, int(tg.size), int(s.size)
+    m, xe, xbin, xidx, mask = _fold_tables(tg, count, hist)
+    rng = (C.c_double * 7)()
+    _lib.api.ssfm_eye_fold_range(s, n, start, count, P, None if mask is None else _lib._ptr(mask), rng)
+    min_y, max_y = (np.float64(np.nan),) * 2 if int(rng[2]) & 1 else (np.float64(rng[0]), np.float64(rng[1]))
+    ye = _hist_edges(min_y, max_y, B)                             # (raises NumPy's error for a range that is not finite: nothing further is launched)
+    if not np.isfinite(ye).all():
+        raise ValueError("invalid entry in coordinates array")    # max - min overflows: what np.histogram2d raises (see _eye_density_device)
+    r, w = _gauss_weights(EYE_PLOT_SIGMA)
+    counts = _lib.host_empty((B, B), np.uint32)
+    grid = _lib.host_empty((B, B), np.float64)
+    out = dict(xedges=xe, yedges=ye, extent=(tg[:m].min(), tg[:m].max(), min_y, max_y), n_traces=n_draw)
+    k = n_draw * L
+    points = (None, 0.0, 0.0, None, None, None)
+    if colors:
+        pts, iy, col = (_lib.host_empty((k,), dt) for dt in (np.float64, np.int32, np.float64))
+        points = (_lib._ptr(xidx), float(min_y), float(max_y), _lib._ptr(pts), _lib._ptr(iy), _lib._ptr(col))
+    side = (None, 0, None, None)
+    if hist is not None:
+        n_masked = int(rng[6])
+        he = _fold_hist_edges(n_masked, np.float64(rng[3]), np.float64(rng[4]))
+        hc = np.zeros(H, dtype=np.uint32)
+        out.update(hist_counts=hc, hist_edges=he, n_masked=n_masked)
+        if n_masked:
+            side = (_lib._ptr(mask), H, _lib._ptr(he), _lib._ptr(hc))
+    _lib.api.ssfm_eye_fold_density(s, n, start, count, P, L, n_draw, B, _lib._ptr(ye), _lib._ptr(xbin), _lib._ptr(w), r, _lib._ptr(counts),
+                                   _lib._ptr(grid), *points, *side)
+    _lib.TRANSFERS["d2h"] += 2 + (1 if side[3] is not None else 0)  # counts and grid; the side histogram's counts
+    if colors:
+        _lib.TRANSFERS["d2h"] += 3                                 # the drawn points' values, indices and colours
+        reps = -(-k // P) if k else 0
+        out.update(x=np.tile(tg, reps)[:k], y=pts, colors=col, ix=np.tile(xidx.astype(np.intp), reps)[:k], iy=iy.astype(np.intp))
+    return EyeFoldDensity(grid=grid, counts=counts, **out)
+
+
+def eye_fold_density(eye_obj, *, colors=False, hist=None):
+    """The computed part of ``eye.plot`` (reference ``typing.py:2718-2788``), like :func:`eye_density` is of ``eyediagram``: the eye's record
+    ``y`` without its first ``sps`` samples, folded over the eye's time grid of period ``2 (sps_resamp or sps)``; the result holds
+    ``np.histogram2d(t_, y_, bins=350)``, its ``gaussian_filter(sigma=3)``, with ``colors=True`` the drawn points (``n_traces = len(y_) // (2 sps)``
+    traces of ``2 sps`` points) with their grid indices and their grid values, normalised over all points, and with ``hist=(lo, hi)``
+    ``np.histogram(bins=200)`` of the points whose abscissa lies strictly between ``lo`` and ``hi``.  Returns an :class:`EyeFoldDensity`.
+
+    A record that ``GET_EYE`` left in GPU memory is computed there (``ssfm_eye_fold_range``, ``ssfm_eye_fold_density``) and stays there: only the
+    results come back.  A record on the host (after ``eye.y`` was read) is NumPy / SciPy on the host and loads no device.
+
+    Raises ``ValueError('Empty eye diagram object.')`` for an eye without record or ``t_opt``, and NumPy's ("autodetected range of [...] is not
+    finite") for a NaN or an infinity among the plotted points."""
+    y, sps, count, P, L, n_draw, tg = _eye_plot_fold(eye_obj)
+    if hist is not None:
+        hist = (float(hist[0]), float(hist[1]))
+    if _is_device(y):
+        if np.dtype(y.dtype) != np.dtype(np.float64):
+            raise TypeError(f"the eye diagram takes a float64 device array, not {y.dtype}")
+        return _eye_fold_density_device(y, sps, count, L, n_draw, tg, colors, hist)
+    return _eye_fold_density_host(y, sps, count, L, n_draw, tg, colors, hist)
+
+
+__all__ = ["get_psd", "eye_density", "eyediagram", "EyeDensity", "eye_fold_density", "EyeFoldDensity"]
