@@ -250,6 +250,12 @@ SSFM_API int ssfm_sosfiltfilt(int device, const double* sos, const double* zi, i
  * forms agree to rounding (the one-launch form uses fused multiply-adds), not bit for bit. */
 SSFM_API int ssfm_sosfiltfilt_last(int device, float* ms, int* launches);
 
+/* Which kernels the last filter call on `device` ran (read-only; what the tests assert their route with).  route[0..7]: wavefronts per
+ * workgroup (1 or 4), samples per thread (12 or 18), launches (1 or 3), the look-back depth handed to the one-launch kernel (the nearest
+ * totals a group's start state is made of; 0: all earlier totals), 1 if the totals crossed as tagged 16-byte units (0: behind flags),
+ * 1 if the single-meeting kernel ran, sections, channels per row (1 real, 2 complex).  All zero before the first call. */
+SSFM_API int ssfm_sosfiltfilt_last_route(int device, int* route);
+
 /* Square-law detection of the reference's PD (devices.py:1512-1515): i_ph = r * (x * x.conj()).real summed
  * over the polarisations, signal and noise kept apart as the reference's signal algebra does
  * (typing.py:1337-1344): i_sig = r * sum_p |s_p|^2,  i_noise = r * sum_p Re(s_p n_p* + n_p s_p* + n_p n_p*).

@@ -46,6 +46,7 @@ SYMBOLS = {
     "ssfm_apply_dispersion": (_I, [_VP, _D, _D, _VP]),
     "ssfm_sosfiltfilt": (_I, [_I, _VP, _VP, _I, _VP, _VP, _I64, _I, _I, _I]),
     "ssfm_sosfiltfilt_last": (_I, [_I, C.POINTER(C.c_float), C.POINTER(C.c_int)]),
+    "ssfm_sosfiltfilt_last_route": (_I, [_I, C.POINTER(C.c_int)]),
     "ssfm_square_law": (_I, [_I, _VP, _VP, _I, _I64, _D, _D, _VP, _VP, _I]),
     "ssfm_device_alloc": (_I, [_I, C.c_size_t, C.POINTER(_VP)]),
     "ssfm_device_free": (_I, [_I, _VP, C.c_size_t]),
@@ -291,6 +292,20 @@ def sosfiltfilt_last_launches(device: int = 0) -> int:
     k = C.c_int()
     api.ssfm_sosfiltfilt_last(int(device), None, C.byref(k))
     return int(k.value)
+
+
+SOS_ROUTE_FIELDS = ("waves", "chunk", "launches", "look", "tagged", "meet", "sections", "channels")
+
+
+def sosfiltfilt_last_route(device: int = 0) -> dict:
+    """What the last filter call on ``device`` ran: wavefronts per workgroup, samples per thread, launches, the look-back depth handed to
+    the kernel (0: all earlier totals), whether the totals crossed tagged (else flagged), whether the single-meeting kernel ran, sections
+    and channels per row."""
+    r = (C.c_int * 8)()
+    api.ssfm_sosfiltfilt_last_route(int(device), r)
+    d = dict(zip(SOS_ROUTE_FIELDS, (int(v) for v in r)))
+    d["tagged"], d["meet"] = bool(d["tagged"]), bool(d["meet"])
+    return d
 
 
 # ----------------------------------------------------------------------------- device-resident arrays

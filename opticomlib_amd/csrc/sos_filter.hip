@@ -135,6 +135,7 @@ struct Workspace {
     int give_ups = 0;                    // calls IN A ROW that fell back to three launches after waiting in vain; from kMaxGiveUps on the form rests
     int rested = 0;                      // ... for kRestCalls calls, then gets another try
     int last_launches = 0;
+    int last_route[8] = {0, 0, 0, 0, 0, 0, 0, 0};     // what the last call ran (ssfm_sosfiltfilt_last_route): wavefronts, chunk, launches, look, tagged, meeting, sections, channels
     hipError_t need(int i, size_t bytes) {
         if (bytes <= cap[i]) return hipSuccess;
         if (buf[i]) { (void)hipFree(buf[i]); buf[i] = nullptr; cap[i] = 0; }
@@ -296,5 +297,13 @@ extern "C" int ssfm_sosfiltfilt_last(int device, float* ms, int* launches) {
     std::lock_guard<std::mutex> lock(g_ws[device].mu);
     if (ms) *ms = g_ws[device].last_ms;
     if (launches) *launches = g_ws[device].last_launches;
+    return SSFM_OK;
+}
+
+extern "C" int ssfm_sosfiltfilt_last_route(int device, int* route) {
+    if (device < 0 || device >= kMaxDevices) return fail(SSFM_ERR_NO_DEVICE, "ssfm_sosfiltfilt_last_route: device %d", device);
+    if (!route) return fail(SSFM_ERR_INVALID, "ssfm_sosfiltfilt_last_route: NULL argument");
+    std::lock_guard<std::mutex> lock(g_ws[device].mu);
+    for (int i = 0; i < 8; ++i) route[i] = g_ws[device].last_route[i];
     return SSFM_OK;
 }

@@ -1903,6 +1903,8 @@ int run_filter_w(Workspace& w, const SosCoefs& c, const double* sos_key, const d
         if (*w.status == 0) {
             WS_TRY(hipEventElapsedTime(&w.last_ms, w.ev0, w.ev1));
             w.last_launches = 1;
+            const int route[8] = {W, kChunk, 1, L.look, CH * K <= 8, meet, NS, CH};
+            std::memcpy(w.last_route, route, sizeof(route));
             w.give_ups = 0;
             return SSFM_OK;
         }
@@ -1910,6 +1912,8 @@ int run_filter_w(Workspace& w, const SosCoefs& c, const double* sos_key, const d
     }
     double *d_y1 = w.buf[1], *d_E = w.buf[2], *d_T = w.buf[3];
     w.last_launches = 3;
+    const int route[8] = {W, kChunk, 3, 0, 0, 0, NS, CH};           // (the three-launch form sums all totals and has neither tags nor flags)
+    std::memcpy(w.last_route, route, sizeof(route));
     WS_TRY(hipEventRecord(w.ev0, w.stream));
     // One stream: splitting the rows over two streams (as the propagator does) was measured SLOWER here
     // (145 vs 121 us for 2 x 2^20 complex) -- every kernel is a short latency chain, not a bandwidth phase.

@@ -1787,9 +1787,14 @@ def test_sosfiltfilt_start_states_from_the_totals_that_matter(wn, n, rows, cplx,
     monkeypatch.delenv("SSFM_SOS_NEAR", raising=False)
     near = _lib.sosfiltfilt(sos, zi, x)
     assert _lib.sosfiltfilt_last_launches() == 1
+    r_near = _lib.sosfiltfilt_last_route()
+    assert r_near["tagged"] and not r_near["meet"]
+    if wn >= 0.06:
+        assert r_near["look"] == 1, r_near                              # (the near look-back really ran: the comparison below is of two paths)
     monkeypatch.setenv("SSFM_SOS_NEAR", "0")
     every = _lib.sosfiltfilt(sos, zi, x)
     assert _lib.sosfiltfilt_last_launches() == 1
+    assert _lib.sosfiltfilt_last_route()["look"] == 0                   # ... and every total went into this one
     assert within(near, want, bound) and within(every, want, bound)
     assert within(near, every, max(1e-13, bound / 10))
     # ... and the ONE-meeting kernels (opt-in: they are not faster; taken when the look-back is at most two groups, else the default runs)
@@ -1797,6 +1802,10 @@ def test_sosfiltfilt_start_states_from_the_totals_that_matter(wn, n, rows, cplx,
     monkeypatch.setenv("SSFM_SOS_MEET", "1")
     met = _lib.sosfiltfilt(sos, zi, x)
     assert _lib.sosfiltfilt_last_launches() == 1
+    r_met = _lib.sosfiltfilt_last_route()
+    assert not r_met["meet"] or 1 <= r_met["look"] <= 2, r_met
+    if wn >= 0.06 and n <= 1 << 18:
+        assert r_met["meet"], r_met                                     # (one group back: the single-meeting kernel is what ran)
     assert within(met, want, bound) and within(met, near, max(1e-13, bound / 10))
 
 
@@ -2783,6 +2792,7 @@ def test_call_order_and_argument_errors():
         "ssfm_plan_create": lambda: lib.ssfm_plan_create(vp, 99, 4096, 2, _lib.C64),
         "ssfm_sosfiltfilt": lambda: lib.ssfm_sosfiltfilt(99, ptr(sos), ptr(zi), 1, p, p, 1024, 1, 0, 1),
         "ssfm_sosfiltfilt_last": lambda: lib.ssfm_sosfiltfilt_last(99, fl, i32),
+        "ssfm_sosfiltfilt_last_route": lambda: lib.ssfm_sosfiltfilt_last_route(99, (C.c_int * 8)()),
         "ssfm_square_law": lambda: lib.ssfm_square_law(99, p, None, 1, 1024, 1.0, 1.0, p, None, 1),
         "ssfm_square_law (host)": lambda: lib.ssfm_square_law(99, ptr(host), None, 1, 1024, 1.0, 1.0, ptr(host), None, 0),
         "ssfm_device_alloc": lambda: lib.ssfm_device_alloc(99, 1024, vp),
