@@ -391,6 +391,19 @@ SSFM_API int ssfm_chirp_propagate_c64(ssfm_plan* plan, void* A, const void* chir
  * table slots of ssfm_transfer_table are overwritten (their tags cleared); the linear operator stays. */
 SSFM_API int ssfm_manakov_propagate(ssfm_plan* plan, double g, const double* hs, int64_t nsteps, double length, double phi_max, int64_t max_steps,
                            void* snaps, int64_t snap_every, int64_t snap_capacity, int64_t chunk, double* z_out, int64_t* steps_out);
+/* ... with polarisation-mode dispersion: the Manakov-PMD equation in the coarse-step (waveplate) model, one section per step.  Step k of size h
+ *     A <- A exp(i g P h/2);  A <- U_k A;  A_r <- ifft(fft(A_r) exp(D~ h -+ i w tau / 2));  A <- A exp(i g P h/2),     tau = dp sqrt(h)
+ * (- for row 0, which is delayed by tau / 2; + for row 1, which is advanced), everything else -- the stale P, the step rule, z, snaps (taken behind the closing
+ * half rotation, before the next step's U), chunk -- as ssfm_manakov_propagate.  dp: the PMD coefficient [ps / sqrt(km)], finite and >= 0; tau is formed
+ * in the plan's real type, the square root correctly rounded.  quats (HOST, nullable; nquats x 4 doubles): (Re a, Im a, Re b, Im b) of
+ * U_k = [[a, b], [-conj b, conj a]], one per step: at least nsteps of them for a fixed-step run, at least max_steps for an adaptive one (step k takes
+ * the k-th); NULL: no scattering, the axes stay.  w (HOST; n doubles): the angular frequencies [rad/ps] in natural (FFT) order.  With an equal step the
+ * sections are equally long and the rms differential group delay of L km is dp sqrt(L); with the adaptive step the section lengths follow the steps.
+ * The launches per step are ssfm_manakov_propagate's; the tables hold a row per polarisation and live in the plan's workspace: the table slots of
+ * ssfm_transfer_table stay as they are.  Every refusal returns before the first launch and leaves the field as it was. */
+SSFM_API int ssfm_manakov_pmd_propagate(ssfm_plan* plan, double g, const double* hs, int64_t nsteps, double length, double phi_max, int64_t max_steps,
+                               void* snaps, int64_t snap_every, int64_t snap_capacity, int64_t chunk, double* z_out, int64_t* steps_out,
+                               double dp, const double* quats, int64_t nquats, const double* w);
 /* x <- ifft_n(fft_n(x) * tab) (exponent = 0: DM's H for any length, devices.py:1019-1035) or * exp(tab) (exponent != 0) for every row of the DEVICE array
  * A (batch x n complex128, in place); tab: n complex128, DEVICE.  Plan as for ssfm_chirp_propagate.  Asynchronous on the plan's stream. */
 SSFM_API int ssfm_chirp_transfer(ssfm_plan* plan, int64_t plan_n, int batch, void* A, const void* chirp, const void* tab, int64_t n, int exponent);
@@ -459,7 +472,8 @@ enum ssfm_engine {
     SSFM_ENGINE_CHIRP_MEDIUM_ADAPT = 12, /* ... adaptive */
     SSFM_ENGINE_SPLIT = 13,            /* more than 2^22 samples per row, fixed step: four launches per step (csrc/ssfm_split.hpp) */
     SSFM_ENGINE_SPLIT_ADAPT = 14,      /* ... adaptive: five launches per step */
-    SSFM_ENGINE_MANAKOV_LINE = 15      /* Manakov-coupled polarisations (ssfm_manakov_propagate): four launches per fixed step, seven adaptive */
+    SSFM_ENGINE_MANAKOV_LINE = 15,     /* Manakov-coupled polarisations (ssfm_manakov_propagate): four launches per fixed step, seven adaptive */
+    SSFM_ENGINE_MANAKOV_PMD_LINE = 16  /* ... with PMD (ssfm_manakov_pmd_propagate): the same launches, a table per polarisation */
 };
 typedef struct ssfm_run_info {
     int engine;

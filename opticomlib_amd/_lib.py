@@ -80,6 +80,8 @@ SYMBOLS = {
     "ssfm_chirp_setup": (_I, [_VP, _I64, _I64]),
     "ssfm_chirp_propagate_c64": (_I, [_VP, _VP, _VP, _VP, _I64, _D, C.POINTER(_D), _I64, _D, _D, _I64, C.POINTER(_D), C.POINTER(_I64)]),
     "ssfm_manakov_propagate": (_I, [_VP, _D, C.POINTER(_D), _I64, _D, _D, _I64, _VP, _I64, _I64, _I64, C.POINTER(_D), C.POINTER(_I64)]),
+    "ssfm_manakov_pmd_propagate": (_I, [_VP, _D, C.POINTER(_D), _I64, _D, _D, _I64, _VP, _I64, _I64, _I64, C.POINTER(_D), C.POINTER(_I64),
+                                        _D, C.POINTER(_D), _I64, C.POINTER(_D)]),
     "ssfm_chirp_transfer": (_I, [_VP, _I64, _I, _VP, _VP, _VP, _I64, _I]),
     "ssfm_chirp_fourier": (_I, [_VP, _I64, _I, _VP, _VP, _VP, _I64, _I]),
     "ssfm_device_reduce": (_I, [_I, _I, _VP, _VP, _I, _I64, _I, C.POINTER(_D)]),
@@ -139,7 +141,8 @@ SYMBOLS = {
 
 # enum ssfm_engine of include/ssfm_amd.h, by value
 ENGINES = ("none", "two_kernel", "small", "medium", "adaptive_3_launches", "adaptive_fused", "small_adaptive", "medium_adaptive",
-           "chirp_small", "chirp_small_adaptive", "chirp_steps", "chirp_medium", "chirp_medium_adaptive", "split", "split_adaptive", "manakov_line")
+           "chirp_small", "chirp_small_adaptive", "chirp_steps", "chirp_medium", "chirp_medium_adaptive", "split", "split_adaptive", "manakov_line",
+           "manakov_pmd_line")
 DIRECT_LOG2_MAX = 22      # rows of more than 2^22 samples are split plans (csrc/ssfm_split.hpp): propagation, DM and field transfers -- no tables, chirp-z or strided capture
 
 
@@ -945,6 +948,34 @@ class Plan:
             run = (None, 0, float(length), float(phi_max), int(max_steps))
         api.ssfm_manakov_propagate(self._h, float(g), *run, snaps, check_every(every), cap, int(chunk),
                                    None if z is None else z.ctypes.data_as(C.POINTER(_D)), C.byref(steps))
+        return int(steps.value), (None if z is None else z[: int(steps.value) + 1])
+
+    def manakov_pmd_propagate(self, g: float, hs=None, *, dp: float, w, sections=None, length: float = 0.0, phi_max: float = 0.0, max_steps: int = 1 << 17,
+                              snaps: "DeviceArray" = None, every: int = 1, chunk: int = 0):
+        """:meth:`manakov_propagate` with PMD (``ssfm_manakov_pmd_propagate``): ``dp`` [ps/sqrt(km)]; ``w``: the ``n`` angular frequencies [rad/ps] in FFT
+        order; ``sections``: ``(count, 2, 2)`` unitaries ``[[a, b], [-conj b, conj a]]`` (``devices.pmd_sections``), one per step -- at least ``len(hs)``
+        of them, or ``max_steps`` for the adaptive rule -- or None for no scattering."""
+        steps, z = _I64(0), None
+        cap = 0 if snaps is None else snaps.nbytes // (2 * self.n * np.dtype(self.cdtype).itemsize)
+        w = np.ascontiguousarray(w, dtype=np.float64)
+        if w.shape != (self.n,):
+            raise ValueError(f"w must hold the plan's {self.n} frequencies, got shape {w.shape}")
+        quats, nq = None, 0
+        if sections is not None:
+            U = np.asarray(sections, dtype=np.complex128)
+            if U.ndim != 3 or U.shape[1:] != (2, 2):
+                raise ValueError(f"sections must have shape (count, 2, 2), got {U.shape}")
+            quats = np.ascontiguousarray(np.stack([U[:, 0, 0].real, U[:, 0, 0].imag, U[:, 0, 1].real, U[:, 0, 1].imag], axis=1))
+            nq = quats.shape[0]
+        if hs is not None:
+            hs = np.ascontiguousarray(hs, dtype=np.float64)
+            run = (hs.ctypes.data_as(C.POINTER(_D)), hs.size, 0.0, 0.0, 1)
+        else:
+            z = np.zeros(int(max_steps) + 1, dtype=np.float64)
+            run = (None, 0, float(length), float(phi_max), int(max_steps))
+        api.ssfm_manakov_pmd_propagate(self._h, float(g), *run, snaps, check_every(every), cap, int(chunk),
+                                       None if z is None else z.ctypes.data_as(C.POINTER(_D)), C.byref(steps),
+                                       float(dp), None if quats is None else quats.ctypes.data_as(C.POINTER(_D)), nq, w.ctypes.data_as(C.POINTER(_D)))
         return int(steps.value), (None if z is None else z[: int(steps.value) + 1])
 
     def debug_fft(self) -> np.ndarray:

@@ -55,7 +55,8 @@ SSFM_INTERNAL int plan_chirp_medium(ssfm_plan* plan, void* A, const void* chirp,
 SSFM_INTERNAL int plan_chirp_medium_adapt(ssfm_plan* plan, void* A, const void* chirp, const void* Dt, int64_t n, double gamma, double length, double phi_max,
                                           int64_t max_steps, double* z_out, int64_t* steps_out);
 SSFM_INTERNAL int64_t plan_length(ssfm_plan* plan, int* batch, int* precision);
-// A device buffer of at least `bytes` bytes owned by the plan (slot 0 ... 3; grows on demand, freed with the plan; contents undefined between calls; a growing
+constexpr int kWorkSlots = 8;
+// A device buffer of at least `bytes` bytes owned by the plan (slot 0 ... kWorkSlots - 1; grows on demand, freed with the plan; contents undefined between calls; a growing
 // call waits for the plan's stream): scratch for the driver loops of chirpz.hip (the exp(D~ h) tables, the step control block, the z log) without a
 // hipMalloc / hipFree pair per call -- hipFree waits for the whole device and stalls the streams of every other plan
 SSFM_INTERNAL int plan_workspace(ssfm_plan* plan, int slot, size_t bytes, void** out);
@@ -72,6 +73,15 @@ struct ManakovPlan {
     int batch, precision;
 };
 SSFM_INTERNAL int plan_manakov_begin(ssfm_plan* plan, ManakovPlan* out);
+// ... for the Manakov-PMD line (SSFM_ENGINE_MANAKOV_PMD_LINE): its tables hold a row per polarisation and live in the plan's workspace, so `tab` comes
+// back empty and the slots of ssfm_apply_table stay as they are
+SSFM_INTERNAL int plan_manakov_pmd_begin(ssfm_plan* plan, ManakovPlan* out);
+// out <- src brought from the natural frequency order into the order of the plan's transfer tables (both DEVICE, plan_length complex values of the plan's
+// type), with the kernel that brings D~ there; asynchronous on the plan's stream
+SSFM_INTERNAL int plan_to_table_order(ssfm_plan* plan, const void* src, void* out);
+// ssfm_apply_table with a table per batch row: x_b <- ifft(fft(x_b) tabs[b]) -- `tabs` (DEVICE) holds batch * plan_length entries in the tables' order
+// (the row pass in FM_TABLE_ROWS, ssfm_kernels.hpp); three launches, asynchronous.  SSFM_ERR_UNSUPPORTED for split plans
+SSFM_INTERNAL int plan_apply_row_tables(ssfm_plan* plan, const void* tabs);
 SSFM_INTERNAL void plan_count_launches(ssfm_plan* plan, int64_t launches);     // (ssfm_last_propagate_ms's count)
 
 // Philox4x32-10 (Salmon et al., SC'11): ten rounds on the counter `c` under the key (k0, k1) -- the documented device generator of

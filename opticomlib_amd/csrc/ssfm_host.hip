@@ -636,7 +636,7 @@ template <typename T> struct PlanT : PlanBase {
     bool external_order = false;
     // plan-owned device workspaces that grow on demand (ssfm_plan_workspace): what a driver loop outside this file (chirpz.hip) needs per call
     // without a hipMalloc / hipFree pair per call -- hipFree waits for the whole device and stalls the streams of every other plan
-    DeviceBuffer<char> work[4];
+    DeviceBuffer<char> work[kWorkSlots];
     // A buffer that work queued on the plan's stream may still read grows like this everywhere: the stream is drained, then the old block is freed
     template <typename B> int grow(B& b, size_t bytes, size_t slack = 0) {
         if (b.capacity() >= bytes) return SSFM_OK;
@@ -645,7 +645,7 @@ template <typename T> struct PlanT : PlanBase {
         return SSFM_OK;
     }
     int workspace(int slot, size_t bytes, void** out) {
-        if (slot < 0 || slot > 3 || !out) return fail(SSFM_ERR_INVALID, "ssfm_plan_workspace: slot %d", slot);
+        if (slot < 0 || slot >= kWorkSlots || !out) return fail(SSFM_ERR_INVALID, "ssfm_plan_workspace: slot %d", slot);
         if (int rc = use_device()) return rc;
         if (int rc = grow(work[slot], bytes, bytes / 2 + 256)) return rc;
         *out = work[slot].get();
@@ -2821,6 +2821,27 @@ template <typename T> struct PlanT : PlanBase {
         last_launches += 3;
         return SSFM_OK;
     }
+    // apply_table with a table per batch row (FM_TABLE_ROWS): `tabs` holds batch * n entries in the tables' order, row b's from b * n on
+    int apply_row_tables(const void* tabs) {
+        if (int rc = no_split("ssfm_manakov_pmd_propagate")) return rc;
+        if (!tabs) return fail(SSFM_ERR_INVALID, "ssfm_manakov_pmd_propagate: NULL row tables");
+        if (int rc = use_device()) return rc;
+        HIP_TRY((launch_time<T, TM_BEGIN>(N1, batch, stream, targs(0, 0, 0, nullptr), E)));
+        HIP_TRY((launch_freq<T, FM_TABLE_ROWS>(N2, N1 * batch, stream, fargs(static_cast<const cx<T>*>(tabs), 0, nullptr), Ef)));
+        HIP_TRY((launch_time<T, TM_END>(N1, batch, stream, targs(0, 0, 0, nullptr), E)));
+        last_launches += 3;
+        return SSFM_OK;
+    }
+    // out <- src (n complex values, natural frequency order) in the order of the plan's transfer tables: k_make_freq_table's copy, as D~ is brought there
+    int to_table_order(const void* src, void* out) {
+        if (int rc = no_split("ssfm_manakov_pmd_propagate")) return rc;
+        if (int rc = use_device()) return rc;
+        hipLaunchKernelGGL((k_make_freq_table<T, 0>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, stream,
+                           static_cast<const cx<T>*>(src), static_cast<cx<T>*>(out), N1, N2, N2 / Ef, (T)0, inv_n());
+        HIP_TRY(hipGetLastError());
+        ++last_launches;
+        return SSFM_OK;
+    }
 
     int debug_fft(void* dst) {
         if (int rc = no_split("ssfm_debug")) return rc;
@@ -3136,6 +3157,23 @@ int plan_manakov_begin(ssfm_plan* plan, ManakovPlan* out) {
     if (!out) return fail(SSFM_ERR_INVALID, "ssfm_manakov_propagate: NULL plan description");
     WITH_PLAN(plan, manakov_begin_impl(P_, out));
 }
+namespace {
+template <typename PT> static int manakov_pmd_begin_impl(PT* P_, ManakovPlan* out) {
+    if (int rc = P_->no_split("ssfm_manakov_pmd_propagate")) return rc;
+    if (int rc = P_->use_device()) return rc;
+    if (!P_->have_op) return fail(SSFM_ERR_STATE, "ssfm_manakov_pmd_propagate: the plan has no linear operator (ssfm_set_linear_operator)");
+    out->tab[0] = out->tab[1] = nullptr;             // (the per-row tables live in the plan's workspace: the slots of ssfm_transfer_table stay as they are)
+    out->F = P_->F; out->D = P_->dperm; out->stream = P_->stream; out->n = P_->n; out->batch = P_->batch; out->precision = P_->precision;
+    P_->last_engine = SSFM_ENGINE_MANAKOV_PMD_LINE; P_->last_fell_back = 0; P_->last_launches = 0; P_->timed = false;
+    return SSFM_OK;
+}
+}  // namespace
+int plan_manakov_pmd_begin(ssfm_plan* plan, ManakovPlan* out) {
+    if (!out) return fail(SSFM_ERR_INVALID, "ssfm_manakov_pmd_propagate: NULL plan description");
+    WITH_PLAN(plan, manakov_pmd_begin_impl(P_, out));
+}
+int plan_to_table_order(ssfm_plan* plan, const void* src, void* out) { WITH_PLAN(plan, P_->to_table_order(src, out)); }
+int plan_apply_row_tables(ssfm_plan* plan, const void* tabs) { WITH_PLAN(plan, P_->apply_row_tables(tabs)); }
 void plan_count_launches(ssfm_plan* plan, int64_t launches) {
     if (!plan || !plan->impl) return;
     if (plan->impl->precision == SSFM_C64) static_cast<PlanT<float>*>(plan->impl)->last_launches += launches;

@@ -1373,9 +1373,11 @@ __global__ SSFM_KERNEL_BOUNDS(N1 * C / E, sizeof(T), E) void k_time_h(cx<T>* Y, 
 // 8: the table is 16 of the 96 bytes a dual-pol sample*step moves); the kernel forms amp * (cos, sin) itself.
 // (FM_FLY_IM: FM_FLY for an operator whose real part is the same number at every frequency -- a fibre's -alpha/2 -- with `tab` holding the IMAGINARY
 // parts only, four per 16 bytes in FM_PHASE's order, and `amp` the real part: half the operator's bytes, the same arithmetic)
-enum FreqMode { FM_TABLE = 0, FM_FLY = 1, FM_FWD_ONLY = 2, FM_PHASE = 3, FM_FLY_IM = 4, FM_INV_ONLY = 5 };
+enum FreqMode { FM_TABLE = 0, FM_FLY = 1, FM_FWD_ONLY = 2, FM_PHASE = 3, FM_FLY_IM = 4, FM_INV_ONLY = 5, FM_TABLE_ROWS = 6 };
 // (FM_FWD_ONLY: the plan's layout in, the forward row transform, the PLAIN transposed spectrum out; FM_INV_ONLY, round 6: the plain transposed spectrum in,
 // the unnormalised inverse row transform, the plan's layout out -- the two halves of a row pass around k_split_mid, ssfm_split.hpp)
+// (FM_TABLE_ROWS: FM_TABLE with a table per BATCH row -- `tab` holds rows * N1 * N2 entries, batch row b's table from b * N1 * N2 on; the Manakov-PMD line,
+// manakov.hip, whose two polarisations see exp(-+ i w tau / 2) on top of exp(D~ h))
 
 template <typename T> struct FreqArgs {
     cx<T>* F;
@@ -1481,7 +1483,7 @@ __device__ __forceinline__ void freq_body(const FreqArgs<T>& a, const unsigned b
     const int k1 = kgrp * ROWS + rr;
     const long long row = (long long)brow * a.N1 + k1;
     cx<T>* __restrict__ Frow = a.F + row * N2;
-    const cx<T>* __restrict__ trow = a.tab + (long long)k1 * N2;
+    const cx<T>* __restrict__ trow = a.tab + (MODE == FM_TABLE_ROWS ? row : (long long)k1) * N2;
     using RI = RowIdx<row_pad_shift(E)>;
     const RI idx{rr * row_lds_elems(N2, E)};
 
@@ -1581,7 +1583,7 @@ __device__ __forceinline__ void freq_body(const FreqArgs<T>& a, const unsigned b
     }
     cx<T>* ldsT = lds + (fft_nstages(N2, E) > 1 ? ROWS * row_lds_elems(N2, E) : 0);
     line_twiddles_issue_regs<T, N2, E>(tw, j, a.tw2);
-    if constexpr (MODE == FM_TABLE) load_table();
+    if constexpr (MODE == FM_TABLE || MODE == FM_TABLE_ROWS) load_table();
     if ((FLY || MODE == FM_FWD_ONLY || MODE == FM_INV_ONLY) && a.st != nullptr) {
         // (read after the row and the operator have been asked for: the state was written by the previous launch, a ~2 us miss)
         // (the two halves of a split plan's row pass: launches queued behind the end of an adaptive run leave the field alone, like every other kernel)

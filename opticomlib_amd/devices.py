@@ -657,7 +657,10 @@ def FIBER(input: optical_signal,
           every: int = None,
           z_list=None,
           coupling: str = None,
-          kappa: float = None):
+          kappa: float = None,
+          pmd: float = None,
+          pmd_seed: int = None,
+          pmd_scatter: bool = True):
     """Optical fibre: symmetric split-step Fourier solution of the scalar NLSE per polarisation.
 
     Parameters as the reference (``devices.py:1038-1083``): ``length`` [km], ``alpha`` [dB/km],
@@ -683,12 +686,22 @@ def FIBER(input: optical_signal,
     polarisation state (``kappa`` defaults to 8/9; ``kappa=1`` is the coupled equation without the averaging).  Everything else -- the stale power
     over a step, the coefficient rounding, the step rule ``h = phi_max / max(|gamma kappa| P)`` -- is the reference's loop.  For ``(2, N)`` fields
     of a power-of-two length up to 2^22 (:func:`_fiber_manakov`).
+
+    ``pmd`` (keyword-only, with ``coupling="manakov"``): the PMD coefficient ``D_p`` [ps/sqrt(km)], finite and >= 0 -- the Manakov-PMD equation in the
+    coarse-step (waveplate) model with ONE SECTION PER STEP: behind its opening half rotation step ``k`` of size ``h`` turns the axes by the random
+    unitary ``U_k`` of :func:`pmd_sections` ``(pmd_seed, count)`` (Haar on SU(2); not with ``pmd_scatter=False``: the axes stay and the run is a pure
+    differential delay), and its linear operator delays row 0 by ``tau / 2`` and advances row 1 by ``tau / 2``, ``tau = D_p sqrt(h)`` [ps].  A fixed-step
+    run draws one unitary per step, and with an equal step ``h`` the rms differential group delay of ``L`` km is ``D_p sqrt(L)``; the adaptive run draws
+    its ``max_steps`` unitaries once and its section lengths FOLLOW THE STEPS, so its delay statistics depend on the power through the step rule.
+    ``pmd_seed=None`` picks a seed; the result reports the seed it ran with as ``output.pmd_seed`` and the engine as ``"manakov_pmd_line"``.
+    ``pmd=None`` is the ideal fibre above.  Not for ``DBP``: back-propagation cannot know the fibre's random axes.
     """
     t0 = time.time()
     if coupling is not None and coupling != "manakov":
         raise ValueError(f"coupling must be None (per polarisation) or 'manakov', got {coupling!r}")
     if coupling is None and kappa is not None:
         raise ValueError("kappa belongs to coupling='manakov'")
+    pmd = _check_pmd(coupling, pmd, pmd_seed, pmd_scatter)
     input, grid, back = _adopt(input, "optical_signal")
     if not isinstance(input, optical_signal):
         raise TypeError("`input` must be of type 'optical_signal'.")
@@ -749,7 +762,7 @@ def FIBER(input: optical_signal,
     plan = get_plan(n, batch, prec, dev)
     with plan.lock:
         if coupling is not None:
-            output = _fiber_manakov(plan, fibre, kappa, A if A_dev is None else A_dev, shape, show_progress, return_steps, every, z_list)
+            output = _fiber_manakov(plan, fibre, kappa, A if A_dev is None else A_dev, shape, show_progress, return_steps, every, z_list, pmd)
         else:
             output = _fiber_on_plan(plan, fibre, A if A_dev is None else A_dev, shape, show_progress, return_steps, every, z_list)
         if not return_steps:
@@ -775,12 +788,60 @@ def _check_manakov(shape, prec: int, kappa) -> float:
     return kappa
 
 
-def _fiber_manakov(plan, fibre, kappa: float, field, shape, show_progress, return_steps, every=None, z_list=None):
+def _check_pmd(coupling, pmd, pmd_seed, pmd_scatter):
+    """What ``pmd=`` takes, checked before anything touches the GPU; returns None (no PMD) or ``(D_p, seed, scatter)`` with the seed chosen."""
+    if pmd is None:
+        if pmd_seed is not None or pmd_scatter is not True:
+            raise ValueError("pmd_seed and pmd_scatter belong to pmd=")
+        return None
+    if coupling != "manakov":
+        raise ValueError("pmd needs coupling='manakov': PMD is an impairment of the coupled polarisations")
+    try:
+        dp = float(pmd)
+    except (TypeError, ValueError):
+        raise ValueError(f"pmd must be a finite coefficient >= 0 in ps/sqrt(km), got {pmd!r}") from None
+    if not np.isfinite(dp) or dp < 0:
+        raise ValueError(f"pmd must be a finite coefficient >= 0 in ps/sqrt(km), got {pmd!r}")
+    if pmd_seed is None:
+        pmd_seed = int(np.random.SeedSequence().generate_state(1)[0])
+    return dp, int(pmd_seed), bool(pmd_scatter)
+
+
+def pmd_sections(seed, count):
+    """The ``count`` random waveplates of a PMD run, ``(count, 2, 2)`` complex128: a point of the unit 3-sphere per section --
+    ``q = default_rng(seed).standard_normal((count, 4))``, every row scaled to unit length -- read as ``a = q0 + 1j q1``, ``b = q2 + 1j q3``,
+    ``U = [[a, b], [-conj(b), conj(a)]]``: Haar-distributed on SU(2).  The first sections of a longer draw are the shorter draw's."""
+    q = np.random.default_rng(seed).standard_normal((int(count), 4))
+    q = q / np.sqrt((q * q).sum(axis=1, keepdims=True))
+    a, b = q[:, 0] + 1j * q[:, 1], q[:, 2] + 1j * q[:, 3]
+    U = np.empty((int(count), 2, 2), dtype=np.complex128)
+    U[:, 0, 0], U[:, 0, 1], U[:, 1, 0], U[:, 1, 1] = a, b, -np.conj(b), np.conj(a)
+    return U
+
+
+def _grid_w(n, dt, precision):
+    """The angular-frequency grid [rad/ps] of :func:`_grid_powers`, FFT order, in the plan's real type."""
+    w = np.fft.fftfreq(n, dt) * 2 * np.pi * 1e-12
+    return np.asarray(w, dtype=_F32) if precision == _lib.C64 else w
+
+
+def _fiber_manakov(plan, fibre, kappa: float, field, shape, show_progress, return_steps, every=None, z_list=None, pmd=None):
     """``FIBER(coupling="manakov")`` on a power-of-two plan of two rows (the caller holds its lock): the Manakov line of csrc/manakov.hip -- a pointwise
     launch over both rows and the plan's table transform per step, the adaptive step rule on the device.  ``field``: the input, a host array or a
     device array of the plan's type.  Snapshots (``return_steps``) are taken on the device beside the run: every ``every``-th step, or every step
-    when ``z_list`` picks among them."""
+    when ``z_list`` picks among them.  ``pmd``: None or ``(D_p, seed, scatter)`` of :func:`_check_pmd` -- the same run through
+    ``Plan.manakov_pmd_propagate``, one unitary of :func:`pmd_sections` per step (drawn once for the ``max_steps`` of an adaptive run)."""
     n, batch, rt, L = plan.n, plan.batch, fibre.rt, fibre.L
+    if pmd is None:
+        run = plan.manakov_propagate
+    else:
+        dp, seed, scatter = pmd
+        w = _grid_w(n, fibre.dt, fibre.prec)
+
+        def run(g, hs, max_steps=1 << 17, **kw):
+            count = len(hs) if hs is not None else max_steps
+            sections = pmd_sections(seed, count) if scatter else None
+            return plan.manakov_pmd_propagate(g, hs, dp=dp, w=w, sections=sections, max_steps=max_steps, **kw)
     g = float(rt(rt(fibre.gamma) * rt(kappa)))
     op_tag = _tag("fibre", fibre.dt, float(fibre.alpha), float(fibre.beta_2), float(fibre.beta_3))
     if plan.tag(0) != op_tag:
@@ -809,17 +870,17 @@ def _fiber_manakov(plan, fibre, kappa: float, field, shape, show_progress, retur
         hs, z = known
         steps = len(hs)
         snaps = snapshots(steps)
-        plan.manakov_propagate(g, hs, snaps=snaps, every=stride)
+        run(g, hs, snaps=snaps, every=stride)
     else:
         max_steps = 1 << 17
         if return_steps:
             # (the snapshot buffer follows the steps the run takes: the run once for its count -- an adaptive run repeats bit for bit --, the input restored)
             x0 = _lib.DeviceArray((batch, n), plan.cdtype, plan.device)
             plan.get_field_device(x0.ptr)
-            max_steps, _ = plan.manakov_propagate(g, None, length=fibre.length, phi_max=fibre.phi_max, max_steps=max_steps)
+            max_steps, _ = run(g, None, length=fibre.length, phi_max=fibre.phi_max, max_steps=max_steps)
             plan.set_field_device(x0.ptr)
             snaps = snapshots(max_steps)
-        steps, z = plan.manakov_propagate(g, None, length=fibre.length, phi_max=fibre.phi_max, max_steps=max_steps, snaps=snaps, every=stride)
+        steps, z = run(g, None, length=fibre.length, phi_max=fibre.phi_max, max_steps=max_steps, snaps=snaps, every=stride)
     if bar is not None:
         bar.update(100)
         bar.set_postfix(FFTs=2 * int(steps))
@@ -841,6 +902,8 @@ def _fiber_manakov(plan, fibre, kappa: float, field, shape, show_progress, retur
     else:
         output = optical_signal(plan.get_field().reshape(shape))
     output.engine = plan.last_run_info()["engine"]
+    if pmd is not None:
+        output.pmd_seed = pmd[1]
     return output
 
 
@@ -967,8 +1030,14 @@ def DBP(input: optical_signal,
         every: int = None,
         z_list=None,
         coupling: str = None,
-        kappa: float = None):
-    """Digital back-propagation = ``FIBER`` with every operator negated (``devices.py:1280-1283``); ``coupling`` / ``kappa`` as ``FIBER``'s."""
+        kappa: float = None,
+        pmd: float = None,
+        pmd_seed: int = None,
+        pmd_scatter: bool = True):
+    """Digital back-propagation = ``FIBER`` with every operator negated (``devices.py:1280-1283``); ``coupling`` / ``kappa`` as ``FIBER``'s.  ``pmd`` is
+    refused: back-propagation cannot know the fibre's random axes."""
+    if pmd is not None or pmd_seed is not None or pmd_scatter is not True:
+        raise ValueError("DBP takes no pmd: back-propagation cannot know the fibre's random axes")
     return FIBER(input, length=length, alpha=-alpha, beta_2=-beta_2, beta_3=-beta_3, gamma=-gamma,
                  phi_max=phi_max, h=h, show_progress=show_progress, return_steps=return_steps,
                  precision=precision, device=device, every=every, z_list=z_list, coupling=coupling, kappa=kappa)
