@@ -27,6 +27,7 @@
 #include "ssfm_launch.hpp"
 #include "ssfm_medium.hpp"
 #include "ssfm_owned.hpp"
+#include "ssfm_route.hpp"
 #include "ssfm_schedule.hpp"
 #include "ssfm_split.hpp"
 
@@ -35,11 +36,7 @@ using namespace ssfm;
 namespace {
 
 constexpr int kLog2Min = 8, kLog2Max = 24;      // (above 2^22: split plans, ssfm_split.hpp)
-constexpr int kLog2MaxDirect = 22;                // the two-kernel engine's own range: N1 <= 512 column points x N2 <= 8192 row points
-// C, columns per k_time tile: one 128-byte line per row segment in either precision.  (complex128 used 16 as well
-// at first: 512-thread workgroups, one per CU; with 8 the two precisions have the same workgroup shape, two per CU.)
-template <typename T> constexpr int cols_per_tile() { return sizeof(T) == 8 ? 8 : 16; }
-constexpr int kMaxTables = 4;
+// (kLog2MaxDirect, cols_per_tile, kMaxTables and the other shape rules: ssfm_route.hpp)
 
 // rows per k_freq workgroup: at least 64 threads where the row count allows (N1 >= 16 rows per batch entry)
 constexpr int freq_rows(int n2, int e) { return (n2 / e) >= 64 ? 1 : ((64 * e / n2) > 16 ? 16 : (64 * e / n2)); }
@@ -135,7 +132,6 @@ hipError_t launch_time_h_n1(dim3 grid, hipStream_t s, const TimeArgs<double>& a)
     constexpr int C = cols_per_tile<double>();
     return launch_kernel<k_time_h<double, N1, C, E, MODE>, col_pass_lds<double>(N1, C, E)>(grid, dim3(N1 * C / E), s, SSFM_TIME_KERNEL_ARGS(a));
 }
-constexpr bool line_half_shape(int N1, int N2, int E, int Ef) { return ((N1 == 256 && E == 8) || (N1 == 512 && E == 16)) && Ef == 16 && N2 >= 1024 && N2 <= 8192; }
 template <int MODE>
 hipError_t launch_time_h(int N1, int batch, hipStream_t s, TimeArgs<double> a, int E) {
     a.rows = batch;
@@ -197,13 +193,7 @@ hipError_t launch_split_shuffle(int R, hipStream_t s, cx<T>* sub, cx<T>* nat, lo
     return hipGetLastError();
 }
 
-// k_small: one workgroup per row, the whole schedule in one launch.  Points per thread: 8 up to 2048 samples and for
-// complex128 (more wavefronts per row; complex128 with 16 would not fit the registers), 16 for complex64 rows of 4096 / 8192.
-constexpr int kSmallE16Min = 4096;
-template <typename T> constexpr int small_points(int n) { return sizeof(T) == 4 && n >= kSmallE16Min ? 16 : 8; }
-template <typename T> constexpr bool small_supported(int n) {
-    return n >= 256 && n <= (sizeof(T) == 4 ? 8192 : 4096) && (n & (n - 1)) == 0;
-}
+// k_small: one workgroup per row, the whole schedule in one launch (its sizes and points per thread: ssfm_route.hpp small_supported / small_points)
 static_assert(kSmallTabs == kMaxTables, "k_small takes one table per cached step size");
 // The line lengths of the one-workgroup engines, 256 ... MAXN: f(std::integral_constant<int, n>) for the one that n is
 template <int MAXN, typename F>
@@ -305,9 +295,6 @@ hipError_t launch_small_chirp_adapt(int n, int rows, hipStream_t s, const SmallC
 
 // k_small_adapt: all rows of the plan in ONE workgroup (they share the step size); at most 512 threads, so that a thread
 // may use the whole register file
-template <typename T> constexpr bool small_adapt_supported(int n, int rows) {
-    return small_supported<T>(n) && n <= 4096 && rows >= 1 && rows <= 2 && rows * n / small_points<T>(n) <= 512;     // (8192 x 1: 14.8 us per step, chunked 12.7)
-}
 template <typename T, int N, int ROWS>
 hipError_t launch_small_adapt_nr(hipStream_t s, const SmallAdaptArgs<T>& a) {
     constexpr int E = small_points<T>(N);
@@ -448,7 +435,6 @@ struct PlanBase {
     virtual ~PlanBase() {}
 };
 
-constexpr int kMaxLanesConst = 8;
 template <typename T> struct PlanT : PlanBase {
     int device = 0;
     int64_t n = 0;
@@ -501,7 +487,6 @@ template <typename T> struct PlanT : PlanBase {
     bool medium_pending = false;
     bool medium_split_ok = true;   // env SSFM_MEDIUM_SPLIT=0: a dual-polarisation plan's rows stay in one launch
     bool medium_adapt_ok = true;   // env SSFM_MEDIUM_ADAPT=0, or a run whose workgroups once did not all get to run, clears it
-    static constexpr long long medium_max_samples = 1ll << 17;      // samples in all (rows x n) up to which the one-XCD engine is used (measured: a gain up to there)
     int medium_xcc = -1, medium_xccs = 8;          // the XCD this plan's single-launch runs use, of so many
     std::vector<T> medium_sched;
     double medium_gamma = 0;
@@ -621,7 +606,7 @@ template <typename T> struct PlanT : PlanBase {
     // Nothing on the device waits across streams: a stream blocked on another stream's event slows every other queue's launches (see propagate_fixed_capture).
     static constexpr int kCapBlocksMax = 8;
     Stream cap_stream;                                    // (ensure_cap_stream)
-    std::vector<Event> cap_ev_ends[kMaxLanesConst];       // per lane and flush: the lane's END that filled the block
+    std::vector<Event> cap_ev_ends[kMaxLanes];       // per lane and flush: the lane's END that filled the block
     Event cap_ev_in;                                      // on the plan's stream, ahead of the run: the input is in F
     DeviceBuffer<char> cap_blocks;                        // kCapBlocksMax blocks at most, cap_block_bytes each
     DeviceBuffer<char> cap_in;                            // plans whose engine works in place (Y == F): a copy of the input, taken ahead of the run
@@ -664,8 +649,9 @@ template <typename T> struct PlanT : PlanBase {
         return SSFM_OK;
     }
     // the field as it is now, kept for a run that may have to be repeated on another engine
+    size_t field_bytes() const { return sizeof(cx<T>) * n * batch; }
     int backup_field() {
-        const size_t fb = sizeof(cx<T>) * n * batch;
+        const size_t fb = field_bytes();
         HIP_TRY(fused_backup.reserve(fb));
         HIP_TRY(hipMemcpyAsync(fused_backup, F, fb, hipMemcpyDeviceToDevice, stream));
         return SSFM_OK;
@@ -695,7 +681,6 @@ template <typename T> struct PlanT : PlanBase {
     // "lanes": rows are independent (they only share the adaptive step size), so a fixed-step run
     // drives disjoint row groups on separate streams; kernels of different groups overlap, which
     // hides launch gaps and lets one group compute while another waits for memory.
-    static constexpr int kMaxLanes = 8;
     int nlanes = 1;
     bool u16 = false;          // field layout between the kernels: 16-byte units (ssfm_kernels.hpp "U16")
     int E = 16;                // points per thread of k_time (env SSFM_E = 8 | 16)
@@ -794,34 +779,30 @@ template <typename T> struct PlanT : PlanBase {
     }
     ~PlanT() override { free_all(); }
 
+    // What plan_shape and the routes (ssfm_route.hpp) decided for this plan; n / batch / N1 / N2 / E / Ef / Ef_fly / u16 / nlanes / small / split_R are its copies
+    PlanShape shape;
+    static constexpr size_t cb = sizeof(cx<T>);
+    static std::optional<int> env_int(const char* text) { return text ? std::optional<int>(std::atoi(text)) : std::nullopt; }
     int init(int dev, int64_t n_, int batch_) {
         n_full = n_; batch_full = batch_;
-        {
-            int kf = 0;
-            while ((1ll << kf) < n_) ++kf;
-            int above = kLog2MaxDirect;
-            if (const char* e = std::getenv("SSFM_SPLIT_ABOVE")) { const int v = std::atoi(e); if (v >= kSplitLog2M && v < kLog2MaxDirect) above = v; }      // (tests: split plans of 2^21 / 2^22 samples)
-            if (kf > above) {
-                // a split plan: R sub-sequences of M = 2^20 samples per row (the size the two-kernel engine runs best at; SSFM_SPLIT_LOG2M = 21 | 22: diagnostics)
-                int lm = kSplitLog2M;
-                if (const char* e = std::getenv("SSFM_SPLIT_LOG2M")) { const int v = std::atoi(e); if (v >= 20 && v <= kLog2MaxDirect) lm = v; }
-                if (lm >= kf) lm = kf - 1;
-                while ((1 << (kf - lm)) > kSplitMaxR) ++lm;
-                split_R = 1 << (kf - lm);
-                if ((long long)batch_ * split_R > 65535) return fail(SSFM_ERR_INVALID, "batch=%d rows of 2^%d samples: too many sub-sequences", batch_, kf);
-                n_ = 1ll << lm;
-                batch_ *= split_R;
-                sub_valid = false; nat_valid = true;
-            }
-        }
-        device = dev; n = n_; batch = batch_;
-        int k = 0;
-        while ((1ll << k) < n) ++k;
-        // N = N1 * N2: N1 = 2^floor(k/2) up to 256, N2 up to 4096; beyond 2^20: N1 = 512, N2 up to 8192
-        const int k1 = k <= 20 ? (k / 2 < 8 ? k / 2 : 8) : 9;
-        N1 = 1 << k1;
-        N2 = 1 << (k - k1);
+        const ShapeKnobs knobs = {env_int(std::getenv("SSFM_SPLIT_ABOVE")), env_int(std::getenv("SSFM_SPLIT_LOG2M")), env_int(std::getenv("SSFM_E")), env_int(std::getenv("SSFM_EF")),
+                                  env_int(std::getenv("SSFM_EF_FLY")), env_int(std::getenv("SSFM_LANES")), env_int(std::getenv("SSFM_SMALL"))};
+        shape = plan_shape<T>(n_, batch_, knobs);
+        split_R = shape.split_R;
+        if (shape.too_many) return fail(SSFM_ERR_INVALID, "batch=%d rows of 2^%d samples: too many sub-sequences", batch_, shape.log2_full);
+        if (is_split()) { sub_valid = false; nat_valid = true; }
+        device = dev; n = shape.n; batch = shape.batch;
+        N1 = shape.N1; N2 = shape.N2; E = shape.E; Ef = shape.Ef; Ef_fly = shape.Ef_fly; u16 = shape.u16; nlanes = shape.nlanes; small = shape.small;
         HIP_TRY(hipSetDevice(device));
+        if (int rc = make_streams()) return rc;
+        if (int rc = make_tables()) return rc;
+        if (is_split()) if (int rc = make_split_extras()) return rc;
+        if (int rc = make_engine_extras()) return rc;
+        if (nlanes > 1 && nlanes <= 4) return rate_lanes_at_creation();
+        return SSFM_OK;
+    }
+    // the plan's streams (one per lane) and events
+    int make_streams() {
         // All streams of a plan live in the HIGHEST priority class.  The lanes only overlap if their streams
         // sit on different hardware queues; the runtime multiplexes streams onto GPU_MAX_HW_QUEUES (default
         // 4) queues per priority class, and in a process that also holds RCCL's (normal-priority) streams
@@ -831,69 +812,31 @@ template <typename T> struct PlanT : PlanBase {
         // starved the normal one: 26 instead of 16 us per field-step with 4 fields).
         int prio_lo = 0, prio_hi = 0;
         HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi));
-        {
-            // a plan that will drive two lanes takes a rated pair of streams from the process's pool where there is one (lane_pool above)
-            int want2 = (long long)batch * n >= (1ll << 20) ? 2 : 1;
-            if (const char* e = std::getenv("SSFM_LANES")) want2 = std::atoi(e);
-            LanePair lp;
-            if (want2 == 2 && batch_full >= 2 && batch_full % 2 == 0 && !std::getenv("SSFM_LANE_POOL_OFF") && lane_pool().take(device, &lp)) {
-                lane_stream[0].reset(lp.main); lane_stream[1].reset(lp.lane);
-                lane_score = lp.score; lane_alone_us = 0.f; lane_pair_us = 0.f;           // (the periods are this plan's own kernels': the first long run sets them)
-                lanes_from_pool = true;
-                ++g_lane_pairs_reused;
-            }
+        // a plan that will drive two lanes takes a rated pair of streams from the process's pool where there is one (lane_pool above)
+        LanePair lp;
+        if (shape.lanes_wanted == 2 && batch_full >= 2 && batch_full % 2 == 0 && !std::getenv("SSFM_LANE_POOL_OFF") && lane_pool().take(device, &lp)) {
+            lane_stream[0].reset(lp.main); lane_stream[1].reset(lp.lane);
+            lane_score = lp.score; lane_alone_us = 0.f; lane_pair_us = 0.f;           // (the periods are this plan's own kernels': the first long run sets them)
+            lanes_from_pool = true;
+            ++g_lane_pairs_reused;
         }
         if (!lane_stream[0]) HIP_TRY(hipStreamCreateWithPriority(lane_stream[0].out(), hipStreamNonBlocking, prio_hi));
         stream = lane_stream[0];
-        HIP_TRY(hipEventCreate(ev0.out()));
-        HIP_TRY(hipEventCreate(ev1.out()));
-        // measured: complex64 with 8 points per thread (twice the waves, one more exchange) is 10 % slower;
-        // complex128 is 5 % FASTER with 8 (16 need the whole register file: 1 wave per SIMD, AGPR spills)
-        E = sizeof(T) == 8 ? 8 : 16;
-        if (const char* e = std::getenv("SSFM_E")) E = std::atoi(e) == 16 ? 16 : 8;
-        // k_freq: complex128 rows run best with 16 points per thread and load-at-use twiddles (256-thread workgroups,
-        // two per CU; C1 46.8 -> 44.7 us per step), complex64 rows with 16 and register twiddles (8: 22.2 vs 21.4 us)
-        Ef = 16;
-        // up to 2^17 points a step is bound by launch and instruction latency, not by the exchanges: 8 points
-        // per thread in both kernels (twice the wavefronts per workgroup) is 5-19 % faster there (tools/small_n.py:
-        // 7.0 -> 5.7 us per step at 2^10..2^12, 8.6 -> 7.9 at 2^15, 11.3 -> 10.3 at 2^17; equal at 2^18, slower above)
-        // (complex128 likewise in k_freq: 9.0 -> 7.7 us per step at 2^10, 13.2 -> 12.3 at 2^16, 17.1 -> 15.2 at 2^17 x 2)
-        if (k <= 17 && !std::getenv("SSFM_E")) E = Ef = 8;        // (the environment knobs below still override)
-        if (std::getenv("SSFM_E")) Ef = E;
-        if (const char* e = std::getenv("SSFM_EF")) Ef = std::atoi(e) == 16 ? 16 : 8;
-        if (k > 20) E = Ef = 16;        // the large tiles (N1 = 512, N2 = 8192) exist for 16 points per thread only
-        // complex128 rows that form exp(D~ h) in the kernel: 16 points per thread need 256 VGPRs + 164 AGPRs (one wave per SIMD),
-        // 8 need 248 (two): adaptive 2^20 x 2 81.3 -> 74.6 us per step (profiles/r02_adaptive_c128_ef.txt).  The operator table's
-        // order follows the points per thread, so these rows get their own copy of D~ and of the row twiddles.
-        Ef_fly = Ef;
-        if (sizeof(T) == 8 && Ef == 16 && k <= 20 && !std::getenv("SSFM_E") && !std::getenv("SSFM_EF")) Ef_fly = 8;
-        if (const char* e = std::getenv("SSFM_EF_FLY")) Ef_fly = k > 20 ? 16 : (std::atoi(e) == 16 ? 16 : 8);
+        for (Event* e : {&ev0, &ev1}) HIP_TRY(hipEventCreate(e->out()));
         if (const char* e = std::getenv("SSFM_LANE_THREADS")) lane_threads = std::atoi(e) != 0;
-        // two lanes pay off once a launch is long enough to hide the other lane's gap; below ~2^20 points in
-        // all a step is launch-bound and the second stream only doubles the launches (2^14 x 2: 8.1 us per
-        // step with one lane, 12.0 with two; 2^18 x 2: 14.1 / 14.2; 2^20 x 2: 25.6 / 22.9 in a 200-step run)
-        int want = (long long)batch * n >= (1ll << 20) ? 2 : 1;
-        if (const char* e = std::getenv("SSFM_LANES")) want = std::atoi(e);
-        nlanes = want < 1 ? 1 : (want > kMaxLanes ? kMaxLanes : want);
-        if (nlanes > batch_full) nlanes = batch_full;
-        while (batch_full % nlanes) --nlanes;            // (a lane holds whole rows: all sub-sequences of a row of a split plan)
         HIP_TRY(hipEventCreateWithFlags(fork_ev.out(), hipEventDisableTiming));
-        if (lanes_from_pool && nlanes != 2) {           // (cannot happen with the rule above; a pooled lane stream must not leak)
-            lane_stream[1].reset(); lanes_from_pool = false;
-        }
         for (int g = 1; g < nlanes; ++g) {
             if (!(lanes_from_pool && g == 1)) HIP_TRY(hipStreamCreateWithPriority(lane_stream[g].out(), hipStreamNonBlocking, prio_hi));
             HIP_TRY(hipEventCreateWithFlags(lane_ev[g].out(), hipEventDisableTiming));
         }
         lanes_active = nlanes;
-        const size_t cb = sizeof(cx<T>);
+        return SSFM_OK;
+    }
+    // the fields, the twiddle tables of the two kernels and the operator's buffers
+    int make_tables() {
         HIP_TRY(F_own.reserve(cb * n * batch));
         HIP_TRY(P_own.reserve(sizeof(T) * n * batch));
         F = F_own; P = P_own;
-        u16 = u16_layout<T>(N1, cols_per_tile<T>(), E);
-        // the unit layout orders the field between the two kernels by N2 / Ef (k_time's Qf): rows of k_freq<FM_FLY> with another number of points per
-        // thread would pair every spectrum bin with another bin's operator (SSFM_EF_FLY != Ef: tests/test_fft_edges_gpu.py, part C) -- such plans keep Ef
-        if (u16) Ef_fly = Ef;
         Y = F;
         if (u16) { HIP_TRY(Y_own.reserve(cb * n * batch)); Y = Y_own; }
         // inter-pass twiddles W_N^(k1 n2): either the n-entry table in k_time's thread order, or (U16 plans) the two
@@ -913,15 +856,21 @@ template <typename T> struct PlanT : PlanBase {
         if (int rc = make_line_table(&tw2, N2, Ef)) return rc;
         HIP_TRY(dnat.reserve(cb * n_full));
         HIP_TRY(dperm.reserve(cb * n));
-        if (is_split()) {
-            HIP_TRY(Fnat.reserve(cb * n_full * batch_full));
-            HIP_TRY(hipMemsetAsync(Fnat, 0, cb * n_full * batch_full, stream));
-            HIP_TRY(split_twA.reserve(sizeof(double2) * (size_t)split_R * N1));
-            HIP_TRY(split_twB.reserve(sizeof(double2) * (size_t)split_R * N2));
-            const long long nt = (long long)split_R * (N1 + N2);
-            hipLaunchKernelGGL(k_make_split_twiddles, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, stream, split_twA.get(), split_twB.get(), N1, N2, split_R);
-            HIP_TRY(hipGetLastError());
-        }
+        return SSFM_OK;
+    }
+    // a split plan: the caller's natural-order field and the twiddles of the third factor
+    int make_split_extras() {
+        HIP_TRY(Fnat.reserve(cb * n_full * batch_full));
+        HIP_TRY(hipMemsetAsync(Fnat, 0, cb * n_full * batch_full, stream));
+        HIP_TRY(split_twA.reserve(sizeof(double2) * (size_t)split_R * N1));
+        HIP_TRY(split_twB.reserve(sizeof(double2) * (size_t)split_R * N2));
+        const long long nt = (long long)split_R * (N1 + N2);
+        hipLaunchKernelGGL(k_make_split_twiddles, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, stream, split_twA.get(), split_twB.get(), N1, N2, split_R);
+        HIP_TRY(hipGetLastError());
+        return SSFM_OK;
+    }
+    // what single engines need: the tables of rows that form exp(D~ h) themselves, the switches, the one-launch engines' XCD and tables, the step state
+    int make_engine_extras() {
         if (Ef_fly != Ef) {
             if (int rc = make_line_table(&tw2_fly, N2, Ef_fly)) return rc;
             HIP_TRY(dperm_fly.reserve(cb * n));
@@ -935,8 +884,6 @@ template <typename T> struct PlanT : PlanBase {
         if (const char* e = std::getenv("SSFM_FORCE_FLY")) force_fly = std::atoi(e) != 0;
         // the XCD this plan's one-launch runs meet on: decided now (the probe launch behind xcc_mask runs once per device, on a stream of its own)
         if (sizeof(T) == 4 && medium_shape(N1, N2) && (medium_ok || medium_adapt_ok)) (void)pick_xcc();
-        small = small_supported<T>((int)n);
-        if (const char* e = std::getenv("SSFM_SMALL")) small = small && std::atoi(e) != 0;
         if (small) {
             if (int rc = make_line_table(&tw_small, (int)n, small_points<T>((int)n))) return rc;
             HIP_TRY(dsmall.reserve(cb * n));
@@ -945,26 +892,24 @@ template <typename T> struct PlanT : PlanBase {
         HIP_TRY(hipMemsetAsync(P, 0, sizeof(T) * n * batch, stream));
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(stream));
-        if (nlanes > 1 && nlanes <= 4) {
-            // every lane on a hardware queue of its own, and one on which its kernels really run beside lane 0's (rate_lane): rated with the plan's own
-            // kernels on its own buffers, which hold nothing yet -- zeros (a transform of zeros is zeros; D~ = 0 is the identity)
-            HIP_TRY(hipEventCreate(lane_e0.out()));
-            HIP_TRY(hipEventCreate(lane_e1.out()));
-            HIP_TRY(hipEventCreate(run_e0.out()));
-            HIP_TRY(hipEventCreate(run_e1.out()));
-            HIP_TRY(hipMemsetAsync(F, 0, cb * n * batch, stream));
-            if (Y != F) HIP_TRY(hipMemsetAsync(Y, 0, cb * n * batch, stream));
-            HIP_TRY(hipMemsetAsync(dperm, 0, cb * n, stream));
-            if (dperm_fly) HIP_TRY(hipMemsetAsync(dperm_fly, 0, cb * n, stream));
-            bool replaced = false;
-            if (lanes_from_pool && nlanes == 2) lanes_ok = true;               // (rated by the plan that made the pair; lane_health watches the runs as for any plan)
-            else {
-                ++g_lane_ratings;
-                if (int rc = rate_and_replace_lanes(F, Y, P, &replaced)) return rc;
-            }
-            if (!lanes_ok) lane_strikes = 1;          // (no good stream to be had now: the first run that comes out slow and cannot be healed drops the second lane)
-            HIP_TRY(hipStreamSynchronize(stream));
+        return SSFM_OK;
+    }
+    // every lane on a hardware queue of its own, and one on which its kernels really run beside lane 0's (rate_lane): rated with the plan's own
+    // kernels on its own buffers, which hold nothing yet -- zeros (a transform of zeros is zeros; D~ = 0 is the identity)
+    int rate_lanes_at_creation() {
+        for (Event* e : {&lane_e0, &lane_e1, &run_e0, &run_e1}) HIP_TRY(hipEventCreate(e->out()));
+        HIP_TRY(hipMemsetAsync(F, 0, cb * n * batch, stream));
+        if (Y != F) HIP_TRY(hipMemsetAsync(Y, 0, cb * n * batch, stream));
+        HIP_TRY(hipMemsetAsync(dperm, 0, cb * n, stream));
+        if (dperm_fly) HIP_TRY(hipMemsetAsync(dperm_fly, 0, cb * n, stream));
+        bool replaced = false;
+        if (lanes_from_pool && nlanes == 2) lanes_ok = true;               // (rated by the plan that made the pair; lane_health watches the runs as for any plan)
+        else {
+            ++g_lane_ratings;
+            if (int rc = rate_and_replace_lanes(F, Y, P, &replaced)) return rc;
         }
+        if (!lanes_ok) lane_strikes = 1;          // (no good stream to be had now: the first run that comes out slow and cannot be healed drops the second lane)
+        HIP_TRY(hipStreamSynchronize(stream));
         return SSFM_OK;
     }
 
@@ -1309,8 +1254,6 @@ template <typename T> struct PlanT : PlanBase {
         ++fallbacks;
         last_fell_back = 1;
     }
-    // fixed-step runs of a dual-polarisation plan of long rows: one launch per row (see run_medium)
-    bool medium_rows_split() const { return medium_split_ok && batch == 2 && n >= (1ll << 16); }
     // the whole schedule in one launch (k_medium); `distinct` holds at most kMaxTables step sizes
     int run_medium(T gamma, double gamma_d, const Schedule<T>& sch, bool phase) {
         if constexpr (sizeof(T) != 4) { (void)gamma; (void)gamma_d; (void)sch; (void)phase; return fail(SSFM_ERR_STATE, "the medium engine is complex64 only"); }
@@ -1325,7 +1268,7 @@ template <typename T> struct PlanT : PlanBase {
         if (int rc = backup_field()) return rc;                  // for a repeat on the two-kernel engine
         // The rows of a fixed-step run share nothing: a dual-polarisation plan of long rows (2^16 samples and more) runs them as TWO launches, each
         // on an XCD and a stream of its own (2^16 x 2: 8.3 against 9.25 us per step in one launch; 2^17 x 2 only fits this way)
-        const bool two = medium_rows_split();
+        const bool two = medium_rows_split(medium_split_ok, n, batch);
         if (int rc = medium_prepare(a, two ? 1 : batch, 2)) return rc;        // (both sets of meeting words: the second launch has its own)
         a.hs = d_hs; a.which = d_which(sch);
         a.gamma = gamma; a.inv_n = inv_n(); a.nsteps = (int)nsteps;
@@ -1521,7 +1464,7 @@ template <typename T> struct PlanT : PlanBase {
         int per_row = 0, nblocks = 0, nlanes = 0;
         size_t fb = 0;
         int64_t per_block = 0, nsnap = 0, nflush = 0, nsteps = 0;
-        std::atomic<int64_t> ends_done[kMaxLanesConst];     // flushes whose last END event a lane has recorded
+        std::atomic<int64_t> ends_done[kMaxLanes];     // flushes whose last END event a lane has recorded
         std::atomic<int64_t> flushes_done{0};               // flushes whose transfer is complete (their block may be written again)
         std::atomic<int64_t> input_done{0};                 // the input's transfer is complete (F may be written)
         std::atomic<int64_t> run_queued{0};                 // 1: the run is queued (ev1 recorded), 2: it failed
@@ -1539,246 +1482,248 @@ template <typename T> struct PlanT : PlanBase {
     CapRun cap_cr;                          // (a member: the helper thread works on it after propagate_fixed_capture has returned)
     CapRun* cap_run = nullptr;              // set around the propagate_fixed call of a capture run
 
+    // One fixed-step run as its drivers see it: the caller's arguments, the schedule, the route it takes (ssfm_route.hpp fixed_route) and the two-kernel
+    // engine's operator tables.  `nlanes` is lanes_active when the run was asked for (a plan that dropped to one lane drives its rows on one stream).
+    struct FixedRun {
+        T gamma; const T* h; int64_t nsteps; const Schedule<T>* sch;
+        int nlanes, rows;                  // rows per lane
+        FixedRoute route;
+        std::vector<const cx<T>*> tabptr;
+    };
+    FixedState fixed_state() {
+        return {medium_ok, medium_split_ok, phase_tables, force_fly, profiling, SSFM_TRACE != 0, op_flat_re, twA != nullptr, medium_shape(N1, N2), lanes_active, run_e0 != nullptr};
+    }
     int propagate_fixed(double gamma_d, const T* h, int64_t nsteps, void* snapshots) {
         if (!have_op) return fail(SSFM_ERR_STATE, "ssfm_propagate_fixed: call ssfm_set_linear_operator first");
         if (int rc = use_device()) return rc;
         if (int rc = lane_health()) return rc;             // (the previous run, if it was a long two-lane run: slow lanes are repaired before this one is enqueued)
-        const T gamma = (T)gamma_d;
-        const int nlanes = lanes_active;                   // (shadows the configured number: a plan that dropped to one lane drives its rows on one stream)
-        last_launches = 0;
-        timed = false;
+        last_launches = 0; timed = false;
         if (nsteps <= 0) return SSFM_OK;
         // distinct step sizes -> operator tables (normally 1, +1 for a short last step)
         const Schedule<T> sch(h, nsteps, kMaxTables);
         if (!sch.valid())
             return fail(SSFM_ERR_INVALID, "ssfm_propagate_fixed: step %lld is %g km (must be finite and > 0)", (long long)sch.first_bad, (double)h[sch.first_bad]);
-        const std::vector<T>& distinct = sch.distinct;
-        const bool use_tables = sch.fits_tables() && !force_fly;
-        std::vector<const cx<T>*> tabptr(distinct.size(), nullptr);
-        const bool small_sched = small && use_tables && !profiling && nsteps <= 0x7fffffff;
-        // a fibre's operator has one modulus for all frequencies: 4-byte phase tables (ssfm_kernels.hpp FM_PHASE)
-        // (complex128: float64 turn fractions, 8 instead of 16 bytes per frequency -- measured -2.5 % at 2^20 x 2 (39.5 against 40.5 us per step) and
-        // +5 % at 2^16 x 2, where nothing hides the float64 sincos: from 2^20 samples in all)
-        const bool use_phase = use_tables && phase_tables && op_flat_re && (sizeof(T) == 8 ? n * batch >= (1ll << 20) && !is_split() : u16);      // (split plans: 4-byte phases in complex64)
+        FixedRun fr = {(T)gamma_d, h, nsteps, &sch, lanes_active, batch / lanes_active,
+                       fixed_route<T>(shape, fixed_state(), FixedRequest{nsteps, sch.fits_tables(), snapshots != nullptr, cap_run != nullptr}),
+                       std::vector<const cx<T>*>(sch.distinct.size(), nullptr)};
+        const FixedRoute& r = fr.route;
         if (int rc = ensure_sub()) return rc;
-        if (is_split() && !use_tables) if (int rc = split_fly_ready()) return rc;
-        // plans of 2^12 ... 2^17 samples in the unit layout: the whole schedule in one launch on one XCD (ssfm_kernels.hpp k_medium).  Measured against the
-        // one-workgroup-per-row kernel of the small plans (k_small): 5.4 against 6.4 us per step at 8192 samples, 5.6 against 3.5 at 4096 -- so from 8192 on
-        const long long med_blocks = (long long)(N2 / cols_per_tile<T>()) * (medium_rows_split() ? 1 : batch);
-        const long long med_samples = medium_rows_split() ? n : n * batch;
-        const bool med_elig = medium_ok && sizeof(T) == 4 && u16 && E == 8 && Ef == 8 && medium_shape(N1, N2) && use_tables && !profiling
-                               && snapshots == nullptr && twA != nullptr && nsteps >= 2 && nsteps <= 0x7fffffff
-                               && med_blocks % kBarShards == 0 && med_blocks <= 64 && med_samples <= medium_max_samples && (use_phase || !phase_tables || !op_flat_re);
-        const bool go_small = small_sched && snapshots == nullptr && !(med_elig && n >= 8192) && cap_run == nullptr;      // (a capture run: the two-kernel engine)
-        const bool go_medium = med_elig && !go_small && cap_run == nullptr;
+        if (is_split() && !r.use_tables) if (int rc = split_fly_ready()) return rc;
         last_fell_back = 0;
-        last_engine = (go_small || (small_sched && snapshots != nullptr)) ? SSFM_ENGINE_SMALL : go_medium ? SSFM_ENGINE_MEDIUM : is_split() ? SSFM_ENGINE_SPLIT : SSFM_ENGINE_TWO_KERNEL;
-        if (use_tables && !go_small && !go_medium)
-            if (int rc = tables_for(distinct, tabptr.data(), false, use_phase ? 1 : 0)) return rc;
-        auto freq_rows = [&](int64_t s, int row0, int rows, hipStream_t st_) -> hipError_t {
-            const int lane_ = rows > 0 ? row0 / rows : 0;
-            const T hs = h[s];
-            const cx<T>* const tp = use_tables ? tabptr[sch.which[(size_t)s]] : nullptr;
-            ++last_launches;
-            if (is_split()) {
-                last_launches += 2;
-                const T xr = op_re0 * hs;
-                return split_freq(tp, hs, nullptr, 0, row0, rows, st_, use_phase, (T)std::exp((double)xr) * inv_n_full());
-            }
-            if (use_tables) {
-                if (use_phase) {
-                    FreqArgs<T> fa = fargs(tp, hs, nullptr, row0, lane_);
-                    // the modulus as the complex table forms it: e = exp(Re * h) with the product in T, then e * (1/N) (exact: N = 2^k)
-                    const T xr = op_re0 * hs;
-                    fa.amp = (T)std::exp((double)xr) * inv_n();
-                    return launch_freq<T, FM_PHASE>(N2, N1 * rows, st_, fa, Ef);
-                }
-                return launch_freq<T, FM_TABLE>(N2, N1 * rows, st_, fargs(tp, hs, nullptr, row0, lane_), Ef);
-            }
-            return launch_freq<T, FM_FLY>(N2, N1 * rows, st_, fargs_fly(hs, nullptr, row0, lane_), Ef_fly);
-        };
-        auto freq = [&](int64_t s) -> hipError_t { return freq_rows(s, 0, batch, stream); };
-        const T half = (T)0.5;
+        if (r.use_tables && !r.go_small && !r.go_medium)
+            if (int rc = tables_for(sch.distinct, fr.tabptr.data(), false, r.use_phase ? 1 : 0)) return rc;
         for (auto& p : prof) p.n = 0;
         HIP_TRY(hipEventRecord(ev0, stream));
-        const bool health = snapshots == nullptr && !go_small && !go_medium && nlanes > 1 && !profiling && !SSFM_TRACE && nsteps >= 64 && run_e0 != nullptr && cap_run == nullptr;
-        if (health) HIP_TRY(hipEventRecord(run_e0, stream));
-        // The sequence of a run is BEGIN, (row pass, MID)*, row pass, END on every lane: lane g drives `rows` rows from row g * rows on lane_stream[g] (one lane:
-        // all rows on the plan's stream, which is lane 0's).  The three launches of it, spelled once; the drivers below differ in the ORDER they issue them in.
-        const int rows = batch / nlanes;
-        auto col_begin = [&](int g, int rows_, hipStream_t st_) -> hipError_t {
-            TimeArgs<T> a = targs(gamma, 0, h[0] * half, nullptr, g * rows_, g);
-            if (cap_run) a.scal = cap_run->scal_at(0, g * rows_);
-            ++last_launches;
-            return launch_time<T, TM_BEGIN>(N1, rows_, st_, a, E);
-        };
-        auto row_pass = [&](int g, int64_t s) -> hipError_t { return freq_rows(s, g * rows, rows, lane_stream[g]); };
-        auto col_after = [&](int g, int64_t s) -> hipError_t {            // MID between two steps, END behind the last one
-            const bool last = s + 1 == nsteps;
-            TimeArgs<T> a = targs(gamma, h[s] * half, last ? (T)0 : h[s + 1] * half, nullptr, g * rows, g);
-            if (cap_run) a.scal = cap_run->scal_at(s + 1, g * rows);
-            ++last_launches;
-            return last ? launch_time<T, TM_END>(N1, rows, lane_stream[g], a, E) : launch_time<T, TM_MID>(N1, rows, lane_stream[g], a, E);
-        };
-        // one lane's launches, start to end.  A capture run (cap_run) adds: the scalar log's address to the column launches, and at a capture step an END
-        // launch BESIDE the run -- it only reads the half-transformed field and writes this step's time-order field straight into a slot of a device block
-        // (no copy of F); the MID behind it continues exactly as a run without capture does, so the snapshots and the end field are a plain run's, bit for
-        // bit.  The lane records an event behind the END that fills a block; the helper thread sends the block to the host once every lane's event is
-        // through.  Before a block is written again the lane's THREAD waits (on the host) until the helper has seen its transfer complete: the lanes'
-        // threads run ahead of the GPU by at most the ring of blocks, the GPU never waits as long as PCIe keeps up.
-        auto lane_run = [&](int g) -> int {
-            CapRun* const cr = cap_run;
-            const bool snaps = cr && cr->every > 0;
-            auto body = [&]() -> int {
-                // (round 6 A/B: starting lane 1 of a complex128 run 5 ... 40 us late changes nothing -- 38.6-39.4 against 38.6-38.9 us per step, profiles/r06_c1_ab.txt)
-                HIP_TRY(col_begin(g, rows, lane_stream[g]));
-                int64_t k = 1;                                       // the next snapshot
-                for (int64_t s = 0; s < nsteps; ++s) {
-                    HIP_TRY(row_pass(g, s));
-                    const bool last = s + 1 == nsteps;
-                    if (snaps && !last && (s + 1) % cr->every == 0) {
-                        const int64_t j = k - 1, fl = j / cr->per_block, slot = j % cr->per_block;
-                        const int blk = (int)(fl % cr->nblocks);
-                        if (slot == 0 && fl >= cr->nblocks && !cr->wait_for(cr->flushes_done, fl - cr->nblocks + 1))      // the block is written again
-                            return fail(SSFM_ERR_HIP, "ssfm_propagate_fixed_capture: the transfers failed");
-                        TimeArgs<T> te = targs(gamma, h[s] * half, 0, nullptr, g * rows, g);
-                        te.F = reinterpret_cast<cx<T>*>(cap_blocks + cap_block_bytes * (size_t)blk + cr->fb * (size_t)slot) + (size_t)(g * rows) * n;
-                        ++last_launches;
-                        HIP_TRY((launch_time<T, TM_END>(N1, rows, lane_stream[g], te, E)));
-                        if (slot == cr->per_block - 1 || k == cr->nsnap - 2) {          // the block is full (or the last one of the run): it leaves
-                            HIP_TRY(hipEventRecord(cap_ev_ends[g][fl], lane_stream[g]));
-                            cr->ends_done[g].store(fl + 1, std::memory_order_release);
-                        }
-                        ++k;
-                    }
-                    if (last && snaps && !in_place() && !cr->wait_for(cr->input_done, 1))    // (the input's transfer reads F, which the END overwrites)
-                        return fail(SSFM_ERR_HIP, "ssfm_propagate_fixed_capture: the transfers failed");
-                    HIP_TRY(col_after(g, s));
-                }
-                return SSFM_OK;
-            };
-            const int rc = body();
-            if (rc != SSFM_OK && cr) cr->failed.store(1);
-            return rc;
-        };
-        auto fork_lanes = [&]() -> int {
-            HIP_TRY(hipEventRecord(fork_ev, stream));
-            for (int g = 1; g < nlanes; ++g) HIP_TRY(hipStreamWaitEvent(lane_stream[g], fork_ev, 0));
-            return SSFM_OK;
-        };
-        auto join_lanes = [&]() -> int {
-            for (int g = 1; g < nlanes; ++g) {
-                HIP_TRY(hipEventRecord(lane_ev[g], lane_stream[g]));
-                HIP_TRY(hipStreamWaitEvent(stream, lane_ev[g], 0));
-            }
-            return SSFM_OK;
-        };
-        auto enqueue_steps = [&]() -> int {
-            if (cap_run != nullptr && nlanes == 1) return lane_run(0);
-            if (nlanes > 1 && ((lane_threads && !profiling && nsteps >= 16) || cap_run != nullptr)) {
-                // every lane from a host thread of its own (LaneWorker): lane 0 from this one
-                if (int rc = fork_lanes()) return rc;
-                for (int g = 1; g < nlanes; ++g) { lane_worker[g].start(device); lane_worker[g].submit([&lane_run, g] { return lane_run(g); }); }
-                int rc = lane_run(0);
-                for (int g = 1; g < nlanes; ++g) { const int r = lane_worker[g].wait(); if (rc == SSFM_OK) rc = r; }
-                if (rc != SSFM_OK) return rc;
-                return join_lanes();
-            }
-            // all lanes from this thread, interleaved: every lane's row pass, then every lane's column pass, step by step (one lane: the plan's stream alone)
-            if (nlanes > 1) if (int rc = fork_lanes()) return rc;
-            for (int g = 0; g < nlanes; ++g) {
-                if (int rc = prof_mark(-1, g)) return rc;
-                HIP_TRY(col_begin(g, rows, lane_stream[g]));
-                if (int rc = prof_mark(0, g)) return rc;
-            }
-            for (int64_t s = 0; s < nsteps; ++s) {
-                for (int g = 0; g < nlanes; ++g) {
-                    HIP_TRY(row_pass(g, s));
-                    if (int rc = prof_mark(1, g)) return rc;
-                }
-                for (int g = 0; g < nlanes; ++g) {
-                    HIP_TRY(col_after(g, s));
-                    if (int rc = prof_mark(0, g)) return rc;
-                }
-            }
-            for (int g = 0; g < nlanes; ++g) if (int rc = prof_mark(2, g)) return rc;
-            return join_lanes();
-        };
-        if (snapshots == nullptr) {
+        if (r.health) HIP_TRY(hipEventRecord(run_e0, stream));
+        // z-resolved capture (reference devices.py:1150-1152, 1184-1186).  The field after every step is
+        // copied device-to-device into a block of up to `block` snapshots -- asynchronous, the step loop
+        // never waits for the host -- and a block goes to the host in one transfer.
+        int64_t block = 0;
+        DeviceBuffer<char> dsnap;                       // (lives for this call)
+        if (snapshots != nullptr) {
+            size_t free_b = 0, total_b = 0, fb = field_bytes();
+            HIP_TRY(hipMemGetInfo(&free_b, &total_b));
+            block = (int64_t)std::min<size_t>((size_t)(nsteps + 1), std::max<size_t>(1, std::min<size_t>(free_b / 2, size_t(8) << 30) / fb));
+            HIP_TRY(dsnap.reserve(fb * (size_t)block));
+        }
+        const bool whole = block == nsteps + 1;          // a small plan whose whole capture fits the device: the single launch writes every snapshot itself
+        last_engine = snapshots != nullptr && !whole ? r.engine_in_blocks : r.engine;
+        if (snapshots != nullptr) {
+            if (int rc = r.small_sched && whole ? snapshots_small(fr, snapshots, dsnap) : snapshots_every_step(fr, snapshots, dsnap, block)) return rc;
+        } else {
 #if SSFM_TRACE
-            if (int rc = trace_begin((int)(2 * nsteps + 1) * nlanes)) return rc;
+            if (int rc = trace_begin((int)(2 * nsteps + 1) * fr.nlanes)) return rc;
 #endif
-            if (go_small) {
-                if (int rc = run_small(gamma, sch)) return rc;
-            } else if (go_medium) {
-                if (int rc = run_medium(gamma, gamma_d, sch, use_phase)) return rc;
+            if (r.go_small) {
+                if (int rc = run_small(fr.gamma, sch)) return rc;
+            } else if (r.go_medium) {
+                if (int rc = run_medium(fr.gamma, gamma_d, sch, r.use_phase)) return rc;
                 if (external_order) {          // (see external_order: the caller may consume the field stream-ordered, without ssfm_synchronize)
                     HIP_TRY(hipEventRecord(ev1, stream));
                     timed = true;
                     return finish_medium();
                 }
-            } else if (int rc = enqueue_steps()) return rc;
+            } else if (int rc = run_lanes(fr)) return rc;
 #if SSFM_TRACE
             if (int rc = trace_dump()) return rc;
 #endif
-        } else {
-            // z-resolved capture (reference devices.py:1150-1152, 1184-1186).  The field after every step is
-            // copied device-to-device into a block of up to kSnapBlock snapshots -- asynchronous, the step loop
-            // never waits for the host -- and a block goes to the host in one transfer.
-            const size_t fb = sizeof(cx<T>) * n * batch;
-            char* snap = static_cast<char*>(snapshots);
-            size_t free_b = 0, total_b = 0;
-            HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-            int64_t block = (int64_t)std::min<size_t>((size_t)(nsteps + 1), std::max<size_t>(1, std::min<size_t>(free_b / 2, size_t(8) << 30) / fb));
-            DeviceBuffer<char> dsnap;                       // (lives for this call)
-            HIP_TRY(dsnap.reserve(fb * (size_t)block));
-            if (!(small_sched && block == nsteps + 1)) last_engine = is_split() ? SSFM_ENGINE_SPLIT : SSFM_ENGINE_TWO_KERNEL;
-            if (small_sched && block == nsteps + 1) {
-                // a small plan whose whole capture fits the device: the single launch writes every snapshot itself
-                hipError_t e = hipMemcpyAsync(dsnap, F, fb, hipMemcpyDeviceToDevice, stream);             // the input
-                int rc = e == hipSuccess ? run_small(gamma, sch, reinterpret_cast<cx<T>*>(dsnap.get())) : fail(SSFM_ERR_HIP, "snapshot copy failed: %s", hipGetErrorString(e));
-                if (rc == SSFM_OK) {
-                    e = hipMemcpyAsync(snap, dsnap, fb * (size_t)(nsteps + 1), hipMemcpyDeviceToHost, stream);
-                    if (e == hipSuccess) e = hipStreamSynchronize(stream);
-                    if (e != hipSuccess) rc = fail(SSFM_ERR_HIP, "snapshot download failed: %s", hipGetErrorString(e));
-                }
-                dsnap.free();
-                if (rc != SSFM_OK) return rc;
-                HIP_TRY(hipEventRecord(ev1, stream));
-                timed = true;
-                return SSFM_OK;
-            }
-            auto flush = [&](int64_t first, int64_t count) -> int {
-                hipError_t e = hipMemcpyAsync(snap + fb * first, dsnap, fb * (size_t)count, hipMemcpyDeviceToHost, stream);
-                if (e == hipSuccess) e = hipStreamSynchronize(stream);
-                if (e != hipSuccess) return fail(SSFM_ERR_HIP, "snapshot download failed: %s", hipGetErrorString(e));
-                return SSFM_OK;
-            };
-            int64_t first = 0, held = 0;                    // snapshots [first, first + held) are in dsnap
-            auto capture = [&]() -> hipError_t { return put_time_order(dsnap + fb * held++); };
-            hipError_t ce = capture();
-            for (int64_t s = 0; s < nsteps && ce == hipSuccess; ++s) {
-                if (held == block) { if (int rc = flush(first, held)) return rc; first += held; held = 0; }
-                last_launches += 2;
-                ce = launch_time<T, TM_BEGIN>(N1, batch, stream, targs(gamma, 0, h[s] * half, nullptr), E);
-                if (ce == hipSuccess) ce = freq(s);
-                if (ce == hipSuccess) ce = launch_time<T, TM_END>(N1, batch, stream, targs(gamma, h[s] * half, 0, nullptr), E);
-                if (ce == hipSuccess) ce = capture();
-            }
-            if (ce != hipSuccess) return fail(SSFM_ERR_HIP, "snapshot run failed: %s", hipGetErrorString(ce));
-            if (int rc = flush(first, held)) return rc;
-            dsnap.free();                                   // (here, not at the end of the call: the run's closing event goes behind the wait that hipFree is)
         }
+        // the common tail
         ran();
         if (int rc = publish_if_external()) return rc;          // (a caller that orders its own work on the stream finds the natural-order field)
         HIP_TRY(hipEventRecord(ev1, stream));
         timed = true;
-        if (health) {
+        if (r.health) {
             HIP_TRY(hipEventRecord(run_e1, stream));
             lane_check_pending = true;
             lane_check_launches = (is_split() ? 4 : 2) * nsteps + 1;
         }
         if (snapshots != nullptr) HIP_TRY(hipStreamSynchronize(stream));
+        return SSFM_OK;
+    }
+    // ---- the two-kernel engine's launches.  The sequence of a run is BEGIN, (row pass, MID)*, row pass, END on every lane: lane g drives `rows` rows from
+    // row g * rows on lane_stream[g] (one lane: all rows on the plan's stream, which is lane 0's).  The three launches of it, spelled once; the drivers
+    // below differ in the ORDER they issue them in.
+    hipError_t row_launch(const FixedRun& fr, int64_t s, int row0, int rows, hipStream_t st_) {
+        const FixedRoute& r = fr.route;
+        const int lane_ = rows > 0 ? row0 / rows : 0;
+        const T hs = fr.h[s];
+        const cx<T>* const tp = r.use_tables ? fr.tabptr[fr.sch->which[(size_t)s]] : nullptr;
+        ++last_launches;
+        if (is_split()) {
+            last_launches += 2;
+            const T xr = op_re0 * hs;
+            return split_freq(tp, hs, nullptr, 0, row0, rows, st_, r.use_phase, (T)std::exp((double)xr) * inv_n_full());
+        }
+        if (r.use_tables) {
+            if (r.use_phase) {
+                FreqArgs<T> fa = fargs(tp, hs, nullptr, row0, lane_);
+                // the modulus as the complex table forms it: e = exp(Re * h) with the product in T, then e * (1/N) (exact: N = 2^k)
+                const T xr = op_re0 * hs;
+                fa.amp = (T)std::exp((double)xr) * inv_n();
+                return launch_freq<T, FM_PHASE>(N2, N1 * rows, st_, fa, Ef);
+            }
+            return launch_freq<T, FM_TABLE>(N2, N1 * rows, st_, fargs(tp, hs, nullptr, row0, lane_), Ef);
+        }
+        return launch_freq<T, FM_FLY>(N2, N1 * rows, st_, fargs_fly(hs, nullptr, row0, lane_), Ef_fly);
+    }
+    hipError_t col_begin(const FixedRun& fr, int g) {
+        TimeArgs<T> a = targs(fr.gamma, 0, fr.h[0] * (T)0.5, nullptr, g * fr.rows, g);
+        if (cap_run) a.scal = cap_run->scal_at(0, g * fr.rows);
+        ++last_launches;
+        return launch_time<T, TM_BEGIN>(N1, fr.rows, lane_stream[g], a, E);
+    }
+    hipError_t row_pass(const FixedRun& fr, int g, int64_t s) { return row_launch(fr, s, g * fr.rows, fr.rows, lane_stream[g]); }
+    hipError_t col_after(const FixedRun& fr, int g, int64_t s) {            // MID between two steps, END behind the last one
+        const bool last = s + 1 == fr.nsteps;
+        TimeArgs<T> a = targs(fr.gamma, fr.h[s] * (T)0.5, last ? (T)0 : fr.h[s + 1] * (T)0.5, nullptr, g * fr.rows, g);
+        if (cap_run) a.scal = cap_run->scal_at(s + 1, g * fr.rows);
+        ++last_launches;
+        return last ? launch_time<T, TM_END>(N1, fr.rows, lane_stream[g], a, E) : launch_time<T, TM_MID>(N1, fr.rows, lane_stream[g], a, E);
+    }
+    // one lane's launches, start to end.  A capture run (cap_run) adds: the scalar log's address to the column launches, and at a capture step an END
+    // launch BESIDE the run -- it only reads the half-transformed field and writes this step's time-order field straight into a slot of a device block
+    // (no copy of F); the MID behind it continues exactly as a run without capture does, so the snapshots and the end field are a plain run's, bit for
+    // bit.  The lane records an event behind the END that fills a block; the helper thread sends the block to the host once every lane's event is
+    // through.  Before a block is written again the lane's THREAD waits (on the host) until the helper has seen its transfer complete: the lanes'
+    // threads run ahead of the GPU by at most the ring of blocks, the GPU never waits as long as PCIe keeps up.
+    int lane_run(const FixedRun& fr, int g) {
+        CapRun* const cr = cap_run;
+        const bool snaps = cr && cr->every > 0;
+        auto body = [&]() -> int {
+            // (round 6 A/B: starting lane 1 of a complex128 run 5 ... 40 us late changes nothing -- 38.6-39.4 against 38.6-38.9 us per step, profiles/r06_c1_ab.txt)
+            HIP_TRY(col_begin(fr, g));
+            int64_t k = 1;                                       // the next snapshot
+            for (int64_t s = 0; s < fr.nsteps; ++s) {
+                HIP_TRY(row_pass(fr, g, s));
+                const bool last = s + 1 == fr.nsteps;
+                if (snaps && !last && (s + 1) % cr->every == 0) {
+                    const int64_t j = k - 1, fl = j / cr->per_block, slot = j % cr->per_block;
+                    const int blk = (int)(fl % cr->nblocks);
+                    if (slot == 0 && fl >= cr->nblocks && !cr->wait_for(cr->flushes_done, fl - cr->nblocks + 1))      // the block is written again
+                        return fail(SSFM_ERR_HIP, "ssfm_propagate_fixed_capture: the transfers failed");
+                    TimeArgs<T> te = targs(fr.gamma, fr.h[s] * (T)0.5, 0, nullptr, g * fr.rows, g);
+                    te.F = reinterpret_cast<cx<T>*>(cap_blocks + cap_block_bytes * (size_t)blk + cr->fb * (size_t)slot) + (size_t)(g * fr.rows) * n;
+                    ++last_launches;
+                    HIP_TRY((launch_time<T, TM_END>(N1, fr.rows, lane_stream[g], te, E)));
+                    if (slot == cr->per_block - 1 || k == cr->nsnap - 2) {          // the block is full (or the last one of the run): it leaves
+                        HIP_TRY(hipEventRecord(cap_ev_ends[g][fl], lane_stream[g]));
+                        cr->ends_done[g].store(fl + 1, std::memory_order_release);
+                    }
+                    ++k;
+                }
+                if (last && snaps && !in_place() && !cr->wait_for(cr->input_done, 1))    // (the input's transfer reads F, which the END overwrites)
+                    return fail(SSFM_ERR_HIP, "ssfm_propagate_fixed_capture: the transfers failed");
+                HIP_TRY(col_after(fr, g, s));
+            }
+            return SSFM_OK;
+        };
+        const int rc = body();
+        if (rc != SSFM_OK && cr) cr->failed.store(1);
+        return rc;
+    }
+    int fork_lanes(int nl) {
+        HIP_TRY(hipEventRecord(fork_ev, stream));
+        for (int g = 1; g < nl; ++g) HIP_TRY(hipStreamWaitEvent(lane_stream[g], fork_ev, 0));
+        return SSFM_OK;
+    }
+    int join_lanes(int nl) {
+        for (int g = 1; g < nl; ++g) {
+            HIP_TRY(hipEventRecord(lane_ev[g], lane_stream[g]));
+            HIP_TRY(hipStreamWaitEvent(stream, lane_ev[g], 0));
+        }
+        return SSFM_OK;
+    }
+    // the two-kernel engine's run on its lanes: every lane from a host thread of its own, or all of them from this thread
+    int run_lanes(const FixedRun& fr) {
+        const int nl = fr.nlanes;
+        if (cap_run != nullptr && nl == 1) return lane_run(fr, 0);
+        if (nl > 1 && ((lane_threads && !profiling && fr.nsteps >= 16) || cap_run != nullptr)) {
+            // every lane from a host thread of its own (LaneWorker): lane 0 from this one
+            if (int rc = fork_lanes(nl)) return rc;
+            for (int g = 1; g < nl; ++g) { lane_worker[g].start(device); lane_worker[g].submit([this, &fr, g] { return lane_run(fr, g); }); }
+            int rc = lane_run(fr, 0);
+            for (int g = 1; g < nl; ++g) { const int r = lane_worker[g].wait(); if (rc == SSFM_OK) rc = r; }
+            if (rc != SSFM_OK) return rc;
+            return join_lanes(nl);
+        }
+        // all lanes from this thread, interleaved: every lane's row pass, then every lane's column pass, step by step (one lane: the plan's stream alone)
+        if (nl > 1) if (int rc = fork_lanes(nl)) return rc;
+        for (int g = 0; g < nl; ++g) {
+            if (int rc = prof_mark(-1, g)) return rc;
+            HIP_TRY(col_begin(fr, g));
+            if (int rc = prof_mark(0, g)) return rc;
+        }
+        for (int64_t s = 0; s < fr.nsteps; ++s) {
+            for (int g = 0; g < nl; ++g) {
+                HIP_TRY(row_pass(fr, g, s));
+                if (int rc = prof_mark(1, g)) return rc;
+            }
+            for (int g = 0; g < nl; ++g) {
+                HIP_TRY(col_after(fr, g, s));
+                if (int rc = prof_mark(0, g)) return rc;
+            }
+        }
+        for (int g = 0; g < nl; ++g) if (int rc = prof_mark(2, g)) return rc;
+        return join_lanes(nl);
+    }
+    // snapshots of a small plan whose whole capture fits `dsnap`: the single launch writes every snapshot itself
+    int snapshots_small(const FixedRun& fr, void* snapshots, DeviceBuffer<char>& dsnap) {
+        const size_t fb = field_bytes();
+        hipError_t e = hipMemcpyAsync(dsnap, F, fb, hipMemcpyDeviceToDevice, stream);             // the input
+        int rc = e == hipSuccess ? run_small(fr.gamma, *fr.sch, reinterpret_cast<cx<T>*>(dsnap.get())) : fail(SSFM_ERR_HIP, "snapshot copy failed: %s", hipGetErrorString(e));
+        if (rc == SSFM_OK) {
+            e = hipMemcpyAsync(snapshots, dsnap, fb * (size_t)(fr.nsteps + 1), hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream);
+            if (e != hipSuccess) rc = fail(SSFM_ERR_HIP, "snapshot download failed: %s", hipGetErrorString(e));
+        }
+        dsnap.free();
+        return rc;
+    }
+    // ... of any other plan: BEGIN, row pass, END on the plan's stream for every step, the field copied into `dsnap` behind it; blocks of `block` snapshots go to the host
+    int snapshots_every_step(const FixedRun& fr, void* snapshots, DeviceBuffer<char>& dsnap, int64_t block) {
+        const size_t fb = field_bytes();
+        char* snap = static_cast<char*>(snapshots);
+        auto flush = [&](int64_t first, int64_t count) -> int {
+            hipError_t e = hipMemcpyAsync(snap + fb * first, dsnap, fb * (size_t)count, hipMemcpyDeviceToHost, stream);
+            if (e == hipSuccess) e = hipStreamSynchronize(stream);
+            if (e != hipSuccess) return fail(SSFM_ERR_HIP, "snapshot download failed: %s", hipGetErrorString(e));
+            return SSFM_OK;
+        };
+        int64_t first = 0, held = 0;                    // snapshots [first, first + held) are in dsnap
+        auto capture = [&]() -> hipError_t { return put_time_order(dsnap + fb * held++); };
+        hipError_t ce = capture();
+        for (int64_t s = 0; s < fr.nsteps && ce == hipSuccess; ++s) {
+            if (held == block) { if (int rc = flush(first, held)) return rc; first += held; held = 0; }
+            last_launches += 2;
+            ce = launch_time<T, TM_BEGIN>(N1, batch, stream, targs(fr.gamma, 0, fr.h[s] * (T)0.5, nullptr), E);
+            if (ce == hipSuccess) ce = row_launch(fr, s, 0, batch, stream);
+            if (ce == hipSuccess) ce = launch_time<T, TM_END>(N1, batch, stream, targs(fr.gamma, fr.h[s] * (T)0.5, 0, nullptr), E);
+            if (ce == hipSuccess) ce = capture();
+        }
+        if (ce != hipSuccess) return fail(SSFM_ERR_HIP, "snapshot run failed: %s", hipGetErrorString(ce));
+        if (int rc = flush(first, held)) return rc;
+        dsnap.free();                                   // (here, not behind the call: the run's closing event goes behind the wait that hipFree is)
         return SSFM_OK;
     }
 
@@ -1921,16 +1866,14 @@ template <typename T> struct PlanT : PlanBase {
     // steps; all of them without a capture), adaptive_finish (time-order field, z log).
     struct AdaptRun {
         bool active = false;
-        bool tile_private = false;     // U16 plans without capture: the field between END and BEGIN stays in the Y buffer
         T gamma = 0;
         T length = 0;
         int max_steps = 0;
         int step = 0;                  // index of the next step to launch
         StepState<T> now = {};         // state after the last launched step (host copy)
-        bool fused = false;            // column kernel of at most 128 workgroups, no capture: END + BEGIN in one launch (TM_MID_A)
-        bool medium = false;           // (deferred) a medium plan: the single-launch kernel is k_medium_adapt (one XCD)
-        bool deferred = false;         // small plan without capture: nothing launched yet -- the first adaptive_run decides between
-        int single_step = 0;           // the single-launch kernel (budget covers the run) and the chunked engine
+        bool fused = false, tile_private = false;      // the chunked engine's column pass (ssfm_route.hpp AdaptPiece)
+        AdaptBegin deferred = ADAPT_CHUNKED;      // a small or a medium plan without capture: nothing launched yet -- the first adaptive_run decides between
+        int single_step = 0;           // the single-launch kernel (budget covers the run; k_small_adapt, or k_medium_adapt on one XCD) and the chunked engine
         T phi_max = 0;
     } ar;
     // ---- z-resolved capture of an adaptive run that keeps the run's engine (ssfm_adaptive_set_capture, round 6).  The reference's own consumer calls FIBER with
@@ -1962,7 +1905,7 @@ template <typename T> struct PlanT : PlanBase {
     }
     int adaptive_set_capture(int64_t every, const int64_t* steps, int64_t n_steps, void* fields_host, int64_t capacity, int64_t* taken, int64_t* n_taken) {
         if (!ar.active) return fail(SSFM_ERR_STATE, "ssfm_adaptive_set_capture: call ssfm_adaptive_begin first");
-        if (ar.step != 0 || (!ar.deferred && ar.now.steps != 0)) return fail(SSFM_ERR_STATE, "ssfm_adaptive_set_capture: the run has started");
+        if (ar.step != 0 || (ar.deferred == ADAPT_CHUNKED && ar.now.steps != 0)) return fail(SSFM_ERR_STATE, "ssfm_adaptive_set_capture: the run has started");
         if ((every > 0) == (steps != nullptr && n_steps > 0)) return fail(SSFM_ERR_INVALID, "ssfm_adaptive_set_capture: either a stride or a list of step numbers");
         if (!fields_host || capacity < 1 || !taken || !n_taken) return fail(SSFM_ERR_INVALID, "ssfm_adaptive_set_capture: NULL argument");
         if (int rc = no_split("ssfm_adaptive_set_capture")) return rc;
@@ -1988,13 +1931,17 @@ template <typename T> struct PlanT : PlanBase {
         }
         if (int rc = ensure_cap_stream()) return rc;
         for (auto& e : acap_ev) if (!e) HIP_TRY(hipEventCreateWithFlags(e.out(), hipEventDisableTiming));
-        if (ar.deferred) {            // (a small plan: the capture needs the launch-per-pass engine)
+        if (ar.deferred != ADAPT_CHUNKED) {            // (a small plan: the capture needs the launch-per-pass engine)
             const AdaptRun keep = ar;
             if (int rc = adaptive_begin_chunked(keep.gamma, keep.length, keep.phi_max, keep.single_step, keep.max_steps, 0)) return rc;
         }
         return SSFM_OK;
     }
 
+    void adaptive_reset(T gamma, T length, T phi_max, int single_step, int max_steps) {
+        ar = AdaptRun();
+        ar.active = true; ar.gamma = gamma; ar.length = length; ar.phi_max = phi_max; ar.single_step = single_step; ar.max_steps = max_steps;
+    }
     int adaptive_begin(double gamma_d, double length, double phi_max, int single_step, int64_t max_steps, int capture) {
         if (!have_op) return fail(SSFM_ERR_STATE, "ssfm_propagate_adaptive: call ssfm_set_linear_operator first");
         if (max_steps < 1 || max_steps > (1ll << 30)) return fail(SSFM_ERR_INVALID, "ssfm_propagate_adaptive: max_steps=%lld", (long long)max_steps);
@@ -2006,26 +1953,11 @@ template <typename T> struct PlanT : PlanBase {
         last_engine = SSFM_ENGINE_NONE;
         acap.on = false;
         HIP_TRY(hipEventRecord(ev0, stream));
-        // (4096 x 2: the one-XCD engine, 8.1 us per step, before the one-workgroup kernel that holds both rows, 10.4)
-        bool med_adapt = false;
-        if constexpr (sizeof(T) == 4) {
-            const long long blocks = (long long)(N2 / cols_per_tile<T>()) * batch;
-            med_adapt = medium_ok && medium_adapt_ok && fused_ok && !capture && !single_step && u16 && E == 8 && Ef == 8 && Ef_fly == 8 && medium_shape(N1, N2)
-                        && twA != nullptr && blocks % kBarShards == 0 && blocks <= kBarWords && n * batch <= medium_max_samples;
-        }
-        if (small && !capture && small_adapt_supported<T>((int)n, batch) && !(med_adapt && n == 4096 && batch == 2)) {
-            ar = AdaptRun();
-            ar.active = true; ar.deferred = true;
-            ar.gamma = gamma; ar.length = (T)length; ar.phi_max = (T)phi_max; ar.max_steps = (int)max_steps; ar.single_step = single_step;
-            return SSFM_OK;
-        }
-        if (med_adapt) {
-            ar = AdaptRun();
-            ar.active = true; ar.deferred = true; ar.medium = true;
-            ar.gamma = gamma; ar.length = (T)length; ar.phi_max = (T)phi_max; ar.max_steps = (int)max_steps; ar.single_step = single_step;
-            return SSFM_OK;
-        }
-        return adaptive_begin_chunked(gamma, (T)length, (T)phi_max, single_step, (int)max_steps, capture);
+        const AdaptBegin route = adaptive_route<T>(shape, AdaptSwitches{medium_ok, medium_adapt_ok, fused_ok, twA != nullptr, medium_shape(N1, N2)}, capture != 0, single_step != 0);
+        if (route == ADAPT_CHUNKED) return adaptive_begin_chunked(gamma, (T)length, (T)phi_max, single_step, (int)max_steps, capture);
+        adaptive_reset(gamma, (T)length, (T)phi_max, single_step, (int)max_steps);
+        ar.deferred = route;
+        return SSFM_OK;
     }
     static constexpr int kAdaptChunkMax = 512;          // steps queued between two looks at the state, at most
     AdaptState<T> adapt_host;          // staging copy of the run's parameters (a member: the copy below is asynchronous)
@@ -2062,36 +1994,14 @@ template <typename T> struct PlanT : PlanBase {
         if (int rc = ensure_adapt_look()) return rc;
         HIP_TRY(hipMemcpyAsync(&adapt_look->now, reinterpret_cast<const char*>(st.get()) + offsetof(AdaptState<T>, cur), sizeof(StepState<T>), hipMemcpyDeviceToHost, stream));
         HIP_TRY(hipStreamSynchronize(stream));
-        const StepState<T> first = adapt_look->now;
-        ar = AdaptRun();
-        ar.now = first;
-        ar.active = true;
-        ar.gamma = gamma;
-        ar.length = (T)length;
-        ar.max_steps = (int)max_steps;
-        // U16 plans keep the time-domain field between END and the next BEGIN in the Y buffer, in tile-private 16-byte
-        // units (ssfm_kernels.hpp TM_END_Y / TM_BEGIN_Y); a z-resolved capture needs the time-order field after every
-        // step and uses the plain modes
-        ar.phi_max = phi_max;
-        ar.single_step = single_step;
-        // a column kernel of at most 64 workgroups (measured: a gain up to there, profiles/r02_medium_adaptive.txt) waits for the global maximum inside the launch (TM_MID_A); the input is kept
-        // for the case that the GPU does not run the grid as a whole (then: the three-launch engine, for good)
-        // Larger complex64 grids (up to 512 workgroups = two per CU: 2^20 x 2) take the same kernel with a hand-over that has no counter to
-        // serialise on (AdaptState::wgmax): the column pass is then ONE launch per step instead of two -- 64 MiB of field traffic per step
-        // instead of 96.
-        const long long col_blocks = (long long)(N2 / cols_per_tile<T>()) * batch;
-        long long fused_max = sizeof(T) == 4 ? kAdaptWords : kAdaptSlots;
+        adaptive_reset(gamma, length, phi_max, single_step, max_steps);
+        ar.now = adapt_look->now;
+        // the column pass: fused where the whole grid is resident at once (ssfm_route.hpp adaptive_piece; the CU count only matters to grids beyond kAdaptSlots)
         int cus = 0;
-        if (col_blocks > kAdaptSlots && (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess || col_blocks > 2ll * cus || col_blocks % 64 != 0))
-            fused_max = kAdaptSlots;                              // (the whole grid must be resident at once: two workgroups per CU)
-        ar.fused = fused_ok && !capture && (N1 == 128 || N1 == 256) && col_blocks <= fused_max && !is_split();
+        if (adaptive_col_blocks<T>(shape) > kAdaptSlots && hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) cus = 0;
+        const AdaptPiece piece = adaptive_piece<T>(shape, fused_ok, capture != 0, cus);
+        ar.fused = piece.fused; ar.tile_private = piece.tile_private;
         if (ar.fused) if (int rc = backup_field()) return rc;
-        // (Two engines that drove the polarisations of an adaptive run on two streams, a lane's kernel waiting INSIDE the launch for the other lane's
-        // maxima, were built in round 3 and removed in round 4: both lost their A/B -- 36-38 and 28.9-29.7 against 32-33 and 29.6-31.1 us per step at
-        // 2^20 x 2, profiles/r03_adaptive_two_lanes.txt, r03_adaptive_fused_large.txt -- and both stall until their patience runs out whenever the
-        // runtime maps the plan's two streams to ONE hardware queue, which it does when the number of live streams of the priority class is 3 mod 4:
-        // profiles/r04_order_dependence.txt.)
-        ar.tile_private = u16 && !capture && !ar.fused;
         return SSFM_OK;
     }
 
@@ -2101,81 +2011,81 @@ template <typename T> struct PlanT : PlanBase {
         if (!ar.active) return fail(SSFM_ERR_STATE, "ssfm_adaptive_run: no adaptive run in progress");
         if (budget < 1) return fail(SSFM_ERR_INVALID, "ssfm_adaptive_run: budget=%lld", (long long)budget);
         if (int rc = use_device()) return rc;
-        if (ar.deferred) {
+        int engine = last_engine;              // (a call that finds the run at its end takes no step and leaves the report as it is)
+        bool finished = false;                 // the whole run went in one launch
+        if (ar.deferred != ADAPT_CHUNKED) {
             if (snapshots != nullptr) return fail(SSFM_ERR_STATE, "ssfm_adaptive_run: the run was not begun with capture");
             const AdaptRun keep = ar;
-            if (keep.medium && budget >= (int64_t)keep.max_steps) {
-                if constexpr (sizeof(T) == 4) {
-                    // the whole run in one launch on one XCD (k_medium_adapt); the input is kept for the case that its workgroups do not all get to run
-                    const size_t fb = sizeof(cx<T>) * n * batch;
-                    if (int rc = backup_field()) return rc;
-                    if (int rc = upload_adapt_state(keep.gamma, keep.length, keep.phi_max, keep.max_steps)) return rc;
-                    hipLaunchKernelGGL(k_absmax<T>, dim3(1024), dim3(256), 0, stream, (const cx<T>*)F, (long long)n * batch, st);
-                    hipLaunchKernelGGL(k_step_control<T>, dim3(1), dim3(64), 0, stream, st, zlog, 0, 0, 0);
-                    last_launches += 2;
-                    MediumAdaptArgs<T> ma;                              // (no memset: the struct has no padding and every member is assigned)
-                    if (int rc = medium_prepare(ma, batch, 1)) return rc;        // (one launch for all rows: the first set of meeting words)
-                    ma.D = dperm; ma.st = st; ma.zlog = zlog;
-                    ma.gamma = keep.gamma; ma.inv_n = inv_n();
-                    ++last_launches;
-                    HIP_TRY(launch_medium_adapt(N1, N2, (int)ma.nblk, medium_xccs, stream, ma));
-                    unsigned gave_up[2] = {0u, 0u};
-                    if (int rc = medium_adapt_verdict(ma, gave_up, &ar.now)) return rc;
-                    if (!gave_up[0] && !gave_up[1]) {
-                        ar.deferred = false;
-                        last_engine = SSFM_ENGINE_MEDIUM_ADAPT;
-                        if (steps_total) *steps_total = ar.now.steps;
-                        if (done) *done = ar.now.done;
-                        return SSFM_OK;
-                    }
-                    // part of the grid never ran beside the rest: the same run on the chunked engine, which this plan then keeps to
-                    medium_gave_up(medium_adapt_ok);
-                    HIP_TRY(hipMemcpyAsync(F, fused_backup, fb, hipMemcpyDeviceToDevice, stream));
-                }
-            } else if (keep.medium) {
-                // (a caller that takes the run in pieces: the chunked engine)
-            } else
-            if (budget >= (int64_t)keep.max_steps) {
-                // the whole run in one launch (k_small_adapt); the state and the z log are read once, here
-                if (int rc = upload_adapt_state(keep.gamma, keep.length, keep.phi_max, keep.max_steps)) return rc;
-                SmallAdaptArgs<T> sa;
-                sa.F = F; sa.D = dsmall; sa.tw = tw_small; sa.st = st; sa.zlog = zlog; sa.gamma = keep.gamma; sa.inv_n = inv_n(); sa.single_step = keep.single_step;
-                ++last_launches;
-                HIP_TRY(launch_small_adapt<T>((int)n, batch, stream, sa));
-                HIP_TRY(hipMemcpyAsync(&ar.now, reinterpret_cast<const char*>(st.get()) + offsetof(AdaptState<T>, cur), sizeof(ar.now), hipMemcpyDeviceToHost, stream));
-                HIP_TRY(hipStreamSynchronize(stream));
-                ar.deferred = false;
-                last_engine = SSFM_ENGINE_SMALL_ADAPT;
-                if (steps_total) *steps_total = ar.now.steps;
-                if (done) *done = ar.now.done;
-                return SSFM_OK;
+            if (adaptive_one_launch(keep.deferred, budget, keep.max_steps)) {
+                if (int rc = keep.deferred == ADAPT_DEFER_MEDIUM ? run_deferred_medium(keep) : run_deferred_small(keep)) return rc;
+                finished = ar.deferred == ADAPT_CHUNKED;
+                if (finished) engine = adaptive_engine(keep.deferred);
             }
-            // a budgeted caller: the chunked engine from the start
-            if (int rc = adaptive_begin_chunked(keep.gamma, keep.length, keep.phi_max, keep.single_step, keep.max_steps, 0)) return rc;
+            // a budgeted caller (one that takes the run in pieces), or a medium run part of whose grid never ran beside the rest: the chunked engine from the start
+            if (!finished) if (int rc = adaptive_begin_chunked(keep.gamma, keep.length, keep.phi_max, keep.single_step, keep.max_steps, 0)) return rc;
         }
-        if (ar.fused && ar.step == 0 && budget < (int64_t)ar.max_steps) {
-            // a caller that takes the run in pieces gets the chunked engine (the fused kernel's launches are queued a whole run ahead);
-            // the field itself stays in the tile-private order until ssfm_adaptive_finish (include/ssfm_amd.h)
-            ar.fused = false;
-            ar.tile_private = u16;
+        if (!finished) if (int rc = adaptive_chunks(budget, snapshots, &engine)) return rc;
+        last_engine = engine;
+        if (steps_total) *steps_total = ar.now.steps;
+        if (done) *done = ar.now.done;
+        return SSFM_OK;
+    }
+    // ---- the deferred run in one launch.  ar.deferred stays as it is where the launch's workgroups did not all meet: the field is the input again
+    // a small plan (k_small_adapt); the state and the z log are read once, here
+    int run_deferred_small(const AdaptRun& keep) {
+        if (int rc = upload_adapt_state(keep.gamma, keep.length, keep.phi_max, keep.max_steps)) return rc;
+        SmallAdaptArgs<T> sa;
+        sa.F = F; sa.D = dsmall; sa.tw = tw_small; sa.st = st; sa.zlog = zlog; sa.gamma = keep.gamma; sa.inv_n = inv_n(); sa.single_step = keep.single_step;
+        ++last_launches;
+        HIP_TRY(launch_small_adapt<T>((int)n, batch, stream, sa));
+        HIP_TRY(hipMemcpyAsync(&ar.now, reinterpret_cast<const char*>(st.get()) + offsetof(AdaptState<T>, cur), sizeof(ar.now), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        ar.deferred = ADAPT_CHUNKED;
+        return SSFM_OK;
+    }
+    // a medium plan, on one XCD (k_medium_adapt); the input is kept for the case that its workgroups do not all get to run
+    int run_deferred_medium([[maybe_unused]] const AdaptRun& keep) {
+        if constexpr (sizeof(T) == 4) {
+            if (int rc = backup_field()) return rc;
+            if (int rc = upload_adapt_state(keep.gamma, keep.length, keep.phi_max, keep.max_steps)) return rc;
+            hipLaunchKernelGGL(k_absmax<T>, dim3(1024), dim3(256), 0, stream, (const cx<T>*)F, (long long)n * batch, st);
+            hipLaunchKernelGGL(k_step_control<T>, dim3(1), dim3(64), 0, stream, st, zlog, 0, 0, 0);
+            last_launches += 2;
+            MediumAdaptArgs<T> ma;                              // (no memset: the struct has no padding and every member is assigned)
+            if (int rc = medium_prepare(ma, batch, 1)) return rc;        // (one launch for all rows: the first set of meeting words)
+            ma.D = dperm; ma.st = st; ma.zlog = zlog;
+            ma.gamma = keep.gamma; ma.inv_n = inv_n();
+            ++last_launches;
+            HIP_TRY(launch_medium_adapt(N1, N2, (int)ma.nblk, medium_xccs, stream, ma));
+            unsigned gave_up[2] = {0u, 0u};
+            if (int rc = medium_adapt_verdict(ma, gave_up, &ar.now)) return rc;
+            if (!gave_up[0] && !gave_up[1]) { ar.deferred = ADAPT_CHUNKED; return SSFM_OK; }
+            // part of the grid never ran beside the rest: the same run on the chunked engine, which this plan then keeps to
+            medium_gave_up(medium_adapt_ok);
+            HIP_TRY(hipMemcpyAsync(F, fused_backup, field_bytes(), hipMemcpyDeviceToDevice, stream));
         }
-        const int nrows = N1 * batch;
-        const size_t fb = sizeof(cx<T>) * n * batch;
+        return SSFM_OK;
+    }
+    // ---- the chunked engine: up to `budget` more steps, queued in chunks with a look at the state in between
+    int adaptive_estimate() const {              // about (L - z) / h steps remain (the step only shrinks towards the clamp at L)
+        // Three quarters of them are queued before the next look at the state (a look drains the queue: 25-40 us) -- but the last two dozen all at
+        // once and two more: launches behind the end of the run find `done` and leave (a few us each), where the looks of a tail of 7, 2, 1 steps cost more
+        const double remain = ar.now.h > (T)0 ? ((double)ar.length - (double)ar.now.z) / (double)ar.now.h : 1.0;
+        const int est = remain > 1e6 ? kAdaptChunkMax : (remain <= 24.0 ? (int)remain + 3 : (int)(0.75 * remain) + 1);
+        return est < 2 ? 2 : (est > kAdaptChunkMax ? kAdaptChunkMax : est);
+    }
+    int adaptive_chunks(int64_t budget, void* snapshots, int* engine) {
+        const AdaptPiece piece = adaptive_in_pieces(AdaptPiece{ar.fused, ar.tile_private}, shape, ar.step, budget, ar.max_steps);
+        ar.fused = piece.fused; ar.tile_private = piece.tile_private;
+        const size_t fb = field_bytes();
         char* snap = static_cast<char*>(snapshots);
         if (snap && ar.tile_private) return fail(SSFM_ERR_STATE, "ssfm_adaptive_run: the run was not begun with capture");
         const int first_step = ar.now.steps;
-        auto estimate = [&]() {              // about (L - z) / h steps remain (the step only shrinks towards the clamp at L)
-            // Three quarters of them are queued before the next look at the state (a look drains the queue: 25-40 us) -- but the last two dozen all at
-            // once and two more: launches behind the end of the run find `done` and leave (a few us each), where the looks of a tail of 7, 2, 1 steps cost more
-            const double remain = ar.now.h > (T)0 ? ((double)ar.length - (double)ar.now.z) / (double)ar.now.h : 1.0;
-            const int est = remain > 1e6 ? kAdaptChunkMax : (remain <= 24.0 ? (int)remain + 3 : (int)(0.75 * remain) + 1);
-            return est < 2 ? 2 : (est > kAdaptChunkMax ? kAdaptChunkMax : est);
-        };
-        int chunk = snap ? 1 : estimate();
+        int chunk = snap ? 1 : adaptive_estimate();
         const bool fly_imag = !is_split() && fly_imag_ready();
         if (acap.on && snap) return fail(SSFM_ERR_STATE, "ssfm_adaptive_run: either ssfm_adaptive_set_capture or `snapshots`");
         while (!ar.now.done && ar.now.steps - first_step < budget) {
-            last_engine = is_split() ? SSFM_ENGINE_SPLIT_ADAPT : ar.fused ? SSFM_ENGINE_ADAPT_FUSED : SSFM_ENGINE_ADAPT_3;
+            *engine = adaptive_engine(shape, ar.fused);
             if ((int64_t)chunk > budget - (ar.now.steps - first_step)) chunk = (int)(budget - (ar.now.steps - first_step));
             // a capture run: this chunk's snapshots go to half (chunk_no & 1) of the ring, whose transfers of two chunks ago are waited for ON THE HOST
             std::vector<int64_t> chunk_caps;
@@ -2193,91 +2103,105 @@ template <typename T> struct PlanT : PlanBase {
                 if (acap.chunk_no >= 2) HIP_TRY(hipEventSynchronize(acap_ev[acap.chunk_no & 1]));      // (the transfers of the chunk before the last: NOT the last chunk's, which run beside this one)
                 ring_half = cap_blocks + fb * (size_t)acap.half_slots * (size_t)(acap.chunk_no & 1);
             }
-            for (int i = 0; i < chunk; ++i, ++ar.step) {
-                TimeArgs<T> tb = targs(ar.gamma, 0, 0, st), te = tb;
-                tb.step = te.step = ar.step;
-                tb.derive = i != 0;         // the first BEGIN of a chunk finds its state in cur[] (k_step_control wrote it)
-                if (ar.fused) {
-                    // BEGIN once; then FREQ + MID_A per step (MID_A(s) leaves the state of step s + 1 in cur[(s + 1) & 1])
-                    if (ar.step == 0) { tb.derive = 0; HIP_TRY((launch_time<T, TM_BEGIN>(N1, batch, stream, tb, E))); ++last_launches; }
-                } else if (ar.tile_private && ar.step > 0) HIP_TRY((launch_time<T, TM_BEGIN_Y>(N1, batch, stream, tb, E)));
-                else HIP_TRY((launch_time<T, TM_BEGIN>(N1, batch, stream, tb, E)));
-                FreqArgs<T> fa = fargs_fly(0, st);
-                fa.step = ar.step;
-                if (is_split()) {
-                    HIP_TRY(split_freq(nullptr, 0, st, ar.step, 0, batch, stream));
-                    last_launches += 2;
-                } else
-                if (fly_imag) {           // (half the operator's bytes: 23.7 -> 22.6 us per step at 2^20 x 2, the same bits)
-                    fa.tab = reinterpret_cast<const cx<T>*>(dimag_fly.get()); fa.amp = op_re0;
-                    HIP_TRY((launch_freq<T, FM_FLY_IM>(N2, nrows, stream, fa, Ef_fly)));
-                } else
-                HIP_TRY((launch_freq<T, FM_FLY>(N2, nrows, stream, fa, Ef_fly)));
-                if (acap.on && acap_wants((int64_t)ar.step + 1) && acap.count + (int64_t)chunk_caps.size() < acap.capacity) {
-                    // the capture step's extra launch: this step's time-order field into a ring slot (the step size is the device's: cur[step & 1])
-                    TimeArgs<T> tc = te;
-                    tc.F = reinterpret_cast<cx<T>*>(ring_half + fb * chunk_caps.size());
-                    HIP_TRY((launch_time<T, TM_END>(N1, batch, stream, tc, E)));
-                    ++last_launches;
-                    chunk_caps.push_back((int64_t)ar.step + 1);
-                    if ((int)chunk_caps.size() >= acap.half_slots || (acap.every == 0 && chunk_caps.size() >= 4 && i + 1 >= 64)) chunk = i + 1;          // (the half is full / enough to send: look at the state)
-                }
-                if (ar.fused) HIP_TRY((launch_time<T, TM_MID_A>(N1, batch, stream, te, E)));
-                else if (ar.tile_private) HIP_TRY((launch_time<T, TM_END_Y>(N1, batch, stream, te, E)));
-                else HIP_TRY((launch_time<T, TM_END>(N1, batch, stream, te, E)));
-                last_launches += ar.fused ? 2 : 3;
-            }
-            // the state after the last launched step, for the host (and for the first BEGIN of the next chunk)
-            if (!ar.fused) {
-                hipLaunchKernelGGL(k_step_control<T>, dim3(1), dim3(64), 0, stream, st, zlog, 1, 0, ar.step);
-                ++last_launches;
-            }
+            if (int rc = adaptive_enqueue_chunk(chunk, fly_imag, ring_half, chunk_caps)) return rc;
             const int before = ar.now.steps;
-            adapt_look->gave_up = 0u;
-            HIP_TRY(hipMemcpyAsync(&adapt_look->now, reinterpret_cast<const char*>(st.get()) + offsetof(AdaptState<T>, cur) + sizeof(StepState<T>) * (ar.step & 1),
-                                   sizeof(StepState<T>), hipMemcpyDeviceToHost, stream));
-            if (ar.fused) HIP_TRY(hipMemcpyAsync(&adapt_look->gave_up, reinterpret_cast<const char*>(st.get()) + offsetof(AdaptState<T>, error), sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-            HIP_TRY(hipStreamSynchronize(stream));
-            ar.now = adapt_look->now;
-            const unsigned gave_up = adapt_look->gave_up;
-            if (acap.on && !(ar.fused && gave_up)) {
-                // the chunk has run (the look above waited for it): its snapshots of steps really taken leave for the host beside the next chunk
-                for (size_t k = 0; k < chunk_caps.size(); ++k) {
-                    if (chunk_caps[k] > (int64_t)ar.now.steps) break;                       // (queued behind the end of the run: never written)
-                    HIP_TRY(hipMemcpyAsync(acap.host + fb * (size_t)acap.count, ring_half + fb * k, fb, hipMemcpyDeviceToHost, cap_stream));
-                    acap.taken[acap.count++] = chunk_caps[k];
-                }
-                *acap.n_taken = acap.count;
-                HIP_TRY(hipEventRecord(acap_ev[acap.chunk_no & 1], cap_stream));
-                ++acap.chunk_no;
-            }
+            unsigned gave_up = 0u;
+            if (int rc = adaptive_look(&gave_up)) return rc;
+            if (acap.on && !(ar.fused && gave_up)) if (int rc = adaptive_send_snapshots(chunk_caps, ring_half)) return rc;
             if (ar.fused && gave_up) {
-                // the grid did not run as a whole (another job holds CUs): the same run again on the three-launch engine
-                const AdaptRun keep = ar;
-                if (acap.on) { HIP_TRY(hipStreamSynchronize(cap_stream)); acap.count = 0; acap.next_in_list = 0; acap.chunk_no = 0; *acap.n_taken = 0; }
-                fused_ok = false;
-                last_fell_back = 1;
-                ++fallbacks;
-                HIP_TRY(hipMemcpyAsync(F, fused_backup, fb, hipMemcpyDeviceToDevice, stream));
-                if (int rc = adaptive_begin_chunked(keep.gamma, keep.length, keep.phi_max, keep.single_step, keep.max_steps, 0)) return rc;
-                chunk = estimate();
+                if (int rc = adaptive_fall_back()) return rc;
+                chunk = adaptive_estimate();
                 continue;
             }
             if (snap && ar.now.steps == before + 1) {        // (chunk = 1: the step just launched was really taken)
                 ran();
                 if (int rc = copy_field_out(snap + fb * (size_t)(before - first_step), false, true)) return rc;
             }
-            if (!snap && !ar.now.done) chunk = estimate();       // do not queue far beyond the end
+            if (!snap && !ar.now.done) chunk = adaptive_estimate();       // do not queue far beyond the end
         }
-        if (steps_total) *steps_total = ar.now.steps;
-        if (done) *done = ar.now.done;
         return SSFM_OK;
+    }
+    // enqueue one chunk: `chunk` steps from ar.step on (fewer where a capture fills its half of the ring: `chunk` then says how many)
+    int adaptive_enqueue_chunk(int& chunk, bool fly_imag, char* ring_half, std::vector<int64_t>& chunk_caps) {
+        const size_t fb = field_bytes();
+        for (int i = 0; i < chunk; ++i, ++ar.step) {
+            TimeArgs<T> tb = targs(ar.gamma, 0, 0, st), te = tb;
+            tb.step = te.step = ar.step;
+            tb.derive = i != 0;         // the first BEGIN of a chunk finds its state in cur[] (k_step_control wrote it)
+            if (ar.fused) {
+                // BEGIN once; then FREQ + MID_A per step (MID_A(s) leaves the state of step s + 1 in cur[(s + 1) & 1])
+                if (ar.step == 0) { tb.derive = 0; HIP_TRY((launch_time<T, TM_BEGIN>(N1, batch, stream, tb, E))); ++last_launches; }
+            } else if (ar.tile_private && ar.step > 0) HIP_TRY((launch_time<T, TM_BEGIN_Y>(N1, batch, stream, tb, E)));
+            else HIP_TRY((launch_time<T, TM_BEGIN>(N1, batch, stream, tb, E)));
+            FreqArgs<T> fa = fargs_fly(0, st);
+            fa.step = ar.step;
+            if (is_split()) {
+                HIP_TRY(split_freq(nullptr, 0, st, ar.step, 0, batch, stream));
+                last_launches += 2;
+            } else
+            if (fly_imag) {           // (half the operator's bytes: 23.7 -> 22.6 us per step at 2^20 x 2, the same bits)
+                fa.tab = reinterpret_cast<const cx<T>*>(dimag_fly.get()); fa.amp = op_re0;
+                HIP_TRY((launch_freq<T, FM_FLY_IM>(N2, N1 * batch, stream, fa, Ef_fly)));
+            } else
+            HIP_TRY((launch_freq<T, FM_FLY>(N2, N1 * batch, stream, fa, Ef_fly)));
+            if (acap.on && acap_wants((int64_t)ar.step + 1) && acap.count + (int64_t)chunk_caps.size() < acap.capacity) {
+                // the capture step's extra launch: this step's time-order field into a ring slot (the step size is the device's: cur[step & 1])
+                TimeArgs<T> tc = te;
+                tc.F = reinterpret_cast<cx<T>*>(ring_half + fb * chunk_caps.size());
+                HIP_TRY((launch_time<T, TM_END>(N1, batch, stream, tc, E)));
+                ++last_launches;
+                chunk_caps.push_back((int64_t)ar.step + 1);
+                if ((int)chunk_caps.size() >= acap.half_slots || (acap.every == 0 && chunk_caps.size() >= 4 && i + 1 >= 64)) chunk = i + 1;          // (the half is full / enough to send: look at the state)
+            }
+            if (ar.fused) HIP_TRY((launch_time<T, TM_MID_A>(N1, batch, stream, te, E)));
+            else if (ar.tile_private) HIP_TRY((launch_time<T, TM_END_Y>(N1, batch, stream, te, E)));
+            else HIP_TRY((launch_time<T, TM_END>(N1, batch, stream, te, E)));
+            last_launches += ar.fused ? 2 : 3;
+        }
+        return SSFM_OK;
+    }
+    // look at the state: where the run stands after the last launched step, for the host (and for the first BEGIN of the next chunk); waits for the chunk
+    int adaptive_look(unsigned* gave_up) {
+        if (!ar.fused) {
+            hipLaunchKernelGGL(k_step_control<T>, dim3(1), dim3(64), 0, stream, st, zlog, 1, 0, ar.step);
+            ++last_launches;
+        }
+        adapt_look->gave_up = 0u;
+        HIP_TRY(hipMemcpyAsync(&adapt_look->now, reinterpret_cast<const char*>(st.get()) + offsetof(AdaptState<T>, cur) + sizeof(StepState<T>) * (ar.step & 1),
+                               sizeof(StepState<T>), hipMemcpyDeviceToHost, stream));
+        if (ar.fused) HIP_TRY(hipMemcpyAsync(&adapt_look->gave_up, reinterpret_cast<const char*>(st.get()) + offsetof(AdaptState<T>, error), sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+        HIP_TRY(hipStreamSynchronize(stream));
+        ar.now = adapt_look->now; *gave_up = adapt_look->gave_up;
+        return SSFM_OK;
+    }
+    // send the chunk's snapshots: the chunk has run (the look waited for it), its snapshots of steps really taken leave for the host beside the next chunk
+    int adaptive_send_snapshots(const std::vector<int64_t>& chunk_caps, const char* ring_half) {
+        const size_t fb = field_bytes();
+        for (size_t k = 0; k < chunk_caps.size(); ++k) {
+            if (chunk_caps[k] > (int64_t)ar.now.steps) break;                       // (queued behind the end of the run: never written)
+            HIP_TRY(hipMemcpyAsync(acap.host + fb * (size_t)acap.count, ring_half + fb * k, fb, hipMemcpyDeviceToHost, cap_stream));
+            acap.taken[acap.count++] = chunk_caps[k];
+        }
+        *acap.n_taken = acap.count;
+        HIP_TRY(hipEventRecord(acap_ev[acap.chunk_no & 1], cap_stream));
+        ++acap.chunk_no;
+        return SSFM_OK;
+    }
+    // fall back from fused: the grid did not run as a whole (another job holds CUs) -- the same run again on the three-launch engine
+    int adaptive_fall_back() {
+        const AdaptRun keep = ar;
+        if (acap.on) { HIP_TRY(hipStreamSynchronize(cap_stream)); acap.count = 0; acap.next_in_list = 0; acap.chunk_no = 0; *acap.n_taken = 0; }
+        fused_ok = false;
+        last_fell_back = 1;
+        ++fallbacks;
+        HIP_TRY(hipMemcpyAsync(F, fused_backup, sizeof(cx<T>) * n * batch, hipMemcpyDeviceToDevice, stream));
+        return adaptive_begin_chunked(keep.gamma, keep.length, keep.phi_max, keep.single_step, keep.max_steps, 0);
     }
 
     int adaptive_finish(int64_t* steps_out, double* z_out) {
         if (!ar.active) return fail(SSFM_ERR_STATE, "ssfm_adaptive_finish: no adaptive run in progress");
         if (int rc = use_device()) return rc;
-        if (ar.deferred) {           // finished before any step was asked for: the chunked engine's begin leaves the same state behind
+        if (ar.deferred != ADAPT_CHUNKED) {           // finished before any step was asked for: the chunked engine's begin leaves the same state behind
             const AdaptRun keep = ar;
             if (int rc = adaptive_begin_chunked(keep.gamma, keep.length, keep.phi_max, keep.single_step, keep.max_steps, 0)) return rc;
         }

@@ -13,6 +13,7 @@
 //
 // so one SSFM step is two launches and each reads and writes the field exactly once.
 #pragma once
+#include "ssfm_route.hpp"
 #include "wgfft.hpp"
 
 // Timing-only ablation builds for tools/ablate.sh (results are WRONG when any bit is set): -DSSFM_ABLATE=<bits>
@@ -95,8 +96,6 @@ template <typename T> struct StepState {
     int done;
     int steps;      // steps taken so far
 };
-constexpr int kAdaptSlots = 64;
-constexpr int kAdaptWords = 512;       // workgroups of the largest fused adaptive column kernel (2^20 x 2: 256 tiles x 2 rows)
 template <typename T> struct AdaptState {
     T length;
     T phi_max;
@@ -159,9 +158,7 @@ __host__ __device__ __forceinline__ long long time_tw_pos(long long k1, long lon
 // (h, j mod 4, c8) loads the unit of row j + Q1 (2g + h), and ONE v_permlane32_swap per dword hands the h = 1
 // column's half to lane + 32 and takes that lane's h = 0 half (wavefront shuffle instead of a second pass
 // through memory): afterwards every thread holds rows 2g and 2g+1 of ITS column, as in the plain layout.
-template <typename T> __host__ __device__ constexpr bool u16_layout(int N1, int C, int E) {
-    return sizeof(T) == 4 && C == 16 && ((N1 / E) % 4) == 0 && N1 / E >= 4;
-}
+// (which plans are in it: ssfm_route.hpp u16_layout)
 // natural column of position `pos` of a row in the U16 order (inverse of freq_tab_pos)
 __host__ __device__ __forceinline__ long long u16_col_of_pos(long long pos, int Qf) {
     const long long u = pos >> 1, g = u / Qf, j = u % Qf;
@@ -1758,8 +1755,6 @@ template <typename T> struct MediumArgs {
     int rows;                          // batch rows
     int Qf;
 };
-constexpr int kBarShards = 8;
-constexpr int kBarWords = 64;          // one-XCD form: a flag word per workgroup (no atomics), behind the shards; then the error word and the ticket counter
 
 // The meeting of a one-XCD engine's workgroups: join() once, then meet() between two passes.
 struct Meeting {

@@ -24,9 +24,6 @@
 
 namespace ssfm {
 
-constexpr int kSplitLog2M = 20;            // sub-sequence length of a split plan (env SSFM_SPLIT_LOG2M = 20 | 21 | 22 overrides: diagnostics)
-constexpr int kSplitMaxR = 16;
-
 enum SplitMode { SM_TABLE = 0, SM_FLY = 1, SM_PHASE = 2 };       // SM_PHASE (complex64, a fibre's operator: one modulus for all frequencies): 4-byte phases, as k_freq<FM_PHASE>
 
 template <typename T> struct SplitArgs {

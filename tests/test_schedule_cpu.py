@@ -13,8 +13,8 @@ CSRC = os.path.join(ROOT, "opticomlib_amd", "csrc")
 def test_schedule_against_brute_force(tmp_path):
     cxx = shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
     assert cxx, "a host C++ compiler builds the program"
-    host = open(os.path.join(CSRC, "ssfm_host.hip")).read()
-    kmax = int(re.search(r"constexpr int kMaxTables = (\d+);", host).group(1))
+    route = open(os.path.join(CSRC, "ssfm_route.hpp")).read()
+    kmax = int(re.search(r"constexpr int kMaxTables = (\d+)[,;]", route).group(1))
     exe = str(tmp_path / "schedule_host")
     subprocess.run([cxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", f"-DK_MAX_TABLES={kmax}",
                     f"-I{CSRC}", "-o", exe, os.path.join(ROOT, "tests", "schedule_host.cpp")], check=True)
