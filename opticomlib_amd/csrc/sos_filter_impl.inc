@@ -683,7 +683,6 @@ struct SosLink {
 #else
 #define SOS_MARK(i) do { } while (0)
 #endif
-constexpr int kLookIter = 2;      // a workgroup looks back over at most kLookIter x (its threads) groups: the one-launch form's limit on groups per row
 
 // No fences in the hand-over: an agent-scope release / acquire is a write-back / invalidate of the XCD's whole L2 on gfx950
 // (buffer_wbl2 / buffer_inv sc1), and with 684 workgroups doing both twice a 2^20 x 2 call took 141 us, its workgroups 12 to 55 us
@@ -921,7 +920,6 @@ __device__ __forceinline__ void group_start(const SosLink& L, const double* Tb, 
 // an element of (M^group)^d at or above 1e-40, over the 64 powers it builds anyway; SosLink::look = 0 when that is more than kNear) and a workgroup then waits
 // for `look` totals instead of for all the earlier ones of its row (up to 227 at 2^20: 2.5 us of a wait of 7, profiles/r05_final_sos_timeline.txt).  Every
 // wavefront polls and sums by itself -- uniform addresses: one request per instruction -- so no reduction across lanes or wavefronts follows.
-constexpr int kNear = 4;
 template <int K, int CH>
 __device__ __forceinline__ void group_start_near(const SosLink& L, const unsigned long long* Ub, int g, const double* __restrict__ pwG, double (&acc)[CH][K], int* s_fail) {
     constexpr int N = CH * K;
@@ -1589,348 +1587,59 @@ __global__ __launch_bounds__(kWave * W) __attribute__((amdgpu_waves_per_eu(NS <=
     SOS_MARK(12);
 }
 
-template <int NS, int W> void build_tables(const SosCoefs& c, std::vector<double>& tab) {
-    constexpr int K = 2 * NS;
-    constexpr int kWaves = W;
-    double M[K * K];
-    // column q of A^kChunk = state after kChunk zero-input steps from the unit state e_q
-    for (int q = 0; q < K; ++q) {
-        double z[NS][2];
-        for (int s = 0; s < NS; ++s) z[s][0] = z[s][1] = 0.0;
-        z[q / 2][q % 2] = 1.0;
-        for (int i = 0; i < kChunk; ++i) {
-            double x = 0.0;
-            for (int s = 0; s < NS; ++s) {
-                const double xn = x;
-                x = c.b0[s] * xn + z[s][0];
-                z[s][0] = c.b1[s] * xn - c.a1[s] * x + z[s][1];
-                z[s][1] = c.b2[s] * xn - c.a2[s] * x;
-            }
-        }
-        for (int r = 0; r < K; ++r) M[r * K + q] = z[r / 2][r % 2];
-    }
-    // G[k][t]: component k of the state at the end of a chunk whose only non-zero sample is a 1 at position t
-    std::vector<double> G((size_t)K * kChunk, 0.0);
-    for (int t = 0; t < kChunk; ++t) {
-        double z[NS][2];
-        for (int s = 0; s < NS; ++s) z[s][0] = z[s][1] = 0.0;
-        for (int i = t; i < kChunk; ++i) {
-            double x = i == t ? 1.0 : 0.0;
-            for (int s = 0; s < NS; ++s) {
-                const double xn = x;
-                x = c.b0[s] * xn + z[s][0];
-                z[s][0] = c.b1[s] * xn - c.a1[s] * x + z[s][1];
-                z[s][1] = c.b2[s] * xn - c.a2[s] * x;
-            }
-        }
-        for (int k = 0; k < K; ++k) G[(size_t)k * kChunk + t] = z[k / 2][k % 2];
-    }
-    tab.assign((size_t)3 * (kWave + 1) * K * K, 0.0);
-    for (int level = 0; level < 3; ++level) {
-        double* P = tab.data() + (size_t)level * (kWave + 1) * K * K;
-        for (int r = 0; r < K; ++r) P[r * K + r] = 1.0;
-        for (int j = 0; j < kWave; ++j) matmul<K>(M, P + (size_t)j * K * K, P + (size_t)(j + 1) * K * K);
-        std::memcpy(M, P + (size_t)kWave * K * K, sizeof(M));                 // M^64 of this level
-        if (level == 0) {                                                     // group map = (M^64)^kWaves
-            double A[K * K], B[K * K];
-            std::memcpy(A, M, sizeof(M));
-            for (int w = 1; w < kWaves; ++w) { matmul<K>(M, A, B); std::memcpy(A, B, sizeof(A)); }
-            std::memcpy(M, A, sizeof(M));
-        }
-    }
-    tab.insert(tab.end(), G.begin(), G.end());                 // (behind the three levels of matrix powers)
-}
 
-// The single-meeting kernels' maps (meet_states): what a unit start state e_q of a GROUP adds, through the group's forward outputs, to the backward state at the
-// start of every chunk of the group (Vm, element-major over the threads) and at the group's end (Wm).  [0]: a whole group; [1]: the row's last group, whose
-// sequence ends at position `jl` of the group -- behind it the virtual copies of that output, and the backward pass starts from zi * that output.
-template <int NS, int W> void build_meet_tables(const SosCoefs& c, const double* zi, long long jl, std::vector<double>& out) {
-    constexpr int K = 2 * NS, kGroup = kWave * W;
-    constexpr long long Lg = (long long)kGroup * kChunk;
-    const auto step = [&](double (&z)[NS][2], double x) {
-        for (int s = 0; s < NS; ++s) {
-            const double xn = x;
-            x = c.b0[s] * xn + z[s][0];
-            z[s][0] = c.b1[s] * xn - c.a1[s] * x + z[s][1];
-            z[s][1] = c.b2[s] * xn - c.a2[s] * x;
-        }
-        return x;
-    };
-    out.assign((size_t)2 * K * K * kGroup + 2 * K * K, 0.0);
-    std::vector<double> dy((size_t)Lg);
-    for (int variant = 0; variant < 2; ++variant) {
-        double* Vm = out.data() + (size_t)variant * K * K * kGroup;
-        double* Wm = out.data() + (size_t)2 * K * K * kGroup + (size_t)variant * K * K;
-        const long long end = variant ? jl : Lg - 1;
-        for (int q = 0; q < K; ++q) {
-            double z[NS][2];
-            for (int s = 0; s < NS; ++s) z[s][0] = z[s][1] = 0.0;
-            z[q / 2][q % 2] = 1.0;
-            for (long long j = 0; j <= end; ++j) dy[(size_t)j] = step(z, 0.0);
-            for (long long j = end + 1; j < Lg; ++j) dy[(size_t)j] = dy[(size_t)end];
-            double zb[NS][2];
-            for (int s = 0; s < NS; ++s) { zb[s][0] = variant ? zi[2 * s] * dy[(size_t)end] : 0.0; zb[s][1] = variant ? zi[2 * s + 1] * dy[(size_t)end] : 0.0; }
-            for (int pos = kGroup - 1; pos >= 0; --pos) {
-                for (int r = 0; r < K; ++r) Vm[(size_t)(r * K + q) * kGroup + pos] = zb[r / 2][r % 2];
-                for (int t = kChunk - 1; t >= 0; --t) (void)step(zb, dy[(size_t)pos * kChunk + t]);
-            }
-            for (int r = 0; r < K; ++r) Wm[r * K + q] = zb[r / 2][r % 2];
-        }
-    }
-}
+// ------------------------------------------------------------------------------------------ host glue
+// What has to name a kernel instance of this chunk length; everything else of the host side is sos_filter.hip (its driver takes `Instances` as a parameter).
+struct Instances {
+    static constexpr int chunk = kChunk;
+    using Link = SosLink;
 
-// Workgroups of k_filtfilt the device holds at once.  The runtime's occupancy answer is cut to what the LDS allows with the 512-byte
-// allocation granule and the 161 280 usable bytes measured on gfx950 (three workgroups of 53 760 B fit a CU, three of 54 272 B do not:
-// profiles/r03_sosfilt.txt) -- a grid that waits for workgroups that cannot start would only end by its patience.
-template <int NS, int CH, int W, bool MEET = false> long long one_launch_capacity() {
-    static long long cap = -1;                                  // (calls are serialised by Workspace::mu)
-    if (cap >= 0) return cap;
-    int per_cu = 0, cus = 0, dev = 0;
-    hipFuncAttributes fa;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_filtfilt<NS, CH, W, MEET>, kWave * W, 0) != hipSuccess ||
-        hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k_filtfilt<NS, CH, W, MEET>)) != hipSuccess) {
-        (void)hipGetLastError();
-        return cap = 0;
+    // Workgroups of k_filtfilt the device holds at once.  The runtime's occupancy answer is cut to what the LDS allows with the 512-byte
+    // allocation granule and the 161 280 usable bytes measured on gfx950 (three workgroups of 53 760 B fit a CU, three of 54 272 B do not:
+    // profiles/r03_sosfilt.txt) -- a grid that waits for workgroups that cannot start would only end by its patience.
+    template <int NS, int CH, int W, bool MEET = false> static long long one_launch_capacity() {
+        static long long cap = -1;                                  // (calls are serialised by Workspace::mu)
+        if (cap >= 0) return cap;
+        int per_cu = 0, cus = 0, dev = 0;
+        hipFuncAttributes fa;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, k_filtfilt<NS, CH, W, MEET>, kWave * W, 0) != hipSuccess ||
+            hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k_filtfilt<NS, CH, W, MEET>)) != hipSuccess) {
+            (void)hipGetLastError();
+            return cap = 0;
+        }
+        const long long lds = ((long long)fa.sharedSizeBytes + 511) / 512 * 512;
+        const long long by_lds = lds > 0 ? 161280 / lds : per_cu;
+        return cap = (long long)cus * (per_cu < by_lds ? per_cu : by_lds);
     }
-    const long long lds = ((long long)fa.sharedSizeBytes + 511) / 512 * 512;
-    const long long by_lds = lds > 0 ? 161280 / lds : per_cu;
-    return cap = (long long)cus * (per_cu < by_lds ? per_cu : by_lds);
-}
 
-// Would a call of this size take the one-launch form here?  (The dispatcher asks the long-chunk instance before it prefers it.)
-template <int NS, int CH, int W>
-bool one_launch_would_run(const Workspace& w, const SosCoefs& c, long long n, int rows, int edge) {
-    constexpr int kGroup = kWave * W;
-    const long long m = n + 2ll * edge, nchunks = (m + kChunk - 1) / kChunk, ngroups = (nchunks + kGroup - 1) / kGroup;
-    // (rows of more than kLookIter x threads groups: only when a group's start state needs its nearest totals alone -- group_start_near)
-    const bool groups_ok = ngroups <= kLookIter * kGroup || (CH * 2 * NS <= 8 && ngroups <= kWave * kWave && near_is_certain<NS>(c, (long long)kGroup * kChunk));
-    return one_launch_enabled() && w.give_ups < kMaxGiveUps && groups_ok && ngroups * rows <= one_launch_capacity<NS, CH, W>();
-}
+    // the one launch; `tab`: the filter's device table (sos_tables.hpp TableLayout); p.src / p.mv set by the caller
+    template <int NS, int CH, int W>
+    static void launch_one(bool meet, dim3 grid, hipStream_t stream, const SosCoefs& c, const SosPass& p, int nchunks, int ngroups, const double* tab, double* d_res, const SosLink& L) {
+        using Lay = ssfm::sos::TableLayout<NS, kChunk>;
+        const dim3 block(kWave * W);
+        const double *d_zi = tab + Lay::zi, *d_pw = tab + Lay::pw, *d_pwG = tab + Lay::pwG, *d_pwH = tab + Lay::pwH, *d_G = tab + Lay::G;
+        if constexpr (CH * 2 * NS <= 8) {
+            if (meet) hipLaunchKernelGGL((k_filtfilt<NS, CH, W, true>), grid, block, 0, stream, c, p, nchunks, ngroups, d_zi, d_pw, d_pwG, d_pwH, d_G, d_res, L);
+        }
+        if (!meet) hipLaunchKernelGGL((k_filtfilt<NS, CH, W>), grid, block, 0, stream, c, p, nchunks, ngroups, d_zi, d_pw, d_pwG, d_pwH, d_G, d_res, L);
+    }
 
-template <int NS, int CH, int W>
-int run_filter_w(Workspace& w, const SosCoefs& c, const double* sos_key, const double* zi_h, const double* x, double* y,
-               long long n, int rows, int edge, bool on_device) {
-    constexpr int K = 2 * NS;
-    constexpr int kGroup = kWave * W;
-    const long long m = n + 2ll * edge;
-    const long long nchunks_ll = (m + kChunk - 1) / kChunk;
-    if (nchunks_ll > (1ll << 30)) return fail(SSFM_ERR_UNSUPPORTED, "ssfm_sosfiltfilt: n=%lld too long", n);
-    const int nchunks = (int)nchunks_ll;
-    const int ngroups = (nchunks + kGroup - 1) / kGroup;
-    if (ngroups > kWave * kWave)
-        return fail(SSFM_ERR_UNSUPPORTED, "ssfm_sosfiltfilt: n=%lld exceeds %d samples per row", n, kWave * kWave * kGroup * kChunk - 2 * edge);
-    if ((long long)ngroups * rows > 0x7fffffffll) return fail(SSFM_ERR_UNSUPPORTED, "ssfm_sosfiltfilt: %d rows of %lld samples exceed the grid", rows, n);
-    const size_t xbytes = sizeof(double) * (size_t)n * rows * CH;
-    if (!w.stream) {
-        WS_TRY(hipStreamCreateWithFlags(&w.stream, hipStreamNonBlocking));
-        WS_TRY(hipEventCreate(&w.ev0));
-        WS_TRY(hipEventCreate(&w.ev1));
-    }
-    if (!on_device) WS_TRY(w.need(0, xbytes));
-    WS_TRY(w.need(1, sizeof(double) * (size_t)m * rows * CH));
-    WS_TRY(w.need(2, sizeof(double) * (size_t)ngroups * kGroup * rows * CH * K));
-    WS_TRY(w.need(3, sizeof(double) * (size_t)ngroups * rows * CH * K * 2));           // T of the forward and of the backward pass
-    WS_TRY(w.need(4, sizeof(double) * (size_t)ngroups * kGroup * rows * CH * K));       // E of the backward pass (written by the forward output kernel)
-    const size_t pow_doubles = (size_t)3 * (kWave + 1) * K * K;
-    const size_t tab_doubles = pow_doubles + (size_t)K * kChunk;          // matrix powers, then G
-    const size_t tr_doubles = (size_t)2 * K * K * kWave;                  // behind zi: the lane powers and the group powers once more, element-major (SosLink::pwT)
-    WS_TRY(w.need(5, sizeof(double) * (tab_doubles + K + tr_doubles)));
-    // tables + zi: rebuilt only when the filter changes
-    std::vector<double> key(sos_key, sos_key + 6 * NS);
-    key.insert(key.end(), zi_h, zi_h + K);
-    key.push_back((double)W);                              // the group map is (M^64)^W
-    key.push_back((double)kChunk);                         // the chunk map is A^kChunk
-    if (key != w.table_key) {
-        std::vector<double> tab;
-        build_tables<NS, W>(c, tab);
-        tab.insert(tab.end(), zi_h, zi_h + K);
-        for (int level = 0; level < 2; ++level)
-            for (int e = 0; e < K * K; ++e)
-                for (int j = 0; j < kWave; ++j) tab.push_back(tab[(size_t)level * (kWave + 1) * K * K + (size_t)j * K * K + e]);
-        WS_TRY(hipMemcpyAsync(w.buf[5], tab.data(), sizeof(double) * tab.size(), hipMemcpyHostToDevice, w.stream));
-        WS_TRY(hipStreamSynchronize(w.stream));            // `tab` is a local
-        w.table_key = key;
-        // how many powers of the group map matter (group_start_near): 1 + the last d whose (M^group)^d has an element at or above 1e-40
-        w.look = 1;
-        for (int d = 1; d <= kWave; ++d) {
-            const double* P = tab.data() + (size_t)(kWave + 1) * K * K + (size_t)d * K * K;
-            double big = 0.0;
-            for (int e = 0; e < K * K; ++e) big = std::fabs(P[e]) > big || P[e] != P[e] ? std::fabs(P[e]) : big;
-            if (!(big < 1e-40)) w.look = d + 1;
-        }
-    }
-    const double* d_pw = w.buf[5];
-    const double* d_pwG = w.buf[5] + (size_t)(kWave + 1) * K * K;
-    const double* d_pwH = w.buf[5] + (size_t)2 * (kWave + 1) * K * K;
-    const double* d_G = w.buf[5] + pow_doubles;
-    const double* d_zi = w.buf[5] + tab_doubles;
-    const double* d_x = x;
-    double* d_out = y;
-    if (!on_device) {
-        WS_TRY(hipMemcpyAsync(w.buf[0], x, xbytes, hipMemcpyHostToDevice, w.stream));
-        d_x = w.buf[0];
-        d_out = w.buf[0];          // the backward pass writes the trimmed result over the staged input
-    }
-    SosPass p;
-    p.n = n; p.m = m; p.edge = edge;
-    const dim3 grid((unsigned)(ngroups * rows)), block(kGroup);
-    // ---- one launch, when the whole grid is resident at once.  The result never lands on the input (a call that gives up is repeated
-    // from it): an in-place call's goes to the scratch buffer first and is copied over the input afterwards.
-    const bool overlap = on_device && !(reinterpret_cast<const char*>(y) + xbytes <= reinterpret_cast<const char*>(x) ||
-                                        reinterpret_cast<const char*>(x) + xbytes <= reinterpret_cast<const char*>(y));
-    if (w.give_ups >= kMaxGiveUps && ++w.rested >= kRestCalls) { w.give_ups = kMaxGiveUps - 1; w.rested = 0; }
-    const bool near_now = CH * K <= 8 && sos_near_enabled() && w.look <= kNear;
-    if (one_launch_enabled() && w.give_ups < kMaxGiveUps && (ngroups <= kLookIter * kGroup || near_now) &&
-        (long long)grid.x <= one_launch_capacity<NS, CH, W>()) {
-        const size_t tdoubles = (size_t)2 * grid.x * CH * K;
-        if (tdoubles > w.link_T_cap) {
-            if (w.link_T) (void)hipFree(w.link_T);
-            w.link_T = nullptr; w.link_T_cap = 0;
-            WS_TRY(hipMalloc(&w.link_T, sizeof(double) * tdoubles));
-            w.link_T_cap = tdoubles;
-        }
-        if ((size_t)2 * grid.x > w.link_flag_cap) {
-            if (w.link_flag) (void)hipFree(w.link_flag);
-            w.link_flag = nullptr; w.link_flag_cap = 0;
-            WS_TRY(hipMalloc(&w.link_flag, sizeof(unsigned) * 2 * grid.x));
-            WS_TRY(hipMemsetAsync(w.link_flag, 0, sizeof(unsigned) * 2 * grid.x, w.stream));
-            w.link_flag_cap = (size_t)2 * grid.x;
-            w.epoch = 0;
-        }
-        const size_t uwords = (size_t)2 * grid.x * CH * K * 2;           // tagged totals: 16 bytes per value
-        if (uwords > w.link_U_cap) {
-            if (w.link_U) (void)hipFree(w.link_U);
-            w.link_U = nullptr; w.link_U_cap = 0;
-            WS_TRY(hipMalloc(&w.link_U, sizeof(unsigned long long) * uwords));
-            WS_TRY(hipMemsetAsync(w.link_U, 0, sizeof(unsigned long long) * uwords, w.stream));      // (no tag is 0)
-            w.link_U_cap = uwords;
-        }
-        if (!w.status) WS_TRY(hipHostMalloc(&w.status, 64, hipHostMallocMapped));
-        if (++w.epoch == 0) {                                  // (the counter wrapped: old flags could match again)
-            WS_TRY(hipMemsetAsync(w.link_flag, 0, sizeof(unsigned) * w.link_flag_cap, w.stream));
-            w.epoch = 1;
-        }
-        *w.status = 0;
-        SosLink L;
-        L.T = w.link_T; L.flag = w.link_flag; L.status = w.status; L.epoch = w.epoch; L.patience = one_launch_patience();
-        L.U = w.link_U; L.tag = ++w.link_tag;
-        L.pwT = w.buf[5] + tab_doubles + K; L.pwGT = L.pwT + (size_t)K * K * kWave;
-        L.tl = nullptr;
-        L.look = near_now ? w.look : 0;
-        L.meetV = nullptr; L.meetW = nullptr;
-        bool meet = false;
-        if constexpr (CH * K <= 8) {
-            meet = sos_meet_enabled() && L.look >= 1 && L.look <= 2 && (long long)grid.x <= one_launch_capacity<NS, CH, W, true>();
-            if (meet) {
-                // the maps of the row's last group depend on where the padded row ends inside it
-                const long long jl = (m - 1) - (long long)(ngroups - 1) * kGroup * kChunk;
-                std::vector<double> mkey(w.table_key);
-                mkey.push_back((double)jl);
-                const size_t mdoubles = (size_t)2 * K * K * kGroup + 2 * K * K;
-                if (mkey != w.meet_key) {
-                    if (mdoubles > w.meet_cap) {
-                        if (w.meet_tab) (void)hipFree(w.meet_tab);
-                        w.meet_tab = nullptr; w.meet_cap = 0; w.meet_key.clear();
-                        WS_TRY(hipMalloc(&w.meet_tab, sizeof(double) * mdoubles));
-                        w.meet_cap = mdoubles;
-                    }
-                    std::vector<double> mt;
-                    build_meet_tables<NS, W>(c, zi_h, jl, mt);
-                    WS_TRY(hipMemcpyAsync(w.meet_tab, mt.data(), sizeof(double) * mt.size(), hipMemcpyHostToDevice, w.stream));
-                    WS_TRY(hipStreamSynchronize(w.stream));
-                    w.meet_key = mkey;
-                }
-                L.meetV = w.meet_tab; L.meetW = w.meet_tab + (size_t)2 * K * K * kGroup;
-            }
-        }
-#if SOS_TIMELINE
-        static long long* d_tl = nullptr; static size_t tl_cap = 0;
-        if (std::getenv("SOS_TIMELINE_DUMP")) {
-            if (tl_cap < grid.x) { if (d_tl) (void)hipFree(d_tl); WS_TRY(hipMalloc(&d_tl, sizeof(long long) * 16 * grid.x)); tl_cap = grid.x; }
-            L.tl = d_tl;
-        }
-#endif
-        double* const d_res = (!on_device || overlap) ? w.buf[1] : y;
-        p.backward = 0; p.src = d_x; p.mv = m;
-        WS_TRY(hipEventRecord(w.ev0, w.stream));
-        if constexpr (CH * K <= 8) {
-            if (meet) hipLaunchKernelGGL((k_filtfilt<NS, CH, W, true>), grid, block, 0, w.stream, c, p, nchunks, ngroups, d_zi, d_pw, d_pwG, d_pwH, d_G, d_res, L);
-        }
-        if (!meet) hipLaunchKernelGGL((k_filtfilt<NS, CH, W>), grid, block, 0, w.stream, c, p, nchunks, ngroups, d_zi, d_pw, d_pwG, d_pwH, d_G, d_res, L);
-        WS_TRY(hipGetLastError());
-        WS_TRY(hipEventRecord(w.ev1, w.stream));
-        if (!on_device) WS_TRY(hipMemcpyAsync(y, d_res, xbytes, hipMemcpyDeviceToHost, w.stream));
-        WS_TRY(hipStreamSynchronize(w.stream));
-        if (*w.status == 0 && on_device && overlap) {
-            WS_TRY(hipMemcpyAsync(y, d_res, xbytes, hipMemcpyDeviceToDevice, w.stream));
-            WS_TRY(hipStreamSynchronize(w.stream));
-        }
-#if SOS_TIMELINE
-        if (L.tl) {
-            // per phase: when the first, the median and the last workgroup got there, in us after the first workgroup's start; then a few workgroups' own lines
-            std::vector<long long> h((size_t)16 * grid.x);
-            WS_TRY(hipMemcpy(h.data(), L.tl, sizeof(long long) * h.size(), hipMemcpyDeviceToHost));
-            long long t0 = h[0];
-            for (unsigned b = 0; b < grid.x; ++b) t0 = h[(size_t)b * 16] < t0 ? h[(size_t)b * 16] : t0;
-            static const char* names[14] = {"start", "loaded", "chunk sums", "scanned", "total stored", "flag raised", "forward start state", "forward outputs",
-                                            "backward scanned", "backward flag raised", "backward start state", "backward outputs", "end", "(forward chunk state)"};
-            constexpr int kMarks = 14;
-            for (int i = 0; i < kMarks; ++i) {
-                std::vector<double> v;
-                for (unsigned b = 0; b < grid.x; ++b) v.push_back((h[(size_t)b * 16 + i] - t0) * 0.01);
-                std::sort(v.begin(), v.end());
-                std::fprintf(stderr, "%2d %-22s first %6.2f  median %6.2f  last %6.2f us\n", i, names[i], v.front(), v[v.size() / 2], v.back());
-            }
-            const char* path = std::getenv("SOS_TIMELINE_DUMP");
-            if (path && path[0] == '/') {          // every workgroup: index, HW_ID, XCC_ID, the marks in us
-                if (FILE* f = std::fopen(path, "w")) {
-                    for (unsigned b = 0; b < grid.x; ++b) {
-                        std::fprintf(f, "%u %lld %lld", b, h[(size_t)b * 16 + 14], h[(size_t)b * 16 + 15] & 0xf);
-                        for (int i = 0; i < kMarks; ++i) std::fprintf(f, " %.2f", (h[(size_t)b * 16 + i] - t0) * 0.01);
-                        std::fprintf(f, "\n");
-                    }
-                    std::fclose(f);
-                }
-            }
-            for (unsigned b = 0; b < grid.x; b += grid.x / 6 ? grid.x / 6 : 1) {
-                std::fprintf(stderr, "  workgroup %4u:", b);
-                for (int i = 0; i < kMarks; ++i) std::fprintf(stderr, " %6.2f", (h[(size_t)b * 16 + i] - t0) * 0.01);
-                std::fprintf(stderr, "\n");
-            }
-        }
-#endif
-        if (*w.status == 0) {
-            WS_TRY(hipEventElapsedTime(&w.last_ms, w.ev0, w.ev1));
-            w.last_launches = 1;
-            const int route[8] = {W, kChunk, 1, L.look, CH * K <= 8, meet, NS, CH};
-            std::memcpy(w.last_route, route, sizeof(route));
-            w.give_ups = 0;
-            return SSFM_OK;
-        }
-        ++w.give_ups;                                          // part of the grid never ran beside the rest: three launches from the untouched input
-    }
-    double *d_y1 = w.buf[1], *d_E = w.buf[2], *d_T = w.buf[3];
-    w.last_launches = 3;
-    const int route[8] = {W, kChunk, 3, 0, 0, 0, NS, CH};           // (the three-launch form sums all totals and has neither tags nor flags)
-    std::memcpy(w.last_route, route, sizeof(route));
-    WS_TRY(hipEventRecord(w.ev0, w.stream));
-    // One stream: splitting the rows over two streams (as the propagator does) was measured SLOWER here
-    // (145 vs 121 us for 2 x 2^20 complex) -- every kernel is a short latency chain, not a bandwidth phase.
     // Three launches per call: chunk pass (forward), output pass (forward) + chunk pass (backward) in one kernel, output pass (backward).
-    double *d_E2 = w.buf[4], *d_T2 = w.buf[3] + (size_t)ngroups * rows * CH * K;
-    p.backward = 0; p.src = d_x; p.mv = m;
-    hipLaunchKernelGGL((k_chunk_scan<NS, CH, W>), grid, block, 0, w.stream, p, nchunks, ngroups, d_pw, d_G, d_E, d_T);
-    hipLaunchKernelGGL((k_apply<NS, CH, W>), grid, block, 0, w.stream, c, p, nchunks, ngroups, d_zi, d_pw, d_pwG, d_pwH, (const double*)d_E,
-                       (const double*)d_T, d_y1, d_out, d_G, d_E2, d_T2);
-    p.backward = 1; p.src = d_y1; p.mv = (long long)ngroups * kGroup * kChunk;
-    hipLaunchKernelGGL((k_apply<NS, CH, W>), grid, block, 0, w.stream, c, p, ngroups * kGroup, ngroups, d_zi, d_pw, d_pwG, d_pwH, (const double*)d_E2,
-                       (const double*)d_T2, d_y1, d_out, d_G, (double*)nullptr, (double*)nullptr);
-    WS_TRY(hipGetLastError());
-    WS_TRY(hipEventRecord(w.ev1, w.stream));
-    if (!on_device) WS_TRY(hipMemcpyAsync(y, w.buf[0], xbytes, hipMemcpyDeviceToHost, w.stream));
-    WS_TRY(hipStreamSynchronize(w.stream));
-    WS_TRY(hipEventElapsedTime(&w.last_ms, w.ev0, w.ev1));
-    return SSFM_OK;
-}
-
+    // d_T: the totals of the forward pass, behind them those of the backward pass; d_E2: E of the backward pass (written by the forward output kernel).
+    template <int NS, int CH, int W>
+    static void launch_three(dim3 grid, hipStream_t stream, const SosCoefs& c, SosPass p, int nchunks, int ngroups, int rows, const double* tab, const double* d_x, double* d_y1, double* d_E, double* d_T, double* d_E2, double* d_out) {
+        using Lay = ssfm::sos::TableLayout<NS, kChunk>;
+        constexpr int K = 2 * NS, kGroup = kWave * W;
+        const dim3 block(kGroup);
+        const double *d_zi = tab + Lay::zi, *d_pw = tab + Lay::pw, *d_pwG = tab + Lay::pwG, *d_pwH = tab + Lay::pwH, *d_G = tab + Lay::G;
+        double* d_T2 = d_T + (size_t)ngroups * rows * CH * K;
+        p.backward = 0; p.src = d_x; p.mv = p.m;
+        hipLaunchKernelGGL((k_chunk_scan<NS, CH, W>), grid, block, 0, stream, p, nchunks, ngroups, d_pw, d_G, d_E, d_T);
+        hipLaunchKernelGGL((k_apply<NS, CH, W>), grid, block, 0, stream, c, p, nchunks, ngroups, d_zi, d_pw, d_pwG, d_pwH, (const double*)d_E,
+                           (const double*)d_T, d_y1, d_out, d_G, d_E2, d_T2);
+        p.backward = 1; p.src = d_y1; p.mv = (long long)ngroups * kGroup * kChunk;
+        hipLaunchKernelGGL((k_apply<NS, CH, W>), grid, block, 0, stream, c, p, ngroups * kGroup, ngroups, d_zi, d_pw, d_pwG, d_pwH, (const double*)d_E2,
+                           (const double*)d_T2, d_y1, d_out, d_G, (double*)nullptr, (double*)nullptr);
+    }
+};

@@ -324,7 +324,7 @@ def _step_cols(sos, z, x, dt):
 
 
 def _tables(sos, W, L, dt):
-    """build_tables (sos_filter_impl.inc) in the type dt: the one-sample map A, P[level][j] = (M_level)^j, j = 0..64, and G."""
+    """build_tables (csrc/sos_tables.hpp) in the type dt: the one-sample map A, P[level][j] = (M_level)^j, j = 0..64, and G."""
     ns = sos.shape[0]
     K = 2 * ns
     c = np.asarray(sos, np.float64).astype(dt)
@@ -371,7 +371,7 @@ def _device_tables_cached(key, W, L):
     T.dP = 2 * np.abs(P64 - P_ld).astype(np.float64) + U * np.abs(P64)
     T.dG = 2 * np.abs(G64 - G_ld).astype(np.float64) + U * np.abs(G64)
     T.A_ld = A_ld
-    # the look-back depth as run_filter_w finds it: 1 + the last d <= 64 whose (M^group)^d has an element at or above 1e-40
+    # the look-back depth as the host finds it (csrc/sos_route.hpp look_of_group_powers): 1 + the last d <= 64 whose (M^group)^d has an element at or above 1e-40
     T.look = 1
     for d in range(1, WAVE + 1):
         if not np.abs(P64[1, d]).max() < DROP:
