@@ -24,6 +24,7 @@
 #include "ssfm_amd.h"
 #include "ssfm_common.hpp"
 #include "ssfm_kernels.hpp"
+#include "ssfm_lanes.hpp"
 #include "ssfm_launch.hpp"
 #include "ssfm_medium.hpp"
 #include "ssfm_owned.hpp"
@@ -392,17 +393,6 @@ int streams_run_side_by_side(hipStream_t a, hipStream_t b, unsigned* words /* tw
     return seen != 0u ? 1 : 0;
 }
 
-// A lane is good when its launches run beside the other lane's at (nearly) the rate they run alone: the launch period of the plan's OWN kernels with both lanes
-// running within kLaneGoodRatio x the period of lane 0 alone (healthy plans measure 1.15-1.3 x, the slow states of profiles/r04_order_dependence.txt 2.3-6 x,
-// lanes that share a hardware queue 2 x).  At run time a fixed-step run whose own launch period exceeds kLaneSlowRatio x the best period the plan has seen
-// has its lanes rated again (PlanT::lane_health).
-constexpr float kLaneGoodRatio = 1.6f;
-constexpr float kLaneGoodRatioBig = 2.1f;
-constexpr float kLaneSlowRatio = 1.8f;
-constexpr float kLaneSuspectRatio = 1.3f;        // two checked runs in a row beyond this (round 6: profiles/r05_final_lane_stability.txt had one plan at 1.37 x that 1.8 never sees)
-constexpr int kLaneDroppedCooldown = 32;         // runs after which a plan that dropped to one lane tries its second lane again
-constexpr int kLaneProbeSteps = 12;
-constexpr int kLaneHealsMax = 8;
 
 // Rated lane pairs outlive their plan (round 6): rating a fresh pair costs ~7 ms of probe launches (k_queue_probe_spin was 25 % of an
 // adaptive profile), and what the rating finds out -- which hardware queues the runtime gave the two streams -- is a property of the STREAMS, not of the plan.
@@ -585,20 +575,8 @@ template <typename T> struct PlanT : PlanBase {
     int last_engine = SSFM_ENGINE_NONE;
     int last_fell_back = 0;
     int64_t fallbacks = 0;
-    bool lanes_share_queue = false;    // the plan's lanes could not be given hardware queues of their own (see streams_run_side_by_side)
-    // ---- lane health (round 5; rate_lane / lane_health / heal_lanes below)
-    int lanes_active = 1;              // lanes a fixed-step run really drives: nlanes, or 1 once a plan that could not be healed has dropped to one lane
-    int lanes_remade = 0;              // lane streams replaced at RUN time (a run came out slow, the lanes were rated again and one was not good)
-    int lanes_dropped = 0;             // 1: the plan gave up its second lane (two healing attempts in a row found no good stream)
-    int lane_heals = 0, lane_strikes = 0, lane_suspect = 0, lane_dropped_runs = 0;
-    bool lanes_from_pool = false;      // this plan's lane pair came rated from the process's pool (no probe launches at creation)
-    int lane_fault = 0;                // test hook (ssfm_debug_lane_fault): 2 = every rating comes out "in the way"
-    float lane_alone_us = 0.f;         // launch period of lane 0's chain alone on the chip (the plan's own kernels; last rating)
-    float lane_pair_us = 0.f;          // best launch period seen with all lanes running: the last rating's, or a real run's
-    float lane_last_us = 0.f;          // launch period of the last checked fixed-step run (device time / launches per lane)
-    float lane_score = 0.f;            // last rating: period with the other lane / period alone
-    bool lane_check_pending = false;   // the last run was a two-lane run of >= 64 steps whose period has not been looked at yet
-    int64_t lane_check_launches = 0;
+    // ---- lane health (round 5; ssfm_lanes.hpp; rate_lane / lane_health / heal_lanes below measure and ask it)
+    LaneHealth lanes;
     Event lane_e0, lane_e1;      // brackets of a rating measurement
     Event run_e0, run_e1;        // brackets of the last run that lane_health looks at (its own pair: ev0 / ev1 are re-recorded by every entry point)
     // ---- z-resolved capture that does not stall the loop (propagate_fixed_capture, round 5): a stream of its own for the transfers, a ring of plan-owned
@@ -767,10 +745,10 @@ template <typename T> struct PlanT : PlanBase {
         for (auto& w : lane_worker) w.stop();
         if (stream) (void)hipStreamSynchronize(stream);
         if (cap_stream) (void)hipStreamSynchronize(cap_stream);
-        if (nlanes == 2 && lanes_ok && !lanes_dropped && !lanes_share_queue && lane_fault == 0 && stream && lane_stream[1] && lane_stream[1] != stream
+        if (lanes.pair_may_go_to_pool(nlanes) && stream && lane_stream[1] && lane_stream[1] != stream
             && !std::getenv("SSFM_LANE_POOL_OFF")) {
             (void)hipStreamSynchronize(lane_stream[1]);
-            if (lane_pool().give(LanePair{device, stream, lane_stream[1], lane_score, lane_alone_us, lane_pair_us})) {
+            if (lane_pool().give(LanePair{device, stream, lane_stream[1], lanes.lane_score, lanes.lane_alone_us, lanes.lane_pair_us})) {
                 (void)lane_stream[0].release(); (void)lane_stream[1].release();
             }
         }
@@ -816,8 +794,7 @@ template <typename T> struct PlanT : PlanBase {
         LanePair lp;
         if (shape.lanes_wanted == 2 && batch_full >= 2 && batch_full % 2 == 0 && !std::getenv("SSFM_LANE_POOL_OFF") && lane_pool().take(device, &lp)) {
             lane_stream[0].reset(lp.main); lane_stream[1].reset(lp.lane);
-            lane_score = lp.score; lane_alone_us = 0.f; lane_pair_us = 0.f;           // (the periods are this plan's own kernels': the first long run sets them)
-            lanes_from_pool = true;
+            lanes.took_pair(lp.score);
             ++g_lane_pairs_reused;
         }
         if (!lane_stream[0]) HIP_TRY(hipStreamCreateWithPriority(lane_stream[0].out(), hipStreamNonBlocking, prio_hi));
@@ -826,10 +803,10 @@ template <typename T> struct PlanT : PlanBase {
         if (const char* e = std::getenv("SSFM_LANE_THREADS")) lane_threads = std::atoi(e) != 0;
         HIP_TRY(hipEventCreateWithFlags(fork_ev.out(), hipEventDisableTiming));
         for (int g = 1; g < nlanes; ++g) {
-            if (!(lanes_from_pool && g == 1)) HIP_TRY(hipStreamCreateWithPriority(lane_stream[g].out(), hipStreamNonBlocking, prio_hi));
+            if (!(lanes.lanes_from_pool && g == 1)) HIP_TRY(hipStreamCreateWithPriority(lane_stream[g].out(), hipStreamNonBlocking, prio_hi));
             HIP_TRY(hipEventCreateWithFlags(lane_ev[g].out(), hipEventDisableTiming));
         }
-        lanes_active = nlanes;
+        lanes.streams_made(nlanes);
         return SSFM_OK;
     }
     // the fields, the twiddle tables of the two kernels and the operator's buffers
@@ -903,25 +880,16 @@ template <typename T> struct PlanT : PlanBase {
         HIP_TRY(hipMemsetAsync(dperm, 0, cb * n, stream));
         if (dperm_fly) HIP_TRY(hipMemsetAsync(dperm_fly, 0, cb * n, stream));
         bool replaced = false;
-        if (lanes_from_pool && nlanes == 2) lanes_ok = true;               // (rated by the plan that made the pair; lane_health watches the runs as for any plan)
-        else {
+        if (!lanes.pair_counts_as_rated(nlanes)) {
             ++g_lane_ratings;
             if (int rc = rate_and_replace_lanes(F, Y, P, &replaced)) return rc;
         }
-        if (!lanes_ok) lane_strikes = 1;          // (no good stream to be had now: the first run that comes out slow and cannot be healed drops the second lane)
+        lanes.created();
         HIP_TRY(hipStreamSynchronize(stream));
         return SSFM_OK;
     }
 
-    // ---- lane health.  Which hardware queue the runtime gives a lane's stream decides whether its kernels run beside the other lane's at full rate, one
-    // after the other (a shared queue) or 3-6 x slower than that (profiles/r04_order_dependence.txt); nothing in the API says which.  Round 4 rated a
-    // stream at plan creation by a proxy (dependent launches of a 3 us spin kernel) and still met about one slow plan in 25-40 suite runs, silently.
-    // Round 5: (1) the rating is the real thing -- the launch period of the plan's OWN two kernels with both lanes running against lane 0 alone;
-    // (2) every fixed-step run of >= 64 steps is looked at afterwards (lane_health: its device time / launches per lane against the best period the
-    // plan has seen); a run beyond kLaneSlowRatio has the lanes rated again on scratch buffers, a lane that is not good gets another stream
-    // (`lanes_remade`), and a plan that two healing attempts in a row could not repair drops to one lane (`lanes_dropped`: both rows in one launch on
-    // the plan's stream -- slower than two good lanes, 2-4 x faster than two bad ones).  ssfm_last_run_info reports all of it.
-    //
+    // ---- lane health: what ssfm_lanes.hpp decides on is measured here
     // Launch period [us] of `steps` steps of the two-kernel engine (BEGIN, k_freq<FLY>, MID ... END) on the lanes of `mask`, on the buffers given (zeros).
     // The lanes' queues are held by a spin kernel while the host enqueues, so that the host's enqueue rate is not part of the figure.
     int measure_lanes(unsigned mask, int steps, cx<T>* Fx, cx<T>* Yx, T* Px, float* us) {
@@ -930,7 +898,7 @@ template <typename T> struct PlanT : PlanBase {
         const int rows = batch / nlanes;
         const T hh = (T)0.0625;
         auto body = [&]() -> int {
-            hipLaunchKernelGGL(k_queue_probe_spin, dim3(1), dim3(1), 0, stream, (long long)(400 * (2 * steps + 1) * nlanes));       // (100 MHz ticks: 4 us per launch to come -- the host needs ~3)
+            hipLaunchKernelGGL(k_queue_probe_spin, dim3(1), dim3(1), 0, stream, lane_spin_ticks(steps, nlanes));
             HIP_TRY(hipEventRecord(fork_ev, stream));
             HIP_TRY(hipEventRecord(lane_e0, stream));
             for (int g = 1; g < nlanes; ++g)
@@ -962,9 +930,8 @@ template <typename T> struct PlanT : PlanBase {
         F = F0; Y = Y0; P = P0;
         return rc;
     }
-    // 0 = good, 1 = on a queue of its own but in lane 0's way (score = the ratio), 2 = shares a hardware queue with an earlier lane; < 0: error (g_err set)
-    int rate_lane(int g, cx<T>* Fx, cx<T>* Yx, T* Px, float* score, float* alone_out, float* pair_out) {
-        *score = 1e30f;
+    // One lane's rating (ssfm_lanes.hpp LaneRating) from the queue probe and four measurements; < 0: error (g_err set)
+    int rate_lane(int g, cx<T>* Fx, cx<T>* Yx, T* Px, LaneRating* out) {
         int shared = 0;
         {
             DeviceBuffer<unsigned> words;
@@ -975,27 +942,17 @@ template <typename T> struct PlanT : PlanBase {
                 shared = side == 0;
             }
         }
-        if (shared) return 2;
-        float alone = 1e30f, pair = 0.f;
-        // (rows of 32 MiB and more -- complex128 plans of 2^21 points up, the lines of long chirp-z runs: a launch is 30-100 us long, a third of the probe steps measure it as well)
-        const int probe_steps = big_rows() ? kLaneProbeSteps / 3 : kLaneProbeSteps;
-        for (int r = 0; r < 2; ++r) {           // (the slow state is erratic -- one of its readings may look good: the WORSE of two, against the better alone)
-            float a1 = 0.f, p1 = 0.f;
-            if (measure_lanes(1u, probe_steps, Fx, Yx, Px, &a1) != SSFM_OK) return -1;
-            if (measure_lanes(1u | (1u << g), probe_steps, Fx, Yx, Px, &p1) != SSFM_OK) return -1;
-            alone = a1 < alone ? a1 : alone;
-            pair = p1 > pair ? p1 : pair;
+        float alone[2] = {0.f, 0.f}, pair[2] = {0.f, 0.f};
+        const int probe_steps = lane_probe_steps(big_rows());
+        for (int r = 0; r < 2 && !shared; ++r) {
+            if (measure_lanes(1u, probe_steps, Fx, Yx, Px, &alone[r]) != SSFM_OK) return -1;
+            if (measure_lanes(1u | (1u << g), probe_steps, Fx, Yx, Px, &pair[r]) != SSFM_OK) return -1;
         }
-        *score = pair / alone;
-        *alone_out = alone; *pair_out = pair;
+        *out = ssfm::rate_lane(shared != 0, alone, pair, big_rows(), lanes.lane_fault);
 #ifdef SSFM_LANE_PROBE_DEBUG
-        std::fprintf(stderr, "lane rating: lane %d: %.2f us per launch alone, %.2f with lane 0 beside it\n", g, alone, pair);
+        if (!shared) std::fprintf(stderr, "lane rating: lane %d: %.2f us per launch alone, %.2f with lane 0 beside it\n", g, out->alone_us, out->pair_us);
 #endif
-        if (lane_fault == 2) { *score = 9.f; return 1; }
-        // Round 6: a kernel that moves 32 MiB and more per row keeps the memory system busy by itself, and its twin beside it legitimately takes up to twice as long per launch
-        // (2^22-point complex128 rows: 1.80-1.82, and two lanes are still 18 % faster per step than one launch for both rows) -- rated against 1.6 such a pair was "in the way",
-        // had four replacement streams tried in vain, was never pooled, and every such plan took 117 ms to make (tools/plan_create_time.py).  The slow states measure 2.3-6 x.
-        return *score > (big_rows() ? kLaneGoodRatioBig : kLaneGoodRatio) ? 1 : 0;
+        return 0;
     }
     bool big_rows() const { return (size_t)n * sizeof(cx<T>) >= ((size_t)32 << 20); }
     // Rate every lane beyond the first; a lane that is not good tries replacement streams four at a time -- made together, so that the runtime's
@@ -1006,60 +963,41 @@ template <typename T> struct PlanT : PlanBase {
         *replaced = false;
         bool all_good = true;
         for (int g = 1; g < nlanes; ++g) {
-            float score = 0.f, alone = 0.f, pair = 0.f;
-            int state = rate_lane(g, Fx, Yx, Px, &score, &alone, &pair);
-            if (state < 0) return fail(SSFM_ERR_HIP, "lane rating failed: %s", hipGetErrorString(hipGetLastError()));
-            for (int round = 0; round < 2 && state > 0; ++round) {
+            LaneRating have;
+            if (rate_lane(g, Fx, Yx, Px, &have) < 0) return fail(SSFM_ERR_HIP, "lane rating failed: %s", hipGetErrorString(hipGetLastError()));
+            for (int round = 0; round < 2 && have.state > 0; ++round) {
                 Stream cand[4];                  // (those that do not replace the lane's stream go when the round is over)
                 for (auto& c : cand)
                     if (hipStreamCreateWithPriority(c.out(), hipStreamNonBlocking, prio_hi) != hipSuccess) { (void)hipGetLastError(); c.reset(); }
                 for (auto& c : cand) {
-                    if (!c || state == 0) continue;
-                    float sc = 0.f, al = 0.f, pr = 0.f;
+                    if (!c || have.state == 0) continue;
+                    LaneRating rc_;
                     std::swap(c, lane_stream[g]);                       // (rated in the lane's place; swapped back unless it is better)
-                    const int st_c = rate_lane(g, Fx, Yx, Px, &sc, &al, &pr);
-                    if (st_c >= 0 && (st_c < state || (st_c == state && sc < score))) { state = st_c; score = sc; alone = al; pair = pr; *replaced = true; }
+                    if (rate_lane(g, Fx, Yx, Px, &rc_) >= 0 && lane_rating_better(rc_, have)) { have = rc_; *replaced = true; }
                     else std::swap(c, lane_stream[g]);
                 }
             }
-            if (state != 0) all_good = false;
-            if (state == 2) lanes_share_queue = true;
-            if (g == 1 || score > lane_score) lane_score = score;
-            if (state != 2) { lane_alone_us = alone; if (state == 0) lane_pair_us = pair; }
+            lanes.fold_lane(g, have, &all_good);
         }
-        if (all_good) lanes_share_queue = false;
-        lanes_ok = all_good;
+        lanes.fold_end(all_good);
         return SSFM_OK;
     }
-    bool lanes_ok = true;
     // After a two-lane run of >= 64 steps: was it as fast as this plan's lanes can be?  Called before the next run is enqueued and from ssfm_synchronize /
     // ssfm_last_propagate_ms / ssfm_last_run_info (where the run has ended anyway); waits for the run's closing event.
     int lane_health() {
-        if (lanes_dropped && nlanes == 2 && ++lane_dropped_runs >= kLaneDroppedCooldown && lane_heals < kLaneHealsMax) {
-            // a plan that gave up its second lane under contention that may have passed: one more rating on scratch fields; good lanes come back
-            lane_dropped_runs = 0;
-            const int before = lane_strikes;
+        if (lanes.cooldown_due(nlanes)) {
+            const int before = lanes.cooldown_begin();
             if (int rc = heal_lanes()) return rc;
-            if (lanes_ok) { lanes_active = nlanes; lanes_dropped = 0; lane_strikes = 0; }
-            else lane_strikes = before;
+            lanes.cooldown_end(nlanes, before);
         }
-        if (!lane_check_pending) return SSFM_OK;
-        lane_check_pending = false;
-        if (lanes_active < 2 || lane_check_launches <= 0 || !run_e1) return SSFM_OK;
+        if (!lanes.look_due(run_e1 != nullptr)) return SSFM_OK;
         HIP_TRY(hipEventSynchronize(run_e1));
         float ms = 0.f;
         HIP_TRY(hipEventElapsedTime(&ms, run_e0, run_e1));
-        lane_last_us = ms * 1e3f / (float)lane_check_launches;
-        if (lane_pair_us <= 0.f || lane_last_us < lane_pair_us) { lane_pair_us = lane_last_us; lane_suspect = 0; return SSFM_OK; }
-        if (lane_heals >= kLaneHealsMax) return SSFM_OK;
-        if (lane_last_us > kLaneSlowRatio * lane_pair_us) { lane_suspect = 0; return heal_lanes(); }
-        // a second look for the moderately slow: one such run is other work on the GPU, two in a row are rated
-        if (lane_last_us > kLaneSuspectRatio * lane_pair_us) { if (++lane_suspect >= 2) { lane_suspect = 0; return heal_lanes(); } }
-        else lane_suspect = 0;
-        return SSFM_OK;
+        return lanes.run_measured(ms) ? heal_lanes() : (int)SSFM_OK;
     }
     int heal_lanes() {
-        ++lane_heals;
+        lanes.heal_begin();
         HIP_TRY(hipStreamSynchronize(stream));
         const size_t cb = sizeof(cx<T>) * (size_t)n * batch;
         DeviceBuffer<cx<T>> Fx_own, Yx_own;          // (scratch fields that live for this rating)
@@ -1071,22 +1009,12 @@ template <typename T> struct PlanT : PlanBase {
         (void)hipMemsetAsync(Fx, 0, cb, stream);
         if (Yx != Fx) (void)hipMemsetAsync(Yx, 0, cb, stream);
         (void)hipMemsetAsync(Px, 0, sizeof(T) * (size_t)n * batch, stream);
-        const float seen = lane_pair_us;
+        const float seen = lanes.lane_pair_us;
         bool replaced = false;
         const int rc = rate_and_replace_lanes(Fx, Yx, Px, &replaced);
         (void)hipStreamSynchronize(stream);
         if (rc != SSFM_OK) return rc;
-        if (replaced) ++lanes_remade;
-        if (lanes_ok) {
-            lane_strikes = 0;
-            // nothing wrong with the lanes (any more).  Not replaced: the run was slow for another reason (other work on the GPU, a profiler) -- its period is
-            // the new normal until a faster run is seen, so that every further run at this level is not rated again
-            if (!replaced) lane_pair_us = lane_last_us;
-            else if (seen > 0.f && seen < lane_pair_us) lane_pair_us = seen;
-        } else if (++lane_strikes >= 2) {
-            lanes_active = 1;
-            lanes_dropped = 1;
-        }
+        lanes.heal_rated(replaced, seen);
         return SSFM_OK;
     }
 
@@ -1491,7 +1419,7 @@ template <typename T> struct PlanT : PlanBase {
         std::vector<const cx<T>*> tabptr;
     };
     FixedState fixed_state() {
-        return {medium_ok, medium_split_ok, phase_tables, force_fly, profiling, SSFM_TRACE != 0, op_flat_re, twA != nullptr, medium_shape(N1, N2), lanes_active, run_e0 != nullptr};
+        return {medium_ok, medium_split_ok, phase_tables, force_fly, profiling, SSFM_TRACE != 0, op_flat_re, twA != nullptr, medium_shape(N1, N2), lanes.lanes_active, run_e0 != nullptr};
     }
     int propagate_fixed(double gamma_d, const T* h, int64_t nsteps, void* snapshots) {
         if (!have_op) return fail(SSFM_ERR_STATE, "ssfm_propagate_fixed: call ssfm_set_linear_operator first");
@@ -1503,7 +1431,7 @@ template <typename T> struct PlanT : PlanBase {
         const Schedule<T> sch(h, nsteps, kMaxTables);
         if (!sch.valid())
             return fail(SSFM_ERR_INVALID, "ssfm_propagate_fixed: step %lld is %g km (must be finite and > 0)", (long long)sch.first_bad, (double)h[sch.first_bad]);
-        FixedRun fr = {(T)gamma_d, h, nsteps, &sch, lanes_active, batch / lanes_active,
+        FixedRun fr = {(T)gamma_d, h, nsteps, &sch, lanes.lanes_active, batch / lanes.lanes_active,
                        fixed_route<T>(shape, fixed_state(), FixedRequest{nsteps, sch.fits_tables(), snapshots != nullptr, cap_run != nullptr}),
                        std::vector<const cx<T>*>(sch.distinct.size(), nullptr)};
         const FixedRoute& r = fr.route;
@@ -1555,8 +1483,7 @@ template <typename T> struct PlanT : PlanBase {
         timed = true;
         if (r.health) {
             HIP_TRY(hipEventRecord(run_e1, stream));
-            lane_check_pending = true;
-            lane_check_launches = (is_split() ? 4 : 2) * nsteps + 1;
+            lanes.run_enqueued((is_split() ? 4 : 2) * nsteps + 1);
         }
         if (snapshots != nullptr) HIP_TRY(hipStreamSynchronize(stream));
         return SSFM_OK;
@@ -1795,7 +1722,7 @@ template <typename T> struct PlanT : PlanBase {
             if (!sch.valid())
                 return fail(SSFM_ERR_INVALID, "ssfm_propagate_fixed_capture: step %lld is %g km (must be finite and > 0)", (long long)sch.first_bad, (double)h[sch.first_bad]);
         }
-        const int nl = lanes_active;
+        const int nl = lanes.lanes_active;
         // the capture's own resources, made on first use
         if (int rc = ensure_cap_stream()) return rc;
         const size_t fb = sizeof(cx<T>) * (size_t)n * batch;
@@ -2833,10 +2760,8 @@ template <typename PT> static int run_info_impl(PT* P_, ssfm_run_info* info, siz
     ssfm_run_info r;
     std::memset(&r, 0, sizeof(r));
     r.engine = P_->last_engine; r.fell_back = P_->last_fell_back; r.fallbacks_total = P_->fallbacks;
-    r.lanes = P_->lanes_active; r.lanes_configured = P_->nlanes; r.lanes_share_queue = P_->lanes_share_queue ? 1 : 0; r.lanes_remade = P_->lanes_remade; r.lanes_dropped = P_->lanes_dropped;
-    r.lane_heals = P_->lane_heals;
-    r.lane_alone_us = P_->lane_alone_us; r.lane_pair_us = P_->lane_pair_us; r.lane_last_us = P_->lane_last_us; r.lane_score = P_->lane_score;
-    r.lanes_from_pool = P_->lanes_from_pool ? 1 : 0; r.lane_ratings_total = g_lane_ratings.load(); r.lane_pairs_reused = g_lane_pairs_reused.load();
+    P_->lanes.fill(&r, P_->nlanes);
+    r.lane_ratings_total = g_lane_ratings.load(); r.lane_pairs_reused = g_lane_pairs_reused.load();
     std::memcpy(info, &r, bytes < sizeof(r) ? bytes : sizeof(r));
     return SSFM_OK;
 }
@@ -3011,7 +2936,7 @@ int ssfm_debug(ssfm_plan* plan, int what, int64_t arg, void* dst) {
     }
     if (what == SSFM_DEBUG_LANE_FAULT) {
         const int mode = (int)arg;
-        WITH_PLAN(plan, (P_->lane_fault = mode, P_->lane_pair_us = mode ? P_->lane_pair_us * 0.25f : P_->lane_pair_us, (int)SSFM_OK));
+        WITH_PLAN(plan, (P_->lanes.debug_fault(mode), (int)SSFM_OK));
     }
     return fail(SSFM_ERR_INVALID, "ssfm_debug: what = %d", what);
 }

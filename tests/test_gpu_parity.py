@@ -1388,6 +1388,45 @@ def test_a_plan_whose_lane_goes_bad_heals_itself_and_a_hopeless_one_drops_to_one
         p.close()
 
 
+def test_a_plan_that_dropped_to_one_lane_tries_its_second_lane_again(monkeypatch):
+    """The way back (ssfm_lanes.hpp cooldown_due): a plan that dropped to one lane rates its lanes once more at its 32nd look -- one look per propagate_fixed
+    and synchronize call, two per last_run_info() (it synchronises first), so in the seventh run of this loop.  With the fault hook cleared the rating is the plan's own: lanes it finds good
+    (``lane_score`` <= 1.6) come back, lanes it finds in the way (a contended GPU) stay dropped; either way the heal happens once and every run's field is
+    bit-identical to the two-lane result."""
+    gv(**workloads.BENCH_GV)
+    n = 1 << 19
+    monkeypatch.setenv("SSFM_LANES", "2")
+    a = workloads.qpsk_field(n, seed=5).astype(np.complex64)
+    D = oa.devices.linear_operator(n, gv.dt, 0.2, -21.7, 0.13)
+    hs = np.full(80, 0.125, np.float32)
+    p = _lib.Plan(n, 2, _lib.C64)
+    try:
+        p.set_linear_operator(D); p.set_field(a); p.propagate_fixed(1.3, hs); p.synchronize()
+        want = p.get_field().copy()
+        assert p.last_run_info()["lanes"] == 2
+        p.lane_fault(2)
+        for _ in range(3):
+            p.set_field(a); p.propagate_fixed(1.3, hs); p.synchronize()
+        dropped = p.last_run_info()
+        assert dropped["lanes_dropped"] and dropped["lanes"] == 1, dropped
+        p.lane_fault(0)
+        infos = []
+        for _ in range(32):
+            p.set_field(a); p.propagate_fixed(1.3, hs); p.synchronize()
+            infos.append(p.last_run_info())
+            assert np.array_equal(p.get_field(), want), infos[-1]
+        heals = [i["lane_heals"] - dropped["lane_heals"] for i in infos]
+        assert heals[0] == 0 and heals[-1] == 1 and sorted(heals) == heals, heals            # the cooldown's heal happened, and happened once
+        first = infos[heals.index(1)]
+        print(f"cooldown heal after {heals.index(1) + 1} runs: lane_score {first['lane_score']:.3f}, lanes {first['lanes']}, lanes_dropped {first['lanes_dropped']}")
+        if first["lane_score"] <= 1.6:
+            assert first["lanes"] == 2 and not first["lanes_dropped"], first                   # the plan's own rating found the lanes good: they are back
+        else:
+            assert first["lanes"] == 1 and first["lanes_dropped"], first                       # (a contended machine is not a failure of the rule)
+    finally:
+        p.close()
+
+
 @pytest.mark.parametrize("rows", [1, 2, 4])
 def test_plans_of_8192_samples_take_the_one_xcd_engine(rows, monkeypatch):
     """At 8192 samples the one-XCD engine (k_medium, 64 x 128 shape) is faster than the one-workgroup-per-row kernel of the small plans
