@@ -24,6 +24,7 @@
 
 #include "ssfm_amd.h"
 #include "ssfm_common.hpp"
+#include "ssfm_capture.hpp"
 
 using ssfm::fail;
 using ssfm::grid_for;
@@ -401,10 +402,7 @@ extern "C" int ssfm_chirp_propagate(ssfm_plan* plan, int64_t plan_n, int batch, 
         else hipLaunchKernelGGL(k_chirp_control<double>, dim3(1), dim3(64), 0, t.stream, ctl, zlog, phi_max, ag, length, (int)max_steps, 1);
         if (!hip_ok(hipMemcpyAsync(&now, ctl, sizeof(now), hipMemcpyDeviceToHost, t.stream), "hipMemcpyAsync") || !hip_ok(hipStreamSynchronize(t.stream), "hipStreamSynchronize")) break;
         while (!now.done) {
-            // about (L - z) / h steps remain (the step only shrinks towards the clamp at L): queue most of them, then look
-            const double remain = now.h > 0 ? (length - (now.z - now.h)) / now.h : 1.0;
-            int chunk = remain > 1e6 ? 128 : (int)(0.75 * remain) + 1;
-            chunk = chunk < 2 ? 2 : (chunk > 128 ? 128 : chunk);
+            const int chunk = ssfm::chunk_estimate(length - (now.z - now.h), now.h, ssfm::kLineChunkMax, false);      // queue most of what remains, then look
             for (int i = 0; i < chunk && rc == SSFM_OK; ++i) {
                 rc = step(0.0, ctl, &ctl->maxbits);
                 if (f32) hipLaunchKernelGGL(k_chirp_control<float>, dim3(1), dim3(64), 0, t.stream, ctl, zlog, phi_max, ag, length, (int)max_steps, 0);

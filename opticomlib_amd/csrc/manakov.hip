@@ -28,6 +28,7 @@
 
 #include "ssfm_amd.h"
 #include "ssfm_common.hpp"
+#include "ssfm_capture.hpp"
 #include "ssfm_kernels.hpp"
 
 using ssfm::fail;
@@ -422,14 +423,8 @@ int manakov_run(ssfm_plan* plan, const ssfm::ManakovPlan& mp, double g_d, const 
     HIP_TRY(hipMemcpyAsync(&now, ctl, sizeof(now), hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     while (now.state == 0) {                      // (1: the chunk's last pass has closed the run's last step; 2: steps were queued behind it)
-        // about (L - z) / h steps remain (the step only shrinks towards the clamp at L): queue most of them, then look
-        int chunk;
-        if (chunk_arg > 0) chunk = (int)(chunk_arg > 4096 ? 4096 : chunk_arg);
-        else {
-            const double remain = now.h > 0 ? (length - (now.z - now.h)) / now.h : 1.0;
-            chunk = remain > 1e6 ? 128 : (int)(0.75 * remain) + 1;
-            chunk = chunk < 2 ? 2 : (chunk > 128 ? 128 : chunk);
-        }
+        // the caller's chunk, or: queue most of what remains, then look
+        const int chunk = chunk_arg > 0 ? (int)(chunk_arg > 4096 ? 4096 : chunk_arg) : ssfm::chunk_estimate(length - (now.z - now.h), now.h, ssfm::kLineChunkMax, false);
         for (int i = 0; i < chunk; ++i) {
             if (int rc = linear(0)) return rc;
             measure();

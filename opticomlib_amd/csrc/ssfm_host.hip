@@ -25,6 +25,7 @@
 #include "ssfm_common.hpp"
 #include "ssfm_kernels.hpp"
 #include "ssfm_lanes.hpp"
+#include "ssfm_capture.hpp"
 #include "ssfm_launch.hpp"
 #include "ssfm_medium.hpp"
 #include "ssfm_owned.hpp"
@@ -580,9 +581,8 @@ template <typename T> struct PlanT : PlanBase {
     Event lane_e0, lane_e1;      // brackets of a rating measurement
     Event run_e0, run_e1;        // brackets of the last run that lane_health looks at (its own pair: ev0 / ev1 are re-recorded by every entry point)
     // ---- z-resolved capture that does not stall the loop (propagate_fixed_capture, round 5): a stream of its own for the transfers, a ring of plan-owned
-    // device blocks of snapshots (filled by the capture steps' END launches, sent to the host by a helper thread -- cap_worker -- as they fill), the scalar log.
+    // device blocks of snapshots (laid out by ssfm_capture.hpp CapRing, filled by the capture steps' END launches, sent to the host by a helper thread -- cap_worker -- as they fill), the scalar log.
     // Nothing on the device waits across streams: a stream blocked on another stream's event slows every other queue's launches (see propagate_fixed_capture).
-    static constexpr int kCapBlocksMax = 8;
     Stream cap_stream;                                    // (ensure_cap_stream)
     std::vector<Event> cap_ev_ends[kMaxLanes];       // per lane and flush: the lane's END that filled the block
     Event cap_ev_in;                                      // on the plan's stream, ahead of the run: the input is in F
@@ -1380,24 +1380,22 @@ template <typename T> struct PlanT : PlanBase {
 
     // What a capture run (propagate_fixed_capture) adds to propagate_fixed's lanes: where the scalar log of a step goes, and what happens at a capture step.
     // Snapshot 0 (the input) and the last one (the end field) go to the host straight from F; the snapshots in between are written by the capture steps'
-    // END launches into slot j % per_block of device block (j / per_block) % nblocks, j = snapshot number - 1, and a block is sent ("flushed") when it is
+    // END launches into the ring's slots (ssfm_capture.hpp CapRing: which slot, which block, when it leaves), and a block is sent ("flushed") when it is
     // full -- by the helper thread, which waits ON THE HOST for the lanes' END events and tells the lanes' threads, through `flushes_done`, when a block may
     // be written again.
     struct CapRun {
-        int64_t every = 0;                  // > 0: snapshots
+        CapRing ring;                       // (ring.every > 0: snapshots)
+        ScalLog log = {};
         char* host = nullptr;               // the caller's buffer
         double* scalars_host = nullptr;
-        double* scal = nullptr;             // the wavefronts' pairs: [step][row][per_row][2]
-        size_t step_doubles = 0;
-        int per_row = 0, nblocks = 0, nlanes = 0;
-        size_t fb = 0;
-        int64_t per_block = 0, nsnap = 0, nflush = 0, nsteps = 0;
+        double* scal = nullptr;             // the wavefronts' pairs (ScalLog)
+        int nlanes = 0;
         std::atomic<int64_t> ends_done[kMaxLanes];     // flushes whose last END event a lane has recorded
         std::atomic<int64_t> flushes_done{0};               // flushes whose transfer is complete (their block may be written again)
         std::atomic<int64_t> input_done{0};                 // the input's transfer is complete (F may be written)
         std::atomic<int64_t> run_queued{0};                 // 1: the run is queued (ev1 recorded), 2: it failed
         std::atomic<int> failed{0};
-        double* scal_at(int64_t step, int row0) const { return scal ? scal + step_doubles * (size_t)step + (size_t)row0 * per_row * 2 : nullptr; }
+        double* scal_at(int64_t step, int row0) const { return scal ? scal + log.at(step, row0) : nullptr; }
         bool wait_for(std::atomic<int64_t>& c, int64_t want) {
             for (unsigned spins = 0; c.load(std::memory_order_acquire) < want; ++spins) {
                 if (failed.load()) return false;
@@ -1451,10 +1449,10 @@ template <typename T> struct PlanT : PlanBase {
         if (snapshots != nullptr) {
             size_t free_b = 0, total_b = 0, fb = field_bytes();
             HIP_TRY(hipMemGetInfo(&free_b, &total_b));
-            block = (int64_t)std::min<size_t>((size_t)(nsteps + 1), std::max<size_t>(1, std::min<size_t>(free_b / 2, size_t(8) << 30) / fb));
+            block = snap_block(nsteps, free_b, fb);
             HIP_TRY(dsnap.reserve(fb * (size_t)block));
         }
-        const bool whole = block == nsteps + 1;          // a small plan whose whole capture fits the device: the single launch writes every snapshot itself
+        const bool whole = snap_whole(block, nsteps);    // a small plan whose whole capture fits the device: the single launch writes every snapshot itself
         last_engine = snapshots != nullptr && !whole ? r.engine_in_blocks : r.engine;
         if (snapshots != nullptr) {
             if (int rc = r.small_sched && whole ? snapshots_small(fr, snapshots, dsnap) : snapshots_every_step(fr, snapshots, dsnap, block)) return rc;
@@ -1536,7 +1534,7 @@ template <typename T> struct PlanT : PlanBase {
     // threads run ahead of the GPU by at most the ring of blocks, the GPU never waits as long as PCIe keeps up.
     int lane_run(const FixedRun& fr, int g) {
         CapRun* const cr = cap_run;
-        const bool snaps = cr && cr->every > 0;
+        const bool snaps = cr && cr->ring.every > 0;
         auto body = [&]() -> int {
             // (round 6 A/B: starting lane 1 of a complex128 run 5 ... 40 us late changes nothing -- 38.6-39.4 against 38.6-38.9 us per step, profiles/r06_c1_ab.txt)
             HIP_TRY(col_begin(fr, g));
@@ -1544,18 +1542,17 @@ template <typename T> struct PlanT : PlanBase {
             for (int64_t s = 0; s < fr.nsteps; ++s) {
                 HIP_TRY(row_pass(fr, g, s));
                 const bool last = s + 1 == fr.nsteps;
-                if (snaps && !last && (s + 1) % cr->every == 0) {
-                    const int64_t j = k - 1, fl = j / cr->per_block, slot = j % cr->per_block;
-                    const int blk = (int)(fl % cr->nblocks);
-                    if (slot == 0 && fl >= cr->nblocks && !cr->wait_for(cr->flushes_done, fl - cr->nblocks + 1))      // the block is written again
+                if (snaps && cr->ring.captures(s)) {
+                    const CapSlot c = cr->ring.slot_of(k - 1);
+                    if (c.wait_flushes && !cr->wait_for(cr->flushes_done, c.wait_flushes))      // the block is written again
                         return fail(SSFM_ERR_HIP, "ssfm_propagate_fixed_capture: the transfers failed");
                     TimeArgs<T> te = targs(fr.gamma, fr.h[s] * (T)0.5, 0, nullptr, g * fr.rows, g);
-                    te.F = reinterpret_cast<cx<T>*>(cap_blocks + cap_block_bytes * (size_t)blk + cr->fb * (size_t)slot) + (size_t)(g * fr.rows) * n;
+                    te.F = reinterpret_cast<cx<T>*>(cap_blocks + c.offset) + (size_t)(g * fr.rows) * n;
                     ++last_launches;
                     HIP_TRY((launch_time<T, TM_END>(N1, fr.rows, lane_stream[g], te, E)));
-                    if (slot == cr->per_block - 1 || k == cr->nsnap - 2) {          // the block is full (or the last one of the run): it leaves
-                        HIP_TRY(hipEventRecord(cap_ev_ends[g][fl], lane_stream[g]));
-                        cr->ends_done[g].store(fl + 1, std::memory_order_release);
+                    if (c.leaves) {
+                        HIP_TRY(hipEventRecord(cap_ev_ends[g][c.flush], lane_stream[g]));
+                        cr->ends_done[g].store(c.flush + 1, std::memory_order_release);
                     }
                     ++k;
                 }
@@ -1669,38 +1666,37 @@ template <typename T> struct PlanT : PlanBase {
     // wavefront in its place.  In the capture run that was 1.2-1.4 ms per call (the copy stream's wait for the end of the run, queued 8 ms early -- the
     // host enqueues ahead) and 0.1 ms per snapshot (the marker behind each 0.7 ms transfer): +18-21 % at every = 100 (profiles/r05_capture_ab.txt).
     // Host waits (hipEventSynchronize, hipStreamSynchronize) put nothing into a queue.
-    static int64_t capture_count(int64_t nsteps, int64_t every) { return every > 0 ? 1 + (nsteps + every - 1) / every : 0; }
     bool in_place() const { return static_cast<const void*>(Y) == static_cast<const void*>(F); }
     int capture_helper() {
         CapRun* const cr = &cap_cr;
         auto body = [&]() -> int {
-            const bool snaps = cr->every > 0;
+            const CapRing& ring = cr->ring;
+            const bool snaps = ring.every > 0;
             if (snaps) {                                                // snapshot 0: the input, from F
                 HIP_TRY(hipEventSynchronize(cap_ev_in));
-                HIP_TRY(hipMemcpyAsync(cr->host, in_place() ? cap_in.get() : reinterpret_cast<const char*>(F), cr->fb, hipMemcpyDeviceToHost, cap_stream));
+                HIP_TRY(hipMemcpyAsync(cr->host, in_place() ? cap_in.get() : reinterpret_cast<const char*>(F), ring.fb, hipMemcpyDeviceToHost, cap_stream));
                 HIP_TRY(hipStreamSynchronize(cap_stream));
                 cr->input_done.store(1, std::memory_order_release);
             }
-            for (int64_t fl = 0; fl < cr->nflush; ++fl) {
+            for (int64_t fl = 0; fl < ring.nflush; ++fl) {
                 for (int g = 0; g < cr->nlanes; ++g) {
                     if (!cr->wait_for(cr->ends_done[g], fl + 1)) return fail(SSFM_ERR_HIP, "ssfm_propagate_fixed_capture: the run failed");
                     HIP_TRY(hipEventSynchronize(cap_ev_ends[g][fl]));
                 }
-                const int64_t first = fl * cr->per_block, count = std::min<int64_t>(cr->per_block, cr->nsnap - 2 - first);
-                HIP_TRY(hipMemcpyAsync(cr->host + cr->fb * (size_t)(1 + first), cap_blocks + cap_block_bytes * (size_t)(fl % cr->nblocks), cr->fb * (size_t)count,
-                                       hipMemcpyDeviceToHost, cap_stream));
+                const CapFlush f = ring.flush_of(fl);
+                HIP_TRY(hipMemcpyAsync(cr->host + f.host_offset, cap_blocks + f.ring_offset, f.bytes, hipMemcpyDeviceToHost, cap_stream));
                 HIP_TRY(hipStreamSynchronize(cap_stream));
                 cr->flushes_done.store(fl + 1, std::memory_order_release);
             }
             if (!cr->wait_for(cr->run_queued, 1) || cr->run_queued.load() != 1) return fail(SSFM_ERR_HIP, "ssfm_propagate_fixed_capture: the run failed");
             HIP_TRY(hipEventSynchronize(ev1));                         // the end of the run on the plan's stream: every lane has joined
-            if (snaps) HIP_TRY(hipMemcpyAsync(cr->host + cr->fb * (size_t)(cr->nsnap - 1), F, cr->fb, hipMemcpyDeviceToHost, cap_stream));      // the end field is the last snapshot
+            if (snaps) HIP_TRY(hipMemcpyAsync(cr->host + ring.end_offset(), F, ring.fb, hipMemcpyDeviceToHost, cap_stream));      // the end field is the last snapshot
             if (cr->scalars_host) {
                 // the log goes to the host behind the run: a pair (mean |A|^2, max |A|^2) per row and step
-                double* red = cr->scal + cr->step_doubles * (size_t)(cr->nsteps + 1);
-                hipLaunchKernelGGL(k_scal_reduce<0>, dim3((unsigned)((cr->nsteps + 1) * batch)), dim3(64), 0, cap_stream, (const double*)cr->scal, red, cr->per_row, 1.0 / (double)n);
+                double* red = cr->scal + cr->log.reduced_at();
+                hipLaunchKernelGGL(k_scal_reduce<0>, dim3((unsigned)((ring.nsteps + 1) * batch)), dim3(64), 0, cap_stream, (const double*)cr->scal, red, cr->log.per_row, 1.0 / (double)n);
                 HIP_TRY(hipGetLastError());
-                HIP_TRY(hipMemcpyAsync(cr->scalars_host, red, sizeof(double) * 2 * (size_t)batch * (size_t)(cr->nsteps + 1), hipMemcpyDeviceToHost, cap_stream));
+                HIP_TRY(hipMemcpyAsync(cr->scalars_host, red, cr->log.red_bytes, hipMemcpyDeviceToHost, cap_stream));
             }
             HIP_TRY(hipStreamSynchronize(cap_stream));
             return SSFM_OK;
@@ -1708,6 +1704,25 @@ template <typename T> struct PlanT : PlanBase {
         const int rc = body();
         if (rc != SSFM_OK) cr->failed.store(1);
         return rc;
+    }
+    // a capture run's own resources, made on first use: the copy stream, the ring (made anew for another block size as well), the scalar log -- the wavefronts'
+    // pairs, then the log reduced behind the run (k_scal_reduce) -- and an event per lane and flush (an event that is recorded again before its waiter has
+    // looked at it would tie a transfer to a LATER END)
+    int capture_resources(const CapRing& ring, const ScalLog& log, int nl, bool scalars) {
+        if (int rc = ensure_cap_stream()) return rc;
+        if (ring.nblocks > 0 && (cap_block_bytes != ring.block_bytes || cap_nblocks < ring.nblocks)) {
+            cap_blocks.free(); cap_block_bytes = 0; cap_nblocks = 0;
+            HIP_TRY(cap_blocks.reserve(ring.ring_bytes()));
+            cap_block_bytes = ring.block_bytes; cap_nblocks = ring.nblocks;
+        }
+        if (scalars) if (int rc = grow(cap_scal, log.bytes())) return rc;
+        for (int g = 0; g < nl; ++g)
+            while ((int64_t)cap_ev_ends[g].size() < ring.nflush) {
+                Event e;
+                HIP_TRY(hipEventCreateWithFlags(e.out(), hipEventDisableTiming));
+                cap_ev_ends[g].push_back(std::move(e));
+            }
+        return SSFM_OK;
     }
     int propagate_fixed_capture(double gamma_d, const T* h, int64_t nsteps, int64_t every, void* fields_host, double* scalars_host) {
         if (!have_op) return fail(SSFM_ERR_STATE, "ssfm_propagate_fixed_capture: call ssfm_set_linear_operator first");
@@ -1717,56 +1732,20 @@ template <typename T> struct PlanT : PlanBase {
         if (int rc = no_split("ssfm_propagate_fixed_capture")) return rc;
         if (int rc = use_device()) return rc;                          // (joins the previous capture run's helper)
         if (int rc = lane_health()) return rc;
-        {
-            const Schedule<T> sch(h, nsteps, kMaxTables);
-            if (!sch.valid())
-                return fail(SSFM_ERR_INVALID, "ssfm_propagate_fixed_capture: step %lld is %g km (must be finite and > 0)", (long long)sch.first_bad, (double)h[sch.first_bad]);
-        }
-        const int nl = lanes.lanes_active;
-        // the capture's own resources, made on first use
-        if (int rc = ensure_cap_stream()) return rc;
-        const size_t fb = sizeof(cx<T>) * (size_t)n * batch;
-        const int64_t nsnap = capture_count(nsteps, every);
-        int64_t per_block = 1, nflush = 0;
-        int nblocks = 0;
-        if (fields_host && nsnap > 2) {
-            // a block leaves for the host as soon as it is full: small blocks (8 MiB; one snapshot of a large field) keep the transfers beside the run and
-            // leave little of them behind its end; a ring of up to eight (1 GiB at most) lets the lanes' threads enqueue that far ahead of the transfers
-            per_block = (int64_t)std::max<size_t>(1, std::min<size_t>((size_t(8) << 20) / fb, 64));
-            per_block = std::min<int64_t>(per_block, nsnap - 2);
-            nflush = (nsnap - 2 + per_block - 1) / per_block;
-            const size_t bb = fb * (size_t)per_block;
-            nblocks = (int)std::min<int64_t>(nflush, std::max<int64_t>(2, std::min<int64_t>(kCapBlocksMax, (int64_t)((size_t(1) << 30) / bb))));
-            if (cap_block_bytes != bb || cap_nblocks < nblocks) {
-                cap_blocks.free(); cap_block_bytes = 0; cap_nblocks = 0;           // (another block size as well: the ring is made anew)
-                HIP_TRY(cap_blocks.reserve(bb * (size_t)nblocks));
-                cap_block_bytes = bb; cap_nblocks = nblocks;
-            }
-        }
-        // the scalar log: a pair per wavefront of the column kernels, row and step; reduced to a pair per row and step behind the run (k_scal_reduce)
-        const int per_row = (N2 / cols_per_tile<T>()) * ((N1 * cols_per_tile<T>() / E + 63) / 64);
-        const size_t step_doubles = (size_t)batch * per_row * 2, raw_b = sizeof(double) * step_doubles * (size_t)(nsteps + 1);
-        const size_t red_b = sizeof(double) * 2 * (size_t)batch * (size_t)(nsteps + 1);
-        if (scalars_host) if (int rc = grow(cap_scal, raw_b + red_b)) return rc;
-        // an event per lane and flush (an event that is recorded again before its waiter has looked at it would tie a transfer to a LATER END)
-        for (int g = 0; g < nl; ++g)
-            while ((int64_t)cap_ev_ends[g].size() < nflush) {
-                Event e;
-                HIP_TRY(hipEventCreateWithFlags(e.out(), hipEventDisableTiming));
-                cap_ev_ends[g].push_back(std::move(e));
-            }
+        if (const Schedule<T> sch(h, nsteps, kMaxTables); !sch.valid())
+            return fail(SSFM_ERR_INVALID, "ssfm_propagate_fixed_capture: step %lld is %g km (must be finite and > 0)", (long long)sch.first_bad, (double)h[sch.first_bad]);
         CapRun& cr = cap_cr;
-        cr.every = fields_host ? every : 0; cr.host = static_cast<char*>(fields_host); cr.scalars_host = scalars_host; cr.scal = scalars_host ? cap_scal.get() : nullptr;
-        cr.step_doubles = step_doubles; cr.per_row = per_row; cr.fb = fb; cr.per_block = per_block; cr.nsnap = nsnap; cr.nflush = nflush; cr.nsteps = nsteps;
-        cr.nblocks = nblocks; cr.nlanes = nl;
+        cr.ring = CapRing::make(field_bytes(), nsteps, every, fields_host != nullptr); cr.log = scal_log<T>(N1, N2, E, batch, nsteps); cr.nlanes = lanes.lanes_active;
+        if (int rc = capture_resources(cr.ring, cr.log, cr.nlanes, scalars_host != nullptr)) return rc;
+        cr.host = static_cast<char*>(fields_host); cr.scalars_host = scalars_host; cr.scal = scalars_host ? cap_scal.get() : nullptr;
         for (auto& e : cr.ends_done) e.store(0);
         cr.flushes_done.store(0); cr.input_done.store(0); cr.run_queued.store(0); cr.failed.store(0);
         if (fields_host) {
             // the input is in F once everything queued on the plan's stream so far is through.  The plans whose engine transforms F in place (Y == F:
             // complex128 and the complex64 plans outside the unit layout) overwrite it with their first launch: they keep a copy, made on the plan's stream
             if (in_place()) {
-                if (int rc = grow(cap_in, fb)) return rc;
-                HIP_TRY(hipMemcpyAsync(cap_in, F, fb, hipMemcpyDeviceToDevice, stream));
+                if (int rc = grow(cap_in, cr.ring.fb)) return rc;
+                HIP_TRY(hipMemcpyAsync(cap_in, F, cr.ring.fb, hipMemcpyDeviceToDevice, stream));
             }
             HIP_TRY(hipEventRecord(cap_ev_in, stream));
         }
@@ -1812,24 +1791,13 @@ template <typename T> struct PlanT : PlanBase {
     // a chunk's snapshots go to one half of the ring and travel to the host on a stream of their own while the next chunk runs into the other half.
     struct AdaptCap {
         bool on = false;
-        int64_t every = 0;
-        std::vector<int64_t> list;     // or: ascending step numbers (1-based: the field AFTER step s)
-        size_t next_in_list = 0;
+        CapCursor cur;                 // which steps capture, how many snapshots are out, which half of the ring is next (ssfm_capture.hpp)
+        std::vector<int64_t> list;     // the cursor's list: ascending step numbers (1-based: the field AFTER step s)
         char* host = nullptr;
-        int64_t capacity = 0;
         int64_t* taken = nullptr;      // step number of every snapshot written
         int64_t* n_taken = nullptr;
-        int64_t count = 0;             // snapshots written to the host buffer so far (or queued for it)
-        int half_slots = 0;
-        int chunk_no = 0;
     } acap;
     Event acap_ev[2];      // behind the transfers of the chunk that used half 0 / 1 of the ring (the host waits for it before that half is written again)
-    bool acap_wants(int64_t after) {
-        if (!acap.on) return false;
-        if (acap.every > 0) return after % acap.every == 0;
-        while (acap.next_in_list < acap.list.size() && acap.list[acap.next_in_list] < after) ++acap.next_in_list;
-        return acap.next_in_list < acap.list.size() && acap.list[acap.next_in_list] == after;
-    }
     int adaptive_set_capture(int64_t every, const int64_t* steps, int64_t n_steps, void* fields_host, int64_t capacity, int64_t* taken, int64_t* n_taken) {
         if (!ar.active) return fail(SSFM_ERR_STATE, "ssfm_adaptive_set_capture: call ssfm_adaptive_begin first");
         if (ar.step != 0 || (ar.deferred == ADAPT_CHUNKED && ar.now.steps != 0)) return fail(SSFM_ERR_STATE, "ssfm_adaptive_set_capture: the run has started");
@@ -1838,19 +1806,15 @@ template <typename T> struct PlanT : PlanBase {
         if (int rc = no_split("ssfm_adaptive_set_capture")) return rc;
         if (int rc = use_device()) return rc;
         acap = AdaptCap();
-        acap.on = true; acap.every = every > 0 ? every : 0;
         if (every <= 0) {
+            if (!acap_list_valid(steps, n_steps)) return fail(SSFM_ERR_INVALID, "ssfm_adaptive_set_capture: step numbers must ascend from 1");
             acap.list.assign(steps, steps + n_steps);
-            for (size_t i = 0; i < acap.list.size(); ++i)
-                if (acap.list[i] < 1 || (i && acap.list[i] <= acap.list[i - 1])) { acap.on = false; return fail(SSFM_ERR_INVALID, "ssfm_adaptive_set_capture: step numbers must ascend from 1"); }
+            acap.cur.list = acap.list.data(); acap.cur.n_list = acap.list.size();
         }
-        acap.host = static_cast<char*>(fields_host); acap.capacity = capacity; acap.taken = taken; acap.n_taken = n_taken;
+        acap.on = true; acap.cur.every = every > 0 ? every : 0; acap.cur.capacity = capacity; acap.cur.half_slots = acap_half_slots(field_bytes());
+        acap.host = static_cast<char*>(fields_host); acap.taken = taken; acap.n_taken = n_taken;
         *n_taken = 0;
-        const size_t fb = sizeof(cx<T>) * (size_t)n * batch;
-        // the ring: two halves of up to 32 snapshots, 1 GiB in all at most
-        int half = (int)std::max<size_t>(1, std::min<size_t>(32, (size_t(512) << 20) / fb));
-        acap.half_slots = half;
-        const size_t need = fb * (size_t)half * 2;
+        const size_t need = acap_ring_bytes(field_bytes());          // the ring: two halves (ssfm_capture.hpp)
         if (cap_block_bytes * (size_t)cap_nblocks < need) {
             cap_blocks.free(); cap_block_bytes = 0; cap_nblocks = 0;
             HIP_TRY(cap_blocks.reserve(need));
@@ -1886,7 +1850,6 @@ template <typename T> struct PlanT : PlanBase {
         ar.deferred = route;
         return SSFM_OK;
     }
-    static constexpr int kAdaptChunkMax = 512;          // steps queued between two looks at the state, at most
     AdaptState<T> adapt_host;          // staging copy of the run's parameters (a member: the copy below is asynchronous)
     // what the host reads back during an adaptive run (the step state, the give-up word) lands in page-locked memory: a transfer of a few bytes into
     // pageable memory goes through the runtime's staging path (measured per look at the state: profiles/r05_adaptive_looks.txt)
@@ -1994,13 +1957,7 @@ template <typename T> struct PlanT : PlanBase {
         return SSFM_OK;
     }
     // ---- the chunked engine: up to `budget` more steps, queued in chunks with a look at the state in between
-    int adaptive_estimate() const {              // about (L - z) / h steps remain (the step only shrinks towards the clamp at L)
-        // Three quarters of them are queued before the next look at the state (a look drains the queue: 25-40 us) -- but the last two dozen all at
-        // once and two more: launches behind the end of the run find `done` and leave (a few us each), where the looks of a tail of 7, 2, 1 steps cost more
-        const double remain = ar.now.h > (T)0 ? ((double)ar.length - (double)ar.now.z) / (double)ar.now.h : 1.0;
-        const int est = remain > 1e6 ? kAdaptChunkMax : (remain <= 24.0 ? (int)remain + 3 : (int)(0.75 * remain) + 1);
-        return est < 2 ? 2 : (est > kAdaptChunkMax ? kAdaptChunkMax : est);
-    }
+    int adaptive_estimate() const { return chunk_estimate((double)ar.length - (double)ar.now.z, (double)ar.now.h, kAdaptChunkMax, true); }
     int adaptive_chunks(int64_t budget, void* snapshots, int* engine) {
         const AdaptPiece piece = adaptive_in_pieces(AdaptPiece{ar.fused, ar.tile_private}, shape, ar.step, budget, ar.max_steps);
         ar.fused = piece.fused; ar.tile_private = piece.tile_private;
@@ -2013,22 +1970,13 @@ template <typename T> struct PlanT : PlanBase {
         if (acap.on && snap) return fail(SSFM_ERR_STATE, "ssfm_adaptive_run: either ssfm_adaptive_set_capture or `snapshots`");
         while (!ar.now.done && ar.now.steps - first_step < budget) {
             *engine = adaptive_engine(shape, ar.fused);
-            if ((int64_t)chunk > budget - (ar.now.steps - first_step)) chunk = (int)(budget - (ar.now.steps - first_step));
-            // a capture run: this chunk's snapshots go to half (chunk_no & 1) of the ring, whose transfers of two chunks ago are waited for ON THE HOST
+            chunk = chunk_next(chunk, budget - (ar.now.steps - first_step), acap.on ? acap.cur.every : 0, ar.step);
+            // a capture run: this chunk's snapshots go to one half of the ring, whose transfers of two chunks ago are waited for ON THE HOST
             std::vector<int64_t> chunk_caps;
             char* ring_half = nullptr;
             if (acap.on) {
-                // (short chunks: a chunk's snapshots only leave at the look behind it, and the transfers should run beside the NEXT chunk's kernels -- four
-                // snapshots per chunk, 64 steps at least; a look drains the queue for ~40 us)
-                if (acap.every > 0 && (int64_t)chunk > std::max<int64_t>(64, acap.every * 4)) chunk = (int)std::max<int64_t>(64, acap.every * 4);
-                // ... and a chunk ends right behind a capture step where it can, so that the snapshot leaves at once (the last ones of a run would otherwise
-                // travel behind its end)
-                if (acap.every > 0 && (int64_t)chunk > acap.every) {
-                    const int64_t end = (((int64_t)ar.step + chunk) / acap.every) * acap.every;
-                    if (end > (int64_t)ar.step) chunk = (int)(end - (int64_t)ar.step);
-                }
-                if (acap.chunk_no >= 2) HIP_TRY(hipEventSynchronize(acap_ev[acap.chunk_no & 1]));      // (the transfers of the chunk before the last: NOT the last chunk's, which run beside this one)
-                ring_half = cap_blocks + fb * (size_t)acap.half_slots * (size_t)(acap.chunk_no & 1);
+                if (acap.cur.half_in_use()) HIP_TRY(hipEventSynchronize(acap_ev[acap.cur.half()]));
+                ring_half = cap_blocks + acap.cur.half_offset(fb);
             }
             if (int rc = adaptive_enqueue_chunk(chunk, fly_imag, ring_half, chunk_caps)) return rc;
             const int before = ar.now.steps;
@@ -2071,14 +2019,14 @@ template <typename T> struct PlanT : PlanBase {
                 HIP_TRY((launch_freq<T, FM_FLY_IM>(N2, N1 * batch, stream, fa, Ef_fly)));
             } else
             HIP_TRY((launch_freq<T, FM_FLY>(N2, N1 * batch, stream, fa, Ef_fly)));
-            if (acap.on && acap_wants((int64_t)ar.step + 1) && acap.count + (int64_t)chunk_caps.size() < acap.capacity) {
+            if (acap.on && acap.cur.wants((int64_t)ar.step + 1) && acap.cur.room(chunk_caps.size())) {
                 // the capture step's extra launch: this step's time-order field into a ring slot (the step size is the device's: cur[step & 1])
                 TimeArgs<T> tc = te;
                 tc.F = reinterpret_cast<cx<T>*>(ring_half + fb * chunk_caps.size());
                 HIP_TRY((launch_time<T, TM_END>(N1, batch, stream, tc, E)));
                 ++last_launches;
                 chunk_caps.push_back((int64_t)ar.step + 1);
-                if ((int)chunk_caps.size() >= acap.half_slots || (acap.every == 0 && chunk_caps.size() >= 4 && i + 1 >= 64)) chunk = i + 1;          // (the half is full / enough to send: look at the state)
+                if (acap.cur.cut(chunk_caps.size(), i)) chunk = i + 1;          // (the half is full / enough to send: look at the state)
             }
             if (ar.fused) HIP_TRY((launch_time<T, TM_MID_A>(N1, batch, stream, te, E)));
             else if (ar.tile_private) HIP_TRY((launch_time<T, TM_END_Y>(N1, batch, stream, te, E)));
@@ -2104,20 +2052,20 @@ template <typename T> struct PlanT : PlanBase {
     // send the chunk's snapshots: the chunk has run (the look waited for it), its snapshots of steps really taken leave for the host beside the next chunk
     int adaptive_send_snapshots(const std::vector<int64_t>& chunk_caps, const char* ring_half) {
         const size_t fb = field_bytes();
-        for (size_t k = 0; k < chunk_caps.size(); ++k) {
-            if (chunk_caps[k] > (int64_t)ar.now.steps) break;                       // (queued behind the end of the run: never written)
-            HIP_TRY(hipMemcpyAsync(acap.host + fb * (size_t)acap.count, ring_half + fb * k, fb, hipMemcpyDeviceToHost, cap_stream));
-            acap.taken[acap.count++] = chunk_caps[k];
+        const size_t taken = caps_taken(chunk_caps.data(), chunk_caps.size(), ar.now.steps);      // (the rest was queued behind the end of the run: never written)
+        for (size_t k = 0; k < taken; ++k) {
+            HIP_TRY(hipMemcpyAsync(acap.host + fb * (size_t)(acap.cur.count + k), ring_half + fb * k, fb, hipMemcpyDeviceToHost, cap_stream));
+            acap.taken[acap.cur.count + k] = chunk_caps[k];
         }
-        *acap.n_taken = acap.count;
-        HIP_TRY(hipEventRecord(acap_ev[acap.chunk_no & 1], cap_stream));
-        ++acap.chunk_no;
+        *acap.n_taken = acap.cur.count + (int64_t)taken;
+        HIP_TRY(hipEventRecord(acap_ev[acap.cur.half()], cap_stream));
+        acap.cur.sent((int64_t)taken);
         return SSFM_OK;
     }
     // fall back from fused: the grid did not run as a whole (another job holds CUs) -- the same run again on the three-launch engine
     int adaptive_fall_back() {
         const AdaptRun keep = ar;
-        if (acap.on) { HIP_TRY(hipStreamSynchronize(cap_stream)); acap.count = 0; acap.next_in_list = 0; acap.chunk_no = 0; *acap.n_taken = 0; }
+        if (acap.on) { HIP_TRY(hipStreamSynchronize(cap_stream)); acap.cur.reset(); *acap.n_taken = 0; }
         fused_ok = false;
         last_fell_back = 1;
         ++fallbacks;

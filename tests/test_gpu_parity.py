@@ -1231,6 +1231,69 @@ def test_strided_capture_with_more_snapshots_than_device_blocks(log2n, nsteps, e
         p.close()
 
 
+def _capture_against_plain_runs(p, a, hs, cap, check):
+    """Snapshot s_ of an every-step strided capture against a plain run of s_ steps: bit for bit where that run is the two-kernel engine's."""
+    for s_ in check:
+        p.set_field(a); p.propagate_fixed(1.3, hs[:s_]); p.synchronize()
+        if p.last_run_info()["engine"] == "two_kernel":
+            np.testing.assert_array_equal(cap["fields"][s_], p.get_field())
+        else:
+            assert within(cap["fields"][s_], p.get_field(), 0.5 * tol_at(s_), steps=s_, what="snapshot (two-kernel engine) against a plain run (one-launch engine)")
+
+
+@pytest.mark.parametrize("nsteps", [33, 34, 257, 258])
+def test_strided_capture_at_the_seams_of_the_ring(nsteps):
+    """The ring of a 2^14 x 2 complex64 capture (256 KiB per field) is eight blocks of 32 snapshots (ssfm_capture.hpp CapRing).  With a snapshot at every step,
+    33 / 34 / 257 / 258 steps leave 32 / 33 / 256 / 257 snapshots between the input and the end field: one block exactly, one snapshot into a second block,
+    the ring exactly full, and the first block written again behind its wait.  Input and end field bit for bit, all snapshots against the plan's own
+    every-step capture, and the snapshots on either side of each seam against plain runs of that many steps."""
+    n = 1 << 14
+    gv(**workloads.BENCH_GV)
+    a = workloads.qpsk_field(n, seed=37, n_pol=2).astype(np.complex64)
+    D = oa.devices.linear_operator(n, gv.dt, 0.2, -21.7, 0.13)
+    hs = np.full(nsteps, 0.05, dtype=np.float32)
+    p = _lib.Plan(n, 2, _lib.C64)
+    try:
+        p.set_linear_operator(D)
+        p.set_field(a)
+        cap = p.propagate_fixed_capture(1.3, hs, every=1)
+        end = p.get_field()
+        assert list(cap["steps"]) == list(range(nsteps + 1))
+        np.testing.assert_array_equal(cap["fields"][0], a)
+        np.testing.assert_array_equal(cap["fields"][-1], end)
+        p.set_field(a)
+        every_step = p.propagate_fixed(1.3, hs, snapshots=True)
+        assert within(cap["fields"], every_step, 0.5 * tol_at(nsteps), steps=nsteps, what="strided capture against the every-step capture, all snapshots")
+        _capture_against_plain_runs(p, a, hs, cap, [s_ for s_ in (32, 33, 256, 257) if s_ <= nsteps])
+    finally:
+        p.close()
+
+
+@pytest.mark.parametrize("nsteps", [9, 10])
+def test_strided_capture_of_two_lanes_at_the_seams_of_the_ring(nsteps, monkeypatch):
+    """Two lanes fill the ring: a 2^19 x 2 complex64 field is 8 MiB, one snapshot per block, eight blocks.  With a snapshot at every step, 9 steps fill the
+    ring exactly and 10 write its first block again -- both lanes' threads wait for the same transfer.  Every snapshot against a plain run."""
+    n = 1 << 19
+    gv(**workloads.BENCH_GV)
+    monkeypatch.setenv("SSFM_LANES", "2")
+    a = workloads.qpsk_field(n, seed=31, n_pol=2).astype(np.complex64)
+    D = oa.devices.linear_operator(n, gv.dt, 0.2, -21.7, 0.13)
+    hs = np.full(nsteps, 0.05, dtype=np.float32)
+    p = _lib.Plan(n, 2, _lib.C64)
+    try:
+        assert p.lanes == 2
+        p.set_linear_operator(D)
+        p.set_field(a)
+        cap = p.propagate_fixed_capture(1.3, hs, every=1)
+        end = p.get_field()
+        assert list(cap["steps"]) == list(range(nsteps + 1))
+        np.testing.assert_array_equal(cap["fields"][0], a)
+        np.testing.assert_array_equal(cap["fields"][-1], end)
+        _capture_against_plain_runs(p, a, hs, cap, range(1, nsteps + 1))
+    finally:
+        p.close()
+
+
 @pytest.mark.parametrize("log2n,npol,lanes", [(14, 2, 1), (16, 1, 1), (19, 2, 2), (20, 2, 2)])
 def test_strided_capture_and_scalar_log_against_the_plain_run(log2n, npol, lanes, monkeypatch):
     """ssfm_propagate_fixed_capture at the plan level, one lane and two: every snapshot is bit for bit the field a plain run of that many steps leaves (the same
@@ -3678,6 +3741,48 @@ def test_adaptive_capture_keeps_the_engine_and_every_snapshot_is_a_plain_run_sto
         np.testing.assert_array_equal(fields3[-1], plain_end)                                   # the capture at the last step is the end field
         if steps // 2 % every == 0:
             np.testing.assert_array_equal(fields3[2], fields[steps // 2 // every - 1])
+    finally:
+        p.close()
+
+
+ADAPT_SEAMS_LENGTH = 20.0        # km: the field and link of the test above, lengthened until the run takes 80 ... 400 steps
+
+
+def test_adaptive_capture_at_the_seams_of_its_ring():
+    """An adaptive run of 2^14 x 2 complex64 samples that captures EVERY step: a chunk's snapshots fill one half of the ring (32 slots: ssfm_capture.hpp
+    CapCursor), so a run of more than 64 steps fills a half, the other, and the first again behind the wait for its transfers.  All steps are taken in
+    order, the last snapshot is the end field bit for bit, the snapshots at multiples of 7 are those of an every = 7 capture bit for bit (the same engine,
+    the same launches), a capacity of 5 stops the capture and not the run, and a list reaches the list's own cut (four snapshots, 64 steps)."""
+    n = 1 << 14
+    gv(**workloads.BENCH_GV)
+    a = workloads.qpsk_field(n, seed=90 + 14, n_pol=2, power_w=10e-3).astype(np.complex64)
+    D = oa.devices.linear_operator(n, gv.dt, 0.2, -21.7, 0.13, _lib.C64)
+    L = ADAPT_SEAMS_LENGTH
+    p = _lib.Plan(n, 2, _lib.C64)
+    try:
+        p.set_linear_operator(D)
+        p.set_field(a)
+        steps, _, _ = p.propagate_adaptive(1.3, L, 0.004, False)
+        print(f"adaptive run over {L} km: {steps} steps")
+        assert 80 <= steps <= 400 and steps > 2 * 32
+        p.set_field(a)
+        s1, z1, taken, fields = p.propagate_adaptive_capture(1.3, L, 0.004, every=1, capacity=steps)
+        end = p.get_field()
+        assert s1 == steps and list(taken) == list(range(1, steps + 1)) and fields.shape == (steps, 2, n)
+        np.testing.assert_array_equal(fields[-1], end)
+        p.set_field(a)
+        s7, z7, taken7, fields7 = p.propagate_adaptive_capture(1.3, L, 0.004, every=7, capacity=steps // 7 + 2)
+        assert s7 == steps and np.array_equal(z7, z1) and list(taken7) == list(range(7, steps + 1, 7))
+        np.testing.assert_array_equal(fields7, fields[6::7])
+        np.testing.assert_array_equal(p.get_field(), end)
+        p.set_field(a)
+        s5, z5, taken5, fields5 = p.propagate_adaptive_capture(1.3, L, 0.004, every=1, capacity=5)
+        assert s5 == steps and np.array_equal(z5, z1) and list(taken5) == [1, 2, 3, 4, 5]
+        np.testing.assert_array_equal(p.get_field(), end)
+        want = np.array([1, 2, 3, 4, 5, 70, steps], dtype=np.int64)
+        p.set_field(a)
+        sl, zl, takenl, _ = p.propagate_adaptive_capture(1.3, L, 0.004, steps=want)
+        assert sl == steps and np.array_equal(zl, z1) and list(takenl) == list(want)
     finally:
         p.close()
 
