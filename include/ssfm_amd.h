@@ -66,6 +66,8 @@
  *     typing.py:1971-2041)
  *   typing.py:2577-2808 (eye.plot: the grid, the   ssfm_eye_fold_range (minimum, maximum, non-finite flag of a general fold's points and of those a phase mask
  *     traces' colours, the side histogram)         passes), ssfm_eye_fold_density (ssfm_eye_density of the fold, and np.histogram of the masked points)
+ *   (none: the reference has no coherent           ssfm_qam_encode, ssfm_qam_decide, ssfm_qam_sums (mapper, decisions, alignment and EVM sums),
+ *     receiver)                                    ssfm_cpr_power, ssfm_cpr_search (blind phase search of a record read where it lies)
  *   (none: NumPy arrays are the reference's only   ssfm_device_alloc / _free / _copy / _convert / _add
  *     data format)                                 -- device-resident signals between calls
  *
@@ -777,6 +779,39 @@ SSFM_API int ssfm_eye_fold_density(const double* y, int64_t n, int64_t start, in
                                    const double* yedges, const int32_t* xbin, const double* weights, int64_t radius, uint32_t* counts, double* grid,
                                    const int32_t* xidx, double min_y, double max_y, double* points, int32_t* iy, double* colors, const uint8_t* mask,
                                    int64_t hbins, const double* hedges, uint32_t* hist);
+
+/* The coherent square-QAM receiver (no counterpart in the reference, whose receivers detect intensity): Gray mapper, decisions, blind phase search
+ * and the sums behind the quarter-turn alignment and the error vector magnitude.  M is 4, 16, 64 or 256; k = log2 M bits per symbol, MSB first, the
+ * first k / 2 the in-phase level and the last k / 2 the quadrature level, each read as a binary-reflected Gray code: level g of L = sqrt(M) has the
+ * amplitude a (2 g - (L - 1)).  The half-spacing `a` is the caller's double (1 / sqrt(2 (M - 1) / 3) for unit mean power).  A real component x is
+ * decided as g = clip(floor(x / (2 a) + L / 2), 0, L - 1): a value on a boundary takes the upper level, +-0 gives L / 2.  Everything is float64;
+ * symbol arrays are complex128 in DEVICE memory unless said otherwise.  As ssfm_signal_*: no device argument -- the work runs on the device that owns
+ * the first pointer (`bits` / `z` / `x`), which becomes the calling thread's device; a pointer that is not device memory is SSFM_ERR_INVALID.  Default stream; each call has finished its work when it returns.  No atomics
+ * and no float sum in an order the schedule decides: the same bits on every call.
+ *   ssfm_qam_encode   out (nsym complex128) from nsym k bits (DEVICE uint8, a nonzero byte is a 1).
+ *   ssfm_qam_decide   z (n complex128) is turned by i^-turns (turns in 0 ... 3: exact) and decided; bits (n k uint8) or turned (the turned
+ *                     symbols) may be NULL, not both.
+ *   ssfm_qam_sums     out (HOST, 4) = Re and Im of sum z conj(s), sum |i^-turns z - s|^2, sum |s|^2 over n >= 1 symbols, where s is ref (DEVICE,
+ *                     n complex128) or, with ref = NULL, the decision of the turned z (M and a are then required).  Partial sums per workgroup in a
+ *                     fixed tree, added in workgroup order.
+ * A record of the phase search is read where it lies: symbol k of row r is x[r pitch + start + k step] (complex64 when is_c64, else complex128), rows
+ * = 1 or 2, 1 <= n <= 2^26, step >= 1, start + (n - 1) step < pitch.  A complex64 sample is widened exactly.
+ *   ssfm_cpr_power    out (HOST, rows) = mean |x|^2 of each row's n symbols.
+ *   ssfm_cpr_search   blind phase search of y = scale[r] x (scale: HOST, rows values) with B = test_phases (even, 2 ... 64) and W = window (0 ... 256):
+ *                     table (HOST, 2 B doubles) holds exp(-i phi_b) = (re, im), phi_b = (b - B / 2) phase_step, and travels inside the launch;
+ *                     d_kb = |r - dec(r)|^2 with r = y_k exp(-i phi_b); s_kb = the sum of d_jb over max(0, k - W) <= j <= min(n - 1, k + W), formed
+ *                     from its own terms for every k (nothing is carried from one symbol's sum to the next); b_k = the first b of the smallest s_kb;
+ *                     jump_k = -1 if 2 (b_k - b_(k-1)) > B, +1 if it is < -B, else 0, jump_0 = 0; n_k = the sum of the jumps up to k.
+ *                     index (DEVICE, rows n int32) = u_k = b_k + B n_k, phase (DEVICE, rows n float64) = (u_k - B / 2) phase_step, symbols (DEVICE,
+ *                     rows n complex128) = y_k exp(-i phi_(b_k)) (-i)^(n_k).  Three launches; the rows are independent.  A non-finite sample is
+ *                     outside the contract: every output is still written, and since a NaN compares false b_k stays where the comparison leaves
+ *                     it.  Limits other than these are SSFM_ERR_INVALID before any launch. */
+SSFM_API int ssfm_qam_encode(const unsigned char* bits, int64_t nsym, int M, double a, void* out);
+SSFM_API int ssfm_qam_decide(const void* z, int64_t n, int M, double a, int turns, unsigned char* bits, void* turned);
+SSFM_API int ssfm_qam_sums(const void* z, const void* ref, int64_t n, int M, double a, int turns, double* out);
+SSFM_API int ssfm_cpr_power(const void* x, int is_c64, int rows, int64_t n, int64_t start, int64_t step, int64_t pitch, double* out);
+SSFM_API int ssfm_cpr_search(const void* x, int is_c64, int rows, int64_t n, int64_t start, int64_t step, int64_t pitch, const double* scale, int M,
+                             double a, int test_phases, int window, const double* table, double phase_step, int32_t* index, double* phase, void* symbols);
 
 #ifdef __cplusplus
 }

@@ -136,6 +136,11 @@ SYMBOLS = {
     "ssfm_eye_fold_range": (_I, [_VP, _I64, _I64, _I64, _I64, _VP, C.POINTER(_D)]),
     "ssfm_eye_fold_density": (_I, [_VP, _I64, _I64, _I64, _I64, _I64, _I64, _I64, _VP, _VP, _VP, _I64, _VP, _VP, _VP, _D, _D, _VP, _VP, _VP, _VP, _I64,
                                    _VP, _VP]),
+    "ssfm_qam_encode": (_I, [_VP, _I64, _I, _D, _VP]),
+    "ssfm_qam_decide": (_I, [_VP, _I64, _I, _D, _I, _VP, _VP]),
+    "ssfm_qam_sums": (_I, [_VP, _VP, _I64, _I, _D, _I, C.POINTER(_D)]),
+    "ssfm_cpr_power": (_I, [_VP, _I, _I, _I64, _I64, _I64, _I64, C.POINTER(_D)]),
+    "ssfm_cpr_search": (_I, [_VP, _I, _I, _I64, _I64, _I64, _I64, C.POINTER(_D), _I, _D, _I, _I, C.POINTER(_D), _D, _VP, _VP, _VP]),
 }
 
 
@@ -352,14 +357,14 @@ def host_empty(shape, dtype, limit: int = 256 << 20) -> np.ndarray:
 class DeviceArray:
     """A C-contiguous array in the HBM of one GPU: what a signal object holds between device calls.
 
-    ``dtype`` is complex64, complex128, float64, uint8 (bit sequences) or int64 (ADC codes).  The buffer goes back to the library's
+    ``dtype`` is complex64, complex128, float64, uint8 (bit sequences), int64 (ADC codes) or int32 (phase indices).  The buffer goes back to the library's
     pool when the object is collected.  ``__cuda_array_interface__`` lets torch / RCCL use the memory where it lies."""
 
     def __init__(self, shape, dtype, device: int = 0):
         self.shape = tuple(int(d) for d in np.atleast_1d(shape)) if not isinstance(shape, tuple) else tuple(int(d) for d in shape)
         self.dtype = np.dtype(dtype)
-        if self.dtype not in (np.dtype(np.complex64), np.dtype(np.complex128), np.dtype(np.float64), np.dtype(np.uint8), np.dtype(np.int64)):
-            raise TypeError(f"DeviceArray supports complex64, complex128, float64, uint8 and int64, not {self.dtype}")
+        if self.dtype not in (np.dtype(np.complex64), np.dtype(np.complex128), np.dtype(np.float64), np.dtype(np.uint8), np.dtype(np.int64), np.dtype(np.int32)):
+            raise TypeError(f"DeviceArray supports complex64, complex128, float64, uint8, int64 and int32, not {self.dtype}")
         self.device = int(device)
         self.nbytes = int(np.prod(self.shape)) * self.dtype.itemsize
         self.ptr = 0
